@@ -13,13 +13,25 @@ HIP kernels) -> gradient all-reduce (RCCL, overlapped with backward; N>1 only) -
 Workload at N=1: BASELINE.json configs[1] ("C2"): d=512, 6 layers, 8 heads x 64, mlp 1024, T_v=196 + T_a=128 = 324
 tokens, B=32 per GPU, bf16 MFMA compute with fp32 accumulate/residual.  Weak scaling: B=32 per GPU at every N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel class, timed
-live with HIP events on the launch stream during the timed steps) and `cpu_baseline` (the CPU oracle - a port of the
-reference's math - timed on this host, rank 0, N=1 only, bounded sample).  Beside the contract's fields the line carries
-`north_star_shape` (a second timed region, same step, at B=32 T=512 d=512 - the shape the >=30 % MFMA target is quoted
-on - with per-kernel-class TFLOP/s and fraction of the bf16 MFMA peak) and `f32_parity_clips_per_s` (the fp32 parity mode
-on the main workload, N=1).  `roofline.traffic` comes from the committed PMC profile only while that profile was
-collected from the kernel sources in this tree (hash stamp), else null.
+Prints ONE JSON line on rank 0.  A plain run does only what its headline figure needs: set-up, W warm-up steps, the K timed
+steps, the outputs of the last timed step if --dump-outputs is given, the line (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the workload).  The timed steps start from the training state the W warm-up steps left (saved
+after them and restored in place before the timed region, whatever untimed steps came in between), so that with the same
+arguments the last timed step sees the same weights, optimizer state and batch in every run.
+
+--full adds everything else, as before this option existed: `roofline` (dominant kernel class, timed with HIP events attached
+to every dispatch over K instrumented steps after the timed regions) and `cpu_baseline` (the CPU oracle - a port of the
+reference's math - timed on this host, rank 0, N=1 only, bounded sample); the same steps launched eagerly and fwd+bwd alone
+beside the main region; the clock and power the box allowed; `north_star_shape` (a second timed region, same step, at B=32
+T=512 d=512 - the shape the >=30 % MFMA target is quoted on - with per-kernel-class TFLOP/s and fraction of the bf16 MFMA
+peak), `residual_f32` and `f32_parity_clips_per_s` (the fp32 parity mode on the main workload, N=1); with several ranks the
+data-parallel report. `roofline.traffic` comes from the committed PMC profile only while that profile was collected from the
+kernel sources in this tree (hash stamp), else null.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller as DIR/<name>.npy (float32):
+`loss`, `logits` (the [B, 21] rows, AU logits in 0..11), and `params` / `grads` (the parameters after the optimizer step and
+the gradients that made it, flattened and concatenated in named_parameters() order: all of them, or the same seeded sample of
+DUMP_SAMPLE positions when there are more).  Rank 0's outputs.
 """
 import argparse
 import json
@@ -43,6 +55,7 @@ PKG_DIR = "multi-modal-multi-label-facial-action-unit-detection-with-transformer
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3, "mx8": 2500.0, "mx8-fwd": 2500.0}  # dense, /opt/skills/guides/MI355X_MICROARCH.md
 MX8_PEAK_TFLOPS = 5000.0  # the MX-scaled fp8 MFMA (kernel class gemm_mx8_nt only; attention, dW and dqkv -> dh1 stay bf16)
 HBM_PEAK_GBS = 8000.0
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: at most this many parameter / gradient values each (8 MB per file)
 
 
 def stack_flops_fwd(c, B):
@@ -116,6 +129,18 @@ def pmc_traffic(kernel_class, workload):
             return None, f"{os.path.basename(path)} was collected from other kernel sources ({j.get('kernel_sources_sha')} != {cur})"
         return (None if v is None else round(float(v))), f"{os.path.basename(path)} @ {j.get('commit', '?')}"
     return None, "no PMC profile committed for this workload"
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: {total} bytes of outputs, more than the 64 MB --dump-outputs allows")
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def spawn_ranks(n):
@@ -202,6 +227,9 @@ class Region:
                 dp.finish()
             if opt is not None:
                 opt.step()
+            # what the step hands its caller, for --dump-outputs (detached: no autograd graph may live on into a capture;
+            # under capture these are the graph's static tensors, which every replay rewrites)
+            self.last_out = (out.detach(), loss.detach())
             return loss
 
         self.step = step
@@ -230,11 +258,69 @@ class Region:
             self.dist.barrier()
             self.torch.cuda.synchronize()
 
-    def timed(self, steps, warmup, graph=False, eager_too=True):
-        """W untimed steps, then exactly K steps between two fences, no instrumentation; MAX over ranks"""
+    def _state(self):
+        """every tensor a step rewrites, by a stable name: the parameters (fp32 masters), the module buffers, the optimizer
+        state (moments, step counters), the stacks' bf16 weight images (the library Adam rewrites them in its pass) and their
+        dropout seed counters"""
+        torch = self.torch
+        st = {"p." + n: p for n, p in self.model.named_parameters()}
+        st.update({"b." + n: b for n, b in self.model.named_buffers()})
+        if self.opt is not None:
+            for i, p in enumerate(q for g in self.opt.param_groups for q in g["params"]):
+                for k, v in self.opt.state.get(p, {}).items():
+                    if torch.is_tensor(v):
+                        st[f"o.{i}.{k}"] = v
+        for n, m in self.model.named_modules():
+            for i, b in enumerate(m.__dict__.get("_lowp_bufs") or []):
+                st[f"w.{n}.{i}"] = b
+            if m.__dict__.get("_seed_dev") is not None:
+                st[f"s.{n}"] = m._seed_dev
+        return st
+
+    def save_state(self):
+        """keep a copy of the training state (one copy per storage: the optimizer's step counter is shared)"""
+        copies = {}
+        self._saved = {}
+        for k, t in self._state().items():
+            key = (t.data_ptr(), t.numel(), t.dtype)
+            if key not in copies:
+                copies[key] = t.detach().clone()
+            self._saved[k] = copies[key]
+
+    def restore_state(self):
+        """write the saved training state back into the SAME tensors (a captured graph keeps reading them).  Through `.data`:
+        the parameters' version counters stay as they are, so the library Adam's images stay valid for the next forward"""
+        with self.torch.no_grad():
+            for k, t in self._state().items():
+                src = self._saved.get(k)
+                if src is None or src.shape != t.shape:
+                    raise RuntimeError(f"bench.py: training state {k} appeared or changed shape after it was saved")
+                t.data.copy_(src)
+
+    def collect_outputs(self):
+        """the last step's outputs as host arrays (see --dump-outputs)"""
+        torch = self.torch
+        out, loss = self.last_out
+        ps = [p for _, p in self.model.named_parameters()]
+        params = torch.cat([p.detach().reshape(-1).float() for p in ps])
+        grads = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().reshape(-1).float() for p in ps])
+        if params.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            idx = idx.to(params.device)
+            params, grads = params[idx], grads[idx]
+        return {"loss": loss.float().cpu().numpy(), "logits": out.float().cpu().numpy(),
+                "params": params.cpu().numpy(), "grads": grads.cpu().numpy()}
+
+    def timed(self, steps, warmup, graph=False, eager_too=True, fwd_bwd=True, dump=False):
+        """W untimed steps, then exactly K steps between two fences, no instrumentation; MAX over ranks.  The timed steps start
+        from the state the W warm-up steps left.  eager_too / fwd_bwd: time the same steps launched eagerly / fwd+bwd alone
+        beside the main region; dump: keep the last timed step's outputs in self.outputs"""
         torch = self.torch
         for _ in range(warmup):
             self.step()
+        self._saved = None
+        if warmup > 0:
+            self.save_state()
         # the caching allocator may still be growing after W steps of a large configuration (C4: 59 device allocations over
         # the first ~10 steps, each a multi-millisecond hipMalloc that would land inside the timed region): keep stepping,
         # untimed, until two consecutive steps allocate nothing new (at most 12 more)
@@ -246,6 +332,8 @@ class Region:
             before = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0)
             self.step()
             extra += 1
+            if self._saved is None:  # W = 0: the state after the first step (the optimizer creates its state there)
+                self.save_state()
             grew = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0) != before
             quiet = 0 if self.agree(grew) else quiet + 1
         # ... and until the device has been busy for SETTLE_S seconds, so that the clock / power state the timed steps see is
@@ -271,11 +359,15 @@ class Region:
         eager_dt = None
         watchdog = None
         if auto_dp:
+            self.restore_state()
+            self.fence()
             t0 = time.perf_counter()
             for _ in range(steps):
                 loss = self.step()
             self.fence()
             te = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=self.dev)
+            if dump:  # (the measurement if the graph attempt does not take over)
+                self.outputs = self.collect_outputs()
             if self.use_dist:
                 self.dist.all_reduce(te, op=self.dist.ReduceOp.MAX)
             eager_dt = te.item()
@@ -398,7 +490,11 @@ class Region:
             self._run = run
             self._finish_timed()
             self.fwd_bwd_ms = None
+            self._saved = None
             return
+        self.restore_state()
+        self._saved = None
+        self.fence()
         t0 = time.perf_counter()
         for _ in range(steps):
             loss = run()
@@ -412,10 +508,12 @@ class Region:
             watchdog.cancel()
         if auto_dp and crash_armed:
             self.A._lib.load().avf_crash_line_disarm()
+        if dump:
+            self.outputs = self.collect_outputs()
         # forward + loss + backward (+ the gradient all-reduces) alone - what the metric names; the step above also clears the
         # gradients and applies Adam.  Eager launches, same fences (the step is GPU-bound either way: `eager_ms_per_step`).
         self.fwd_bwd_ms = None
-        if getattr(self, "fwd_bwd", None) is not None:
+        if fwd_bwd and getattr(self, "fwd_bwd", None) is not None:
             # no optimizer step between these forwards: the stacks keep their bf16 weight images (cache_weights) instead of
             # re-deriving them per forward as they must when nothing vouches for the masters being unchanged
             stacks = [m for m in self.model.modules() if hasattr(m, "cache_weights")]
@@ -610,8 +708,14 @@ def main():
                          "launched from Python every step; auto = graph on one rank (falls back to eager if capture fails) and eager "
                          "on several ranks (graph there captures the RCCL all-reduces with the step: opt-in, see AVF_BENCH_DP_GRAPH)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra timed regions (north-star shape C3, fp32 parity mode); the contract line's own "
-                         "fields are unaffected")
+                    help="with --full: skip the extra timed regions (north-star shape C3, fp32 parity mode); the contract "
+                         "line's own fields are unaffected")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: eager and fwd+bwd regions, "
+                         "clock / power, the extra timed regions, per-kernel-class events and roofline, the CPU baseline, the "
+                         "data-parallel report (the --no-* options above leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -658,9 +762,10 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    events = not args.no_kernel_events
+    events = args.full and not args.no_kernel_events
+    extra = args.full and not args.no_extra
     mk = lambda name, dtype, dist_on: Region(A, torch, dist, name, dtype, args, dev, rank, world, dist_on)
-    # ---- timed regions first, all un-instrumented: the contract's own, then (same process) the shape the north-star
+    # ---- timed regions first, all un-instrumented: the contract's own, then (--full, same process) the shape the north-star
     # target is quoted on (C3: B=32/GPU, T=512, d=512 = BASELINE configs[2], which at N=8 is exactly its global batch of
     # 256) and, at N=1, the fp32 parity mode on the main workload (the mode that meets north_star's logits rtol 1e-3).
     main_r = mk(args.config, args.dtype, use_dist)
@@ -691,10 +796,13 @@ def main():
             "launch": "eager (the captured data-parallel step did not return: watchdog; this is the eager region timed before the attempt)",
             "roofline": None, "cpu_baseline": None}
     try:
-        main_r.timed(args.steps, args.warmup, main_graph)
+        main_r.timed(args.steps, args.warmup, main_graph, eager_too=args.full, fwd_bwd=args.full,
+                     dump=args.dump_outputs is not None and rank == 0)
     finally:
         A._lib.load().avf_crash_line_disarm()  # (armed only around the multi-rank graph attempt; never past this region)
-    main_clock = main_r.clock_power() if (world == 1 and not args.no_extra) else None
+    if args.dump_outputs is not None and rank == 0:
+        write_outputs(args.dump_outputs, main_r.outputs)
+    main_clock = main_r.clock_power() if (world == 1 and extra) else None
     c, B = main_r.c, main_r.B
     Tv, Ta = c["t_video"], c["t_audio"]
     result = {
@@ -708,21 +816,24 @@ def main():
                    "global_batch": B * world, "seq_len": Tv + Ta, "parallelism": f"dp{world}",
                    "step": "zero_grad+fwd+AULoss+bwd" + ("+allreduce" if use_dist else "") + ("+adam" if main_r.optimizer else ""),
                    "optimizer": main_r.optimizer, "residual_stream": main_r.residual, "dropout": args.dropout, "loss": main_r.loss},
-        # what the box allowed while this step ran: the step is package-power-limited (DESIGN.md section 10.7)
-        "clock_power": main_clock,
         "untimed_steps_beyond_warmup": main_r.extra_warmup,  # until the caching allocator stopped growing (Region.timed)
         "launch": main_r.launch,
-        # the same step launched eagerly from Python (None when `value` itself is the eager number)
-        "eager_ms_per_step": None if main_r.eager_ms is None else round(main_r.eager_ms, 4),
-        "eager_clips_per_s": None if main_r.eager_ms is None else round(B * world / (main_r.eager_ms * 1e-3), 2),
-        # forward + AULoss + backward (+ all-reduce) only, eager launches: the part of the step the metric names
-        "fwd_bwd_ms_per_step": None if main_r.fwd_bwd_ms is None else round(main_r.fwd_bwd_ms, 4),
-        "fwd_bwd_clips_per_s": None if main_r.fwd_bwd_ms is None else round(B * world / (main_r.fwd_bwd_ms * 1e-3), 2),
     }
-    if use_dist:
+    if args.full or main_r.eager_ms is not None:
+        # the same step launched eagerly from Python (--full; None when `value` itself is the eager number) - or, with several
+        # ranks and --launch auto, the eager region timed before the graph attempt
+        result["eager_ms_per_step"] = None if main_r.eager_ms is None else round(main_r.eager_ms, 4)
+        result["eager_clips_per_s"] = None if main_r.eager_ms is None else round(B * world / (main_r.eager_ms * 1e-3), 2)
+    if args.full:
+        # what the box allowed while this step ran: the step is package-power-limited (DESIGN.md section 10.7)
+        result["clock_power"] = main_clock
+        # forward + AULoss + backward (+ all-reduce) only, eager launches: the part of the step the metric names
+        result["fwd_bwd_ms_per_step"] = None if main_r.fwd_bwd_ms is None else round(main_r.fwd_bwd_ms, 4)
+        result["fwd_bwd_clips_per_s"] = None if main_r.fwd_bwd_ms is None else round(B * world / (main_r.fwd_bwd_ms * 1e-3), 2)
+    if use_dist and args.full:
         result["data_parallel"] = dp_report(torch, dist, main_r, dev, world)
     c3_r = f32_r = f32m_r = r32_r = None
-    if not args.no_extra and args.dtype != "f32" and args.residual == "bf16":
+    if extra and args.dtype != "f32" and args.residual == "bf16":
         # the same workload with the fp32 forward residual stream (the round-1/2 default): reported beside `value`
         keep = args.residual
         args.residual = "f32"
@@ -732,7 +843,7 @@ def main():
         r32 = {"ms_per_step": round(r32_r.ms, 4), "clips_per_s": round(r32_r.clips_per_s, 2), "launch": r32_r.launch}
         r32_r.model = r32_r.opt = r32_r.step = r32_r.dp = None
         result["residual_f32"] = r32
-    if not args.no_extra and args.config == "c2" and args.dtype == "bf16":
+    if extra and args.config == "c2" and args.dtype == "bf16":
         c3_r = mk("c3", "bf16", use_dist)
         c3_r.timed(args.steps, args.warmup, use_graph)
         c3_clock = c3_r.clock_power() if world == 1 else None
@@ -824,7 +935,7 @@ def main():
                                         "frac": round(f32m_r.tflops / MFMA_PEAK_TFLOPS["f32"], 4),
                                         "note": "the same step with avf_set_f32_arith(0): v_mfma_f32_16x16x4_f32 GEMMs and attention"},
                                     "note": "compute_dtype='f32': the mode held to logits rtol 1e-3 against the fp32 CPU reference"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = min(os.cpu_count() or 1, 16)
             try:
                 threads = min(threads, len(os.sched_getaffinity(0)))

@@ -29,7 +29,7 @@ def box_id():
 def run(env_extra, steps, extra):  # extra: bench.py arguments of this arm
     env = dict(os.environ)
     env.update(env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps)] + extra, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps)] + extra, capture_output=True, text=True,
                        env=env, cwd=ROOT, timeout=600)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if not line:
