@@ -41,7 +41,13 @@ typedef struct avf_layer_cfg {
   int32_t tokens;      /* tokens per clip N                                                    */
   int32_t dim;         /* D      - Transformer(dim, ...)                  heads.py:243          */
   int32_t heads;       /* H                                               heads.py:204          */
-  int32_t dim_head;    /* dh ; inner I = H*dh                             heads.py:206          */
+  int32_t dim_head;    /* dh ; inner I = H*dh                             heads.py:206          *
+                        * bf16 / mx8 / resid_bf16: 32, 64 or 128 (else avf_layer_* fail naming dim_head); f32: 8, 16, 32, 64, 128.
+                        * Attention kernels per width: bf16 unmasked - head-resident and merged forms at 64 (<= 576 / 512 tokens),
+                        * the streaming MFMA forms at 32, 64 and 128; masked calls and bf16 storage under a mask - the fp32-arithmetic
+                        * kernels at 8..128 (bf16: the MFMA forms at 64, <= 512 tokens); f32 parity, unmasked - the three-product
+                        * bf16x3 kernels at 64 only, the f32-input MFMA kernels at 32, 64 and 128 (dim_head 128 takes them under
+                        * either arithmetic), the fp32 VALU kernels at 8 and 16. */
   int32_t mlp_dim;     /* M                                               heads.py:189          */
   int32_t dtype;       /* AVF_F32 | AVF_BF16                                                    */
   int32_t project_out; /* 0 iff heads==1 && dim_head==dim (nn.Identity)   heads.py:207: pass the identity matrix as w_out and

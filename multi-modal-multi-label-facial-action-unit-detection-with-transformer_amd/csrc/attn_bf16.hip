@@ -13,6 +13,10 @@
 //   dK / dV      : S = Q K^T      -> lane owns a key column;  dV^T = dO^T P,  dK^T = Q^T dS.
 // k-slot map of a packed accumulator pair / transposed fragment (32 reduction rows per k-step):
 //   slot j of lane group g  <->  row 16*(j>>2) + 4*g + (j&3).
+// Streaming kernels (attn_{fwd,dq,dkv}_bf16_kernel<DH, NW>): a workgroup owns 128 query (key) rows as NW waves of 128/NW.
+// dim_head 32 / 64: NW = 4 (32 rows per wave, two 16-row blocks).  dim_head 128: NW = 8 (16 rows per wave) - with two blocks
+// per wave the dK/dV kernel's accumulators alone take 128 registers and all three kernels spill at 256; with one they need
+// 150 / 162 / 238 VGPRs (forward / dQ / dK-dV), no scratch, one 512-thread workgroup per CU (73.7 KB static LDS each).
 #include <type_traits>
 
 #include "common.hpp"
@@ -72,15 +76,15 @@ __device__ __forceinline__ bf16x8_t load_frag_global(const bf16* p, bool ok) {
 
 // stage ROWS rows x DH bf16 from global (row stride ld elements) into an LDS tile with row stride LD bytes;
 // rows >= nvalid are zero-filled.  Split in issue (global -> regs) / commit (regs -> LDS).
-template <int DH, int ROWS>
+template <int DH, int ROWS, int NT = 256>
 struct TileStager {
-  static constexpr int CPR = DH / 8;                    // 16-byte chunks per row
-  static constexpr int PER = (ROWS * CPR + 255) / 256;  // chunks per thread
+  static constexpr int CPR = DH / 8;                     // 16-byte chunks per row
+  static constexpr int PER = (ROWS * CPR + NT - 1) / NT;  // chunks per thread (NT = threads of the workgroup)
   uint4 r[PER];
   __device__ __forceinline__ void issue(const bf16* src, int64_t ld, int row0, int nvalid, int tid) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int idx = tid + 256 * i;
+      const int idx = tid + NT * i;
       const int row = idx / CPR, c = idx - row * CPR;
       r[i] = make_uint4(0, 0, 0, 0);
       if (idx < ROWS * CPR && row < nvalid) r[i] = *reinterpret_cast<const uint4*>(src + (int64_t)(row0 + row) * ld + c * 8);
@@ -90,7 +94,7 @@ struct TileStager {
   __device__ __forceinline__ void commit(char* tile, int tid) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int idx = tid + 256 * i;
+      const int idx = tid + NT * i;
       const int row = idx / CPR, c = idx - row * CPR;
       if (idx < ROWS * CPR) *reinterpret_cast<uint4*>(tile + row * LD + c * 16) = r[i];
     }
@@ -140,10 +144,10 @@ __device__ __forceinline__ float colsum4(float v) {
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
-template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
-                                                            float* __restrict__ lse2, int /*B*/, int N, int H, int qs) {
-  constexpr int KS = DH / 32, DB = DH / 16;
+template <int DH, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
+                                                                     float* __restrict__ lse2, int /*B*/, int N, int H, int qs) {
+  constexpr int KS = DH / 32, DB = DH / 16, QB = 8 / NW;  // 128 query rows per workgroup: NW waves x QB blocks of 16
   constexpr int KLD = DH * 2 + 32;  // K tile: row reads (ds_read_b128); +32 B keeps them conflict-free (PMC-checked)
   constexpr int VLD = DH * 2 + 32;  // V tile: transposed reads, 8 consecutive rows -> 8 distinct bank windows
   constexpr int STAGE = 64 * KLD + 64 * VLD;
@@ -159,28 +163,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __res
   const bf16* qbase = qkv + (int64_t)b * N * ld + h * DH;
   const bf16* kbase = qbase + I;
   const bf16* vbase = qbase + 2 * I;
-  const int q0 = blk * 128 + wave * 32;
+  const int q0 = blk * 128 + wave * 16 * QB;
   const bool active = __builtin_amdgcn_readfirstlane(q0) < N;
   const float c = qs ? 1.0f : LOG2E / sqrtf((float)DH);  // qs: q already carries log2(e)/sqrt(dh)
   AVF_PHASE_INIT();
 
-  bf16x8_t fq[2][KS];
+  bf16x8_t fq[QB][KS];
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb)
+  for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int q = q0 + qb * 16 + li;
       fq[qb][ks] = load_frag_global(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, q < N);
     }
 
-  f32x4_t ot[DB][2];
+  f32x4_t ot[DB][QB];
 #pragma unroll
   for (int d = 0; d < DB; ++d)
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) ot[d][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
+    for (int qb = 0; qb < QB; ++qb) ot[d][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m[QB], lsum[QB];
+#pragma unroll
+  for (int qb = 0; qb < QB; ++qb) m[qb] = -INFINITY, lsum[qb] = 0.f;
 
-  TileStager<DH, 64> sk, sv;
+  TileStager<DH, 64, 64 * NW> sk, sv;
   const int nt = (N + 63) / 64;
   {
     const int nv = N < 64 ? N : 64;
@@ -210,23 +216,24 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __res
       constexpr bool TAIL = decltype(tail_tag)::value;
       const int nkb = TAIL ? (N - t * 64 + 15) / 16 : 4;
       // S^T[key][q] = K Q^T
-      f32x4_t st[4][2];
+      f32x4_t st[4][QB];
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
-        st[kb][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        st[kb][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) st[kb][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (!TAIL || kb < nkb) {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
             const bf16x8_t fk = row_frag<KLD>(kt, kb * 16 + li, ks * 32 + 8 * lg);
-            st[kb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[0][ks], st[kb][0], 0, 0, 0);
-            st[kb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[1][ks], st[kb][1], 0, 0, 0);
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+              st[kb][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[qb][ks], st[kb][qb], 0, 0, 0);
           }
         }
       }
       AVF_PHASE_MARK(2);
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
+      for (int qb = 0; qb < QB; ++qb) {
         float tmax = -INFINITY;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb)
@@ -259,13 +266,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __res
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (TAIL && 2 * s >= nkb) continue;
-        const bf16x8_t p0 = pack_pair(st[2 * s][0], st[2 * s + 1][0]);
-        const bf16x8_t p1 = pack_pair(st[2 * s][1], st[2 * s + 1][1]);
+        bf16x8_t p[QB];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) p[qb] = pack_pair(st[2 * s][qb], st[2 * s + 1][qb]);
 #pragma unroll
         for (int d = 0; d < DB; ++d) {
           const bf16x8_t fv = tr_frag<VLD>(vt, 32 * s, d * 16, li, lg);
-          ot[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, p0, ot[d][0], 0, 0, 0);
-          ot[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, p1, ot[d][1], 0, 0, 0);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) ot[d][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, p[qb], ot[d][qb], 0, 0, 0);
         }
       }
     };
@@ -284,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const bf16* __res
   }
 
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
+  for (int qb = 0; qb < QB; ++qb) {
     float l = lsum[qb];
     l = colsum4(l);
     const int q = q0 + qb * 16 + li;
@@ -1076,12 +1084,12 @@ store_row_pairs<DB>(outk, lg, [&](int d) { return dkt[d][kb] * kscale; });
 // =============================================================================================
 // backward: dQ  (query on the lane; sweeps key tiles)
 // =============================================================================================
-template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_dq_bf16_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
-                                                           const float* __restrict__ lse2,
-                                                           const float* __restrict__ delta, bf16* __restrict__ dqkv,
-                                                           int /*B*/, int N, int H, int qs) {
-  constexpr int KS = DH / 32, DB = DH / 16;
+template <int DH, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void attn_dq_bf16_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
+                                                                    const float* __restrict__ lse2,
+                                                                    const float* __restrict__ delta, bf16* __restrict__ dqkv,
+                                                                    int /*B*/, int N, int H, int qs) {
+  constexpr int KS = DH / 32, DB = DH / 16, QB = 8 / NW;  // 128 query rows per workgroup: NW waves x QB blocks of 16
   constexpr int KLD = DH * 2 + 32;  // K tile: row reads AND transposed reads
   constexpr int VLD = DH * 2 + 32;  // V tile: row reads only (+32 B: conflict-free, PMC-checked)
   constexpr int STAGE = 64 * KLD + 64 * VLD;
@@ -1098,15 +1106,15 @@ __global__ __launch_bounds__(256, 2) void attn_dq_bf16_kernel(const bf16* __rest
   const bf16* kbase = qbase + I;
   const bf16* vbase = qbase + 2 * I;
   const bf16* gbase = d_o + (int64_t)b * N * I + h * DH;
-  const int q0 = blk * 128 + wave * 32;
+  const int q0 = blk * 128 + wave * 16 * QB;
   const bool active = __builtin_amdgcn_readfirstlane(q0) < N;
   const float scale = 1.0f / sqrtf((float)DH);
   const float c = qs ? 1.0f : LOG2E * scale;
 
-  bf16x8_t fq[2][KS], fg[2][KS];
-  float L[2], dl[2];
+  bf16x8_t fq[QB][KS], fg[QB][KS];
+  float L[QB], dl[QB];
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
+  for (int qb = 0; qb < QB; ++qb) {
     const int q = q0 + qb * 16 + li;
     const bool ok = q < N;
 #pragma unroll
@@ -1117,13 +1125,13 @@ __global__ __launch_bounds__(256, 2) void attn_dq_bf16_kernel(const bf16* __rest
     L[qb] = ok ? lse2[(int64_t)bh * N + q] : 0.f;
     dl[qb] = ok ? delta[(int64_t)bh * N + q] : 0.f;
   }
-  f32x4_t dqt[DB][2];
+  f32x4_t dqt[DB][QB];
 #pragma unroll
   for (int d = 0; d < DB; ++d)
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) dqt[d][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int qb = 0; qb < QB; ++qb) dqt[d][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  TileStager<DH, 64> sk, sv;
+  TileStager<DH, 64, 64 * NW> sk, sv;
   const int nt = (N + 63) / 64;
   {
     const int nv = N < 64 ? N : 64;
@@ -1146,42 +1154,46 @@ __global__ __launch_bounds__(256, 2) void attn_dq_bf16_kernel(const bf16* __rest
     auto tile_body = [&](auto tail_tag) {
       constexpr bool TAIL = decltype(tail_tag)::value;
       const int nkb = TAIL ? (N - t * 64 + 15) / 16 : 4;
-      f32x4_t ds[4][2];
+      f32x4_t ds[4][QB];
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
-        ds[kb][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        ds[kb][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) ds[kb][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (TAIL && kb >= nkb) continue;
-        f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
+        f32x4_t sc[QB], pg[QB];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) sc[qb] = pg[qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const bf16x8_t fk = row_frag<KLD>(kt, kb * 16 + li, ks * 32 + 8 * lg);
           const bf16x8_t fv = row_frag<VLD>(vt, kb * 16 + li, ks * 32 + 8 * lg);
-          s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[0][ks], s0, 0, 0, 0);
-          s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[1][ks], s1, 0, 0, 0);
-          p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, fg[0][ks], p0, 0, 0, 0);
-          p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, fg[1][ks], p1, 0, 0, 0);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) sc[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[qb][ks], sc[qb], 0, 0, 0);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) pg[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, fg[qb][ks], pg[qb], 0, 0, 0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const bool dead = TAIL && (t * 64 + kb * 16 + 4 * lg + r >= N);
-          const float e0 = dead ? 0.f : __builtin_amdgcn_exp2f(s0[r] * c - L[0]);
-          const float e1 = dead ? 0.f : __builtin_amdgcn_exp2f(s1[r] * c - L[1]);
-          ds[kb][0][r] = e0 * (p0[r] - dl[0]);
-          ds[kb][1][r] = e1 * (p1[r] - dl[1]);
+          float e[QB];
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) e[qb] = dead ? 0.f : __builtin_amdgcn_exp2f(sc[qb][r] * c - L[qb]);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) ds[kb][qb][r] = e[qb] * (pg[qb][r] - dl[qb]);
         }
       }
       // dQ^T[d][q] += K^T dS^T
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (TAIL && 2 * s >= nkb) continue;
-        const bf16x8_t a0 = pack_pair(ds[2 * s][0], ds[2 * s + 1][0]);
-        const bf16x8_t a1 = pack_pair(ds[2 * s][1], ds[2 * s + 1][1]);
+        bf16x8_t a[QB];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) a[qb] = pack_pair(ds[2 * s][qb], ds[2 * s + 1][qb]);
 #pragma unroll
         for (int d = 0; d < DB; ++d) {
           const bf16x8_t fkt = tr_frag<KLD>((const lds_char*)kt, 32 * s, d * 16, li, lg);
-          dqt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fkt, a0, dqt[d][0], 0, 0, 0);
-          dqt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fkt, a1, dqt[d][1], 0, 0, 0);
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb) dqt[d][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fkt, a[qb], dqt[d][qb], 0, 0, 0);
         }
       }
     };
@@ -1196,7 +1208,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_bf16_kernel(const bf16* __rest
     __syncthreads();
   }
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
+  for (int qb = 0; qb < QB; ++qb) {
     const int q = q0 + qb * 16 + li;
     if (q < N) {
       bf16* out = dqkv + ((int64_t)b * N + q) * ld + h * DH;
@@ -1208,12 +1220,12 @@ store_row_pairs<DB>(out, lg, [&](int d) { return dqt[d][qb] * scale; });
 // =============================================================================================
 // backward: dK, dV  (key on the lane; sweeps query tiles)
 // =============================================================================================
-template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_dkv_bf16_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
-                                                            const float* __restrict__ lse2,
-                                                            const float* __restrict__ delta, bf16* __restrict__ dqkv,
-                                                            int /*B*/, int N, int H, int qs) {
-  constexpr int KS = DH / 32, DB = DH / 16;
+template <int DH, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void attn_dkv_bf16_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
+                                                                     const float* __restrict__ lse2,
+                                                                     const float* __restrict__ delta, bf16* __restrict__ dqkv,
+                                                                     int /*B*/, int N, int H, int qs) {
+  constexpr int KS = DH / 32, DB = DH / 16, KB = 8 / NW;  // 128 key rows per workgroup: NW waves x KB blocks of 16
   constexpr int TLD = DH * 2 + 32;  // Q and dO tiles: row reads AND transposed reads
   constexpr int STAGE = 2 * 64 * TLD + 2 * 64 * 4;
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -1229,31 +1241,31 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_bf16_kernel(const bf16* __res
   const bf16* kbase = qbase + I;
   const bf16* vbase = qbase + 2 * I;
   const bf16* gbase = d_o + (int64_t)b * N * I + h * DH;
-  const int k0 = blk * 128 + wave * 32;
+  const int k0 = blk * 128 + wave * 16 * KB;
   const bool active = __builtin_amdgcn_readfirstlane(k0) < N;
   const float scale = 1.0f / sqrtf((float)DH);
   const float c = qs ? 1.0f : LOG2E * scale;
   const float kscale = qs ? 1.0f / LOG2E : scale;  // dK = scale dS^T q = dS^T q' / log2(e) when q' = q log2(e) scale
 
-  bf16x8_t fk[2][KS], fv[2][KS];
+  bf16x8_t fk[KB][KS], fv[KB][KS];
 #pragma unroll
-  for (int kb = 0; kb < 2; ++kb)
+  for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int key = k0 + kb * 16 + li;
       fk[kb][ks] = load_frag_global(kbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
       fv[kb][ks] = load_frag_global(vbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
     }
-  f32x4_t dvt[DB][2], dkt[DB][2];
+  f32x4_t dvt[DB][KB], dkt[DB][KB];
 #pragma unroll
   for (int d = 0; d < DB; ++d)
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
+    for (int kb = 0; kb < KB; ++kb) {
       dvt[d][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
       dkt[d][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
 
-  TileStager<DH, 64> sq, sg;
+  TileStager<DH, 64, 64 * NW> sq, sg;
   float rl = 0.f, rd = 0.f;  // staged lse2 / delta (threads 0..63)
   auto issue_stats = [&](int r0) {
     if (tid < 64) {
@@ -1301,48 +1313,53 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_bf16_kernel(const bf16* __res
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (TAIL && 2 * s >= nqb) continue;
-        f32x4_t pm[2][2], dsm[2][2];  // P and dS, [q-block of the pair][key-block]
+        f32x4_t pm[2][KB], dsm[2][KB];  // P and dS, [q-block of the pair][key-block]
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
           const int qb = 2 * s + h2;
-          pm[h2][0] = pm[h2][1] = dsm[h2][0] = dsm[h2][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) pm[h2][kb] = dsm[h2][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
           if (TAIL && qb >= nqb) continue;
-          f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
+          f32x4_t sc[KB], pg[KB];
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) sc[kb] = pg[kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
             const bf16x8_t fqr = row_frag<TLD>(qt, qb * 16 + li, ks * 32 + 8 * lg);
             const bf16x8_t fgr = row_frag<TLD>(gt, qb * 16 + li, ks * 32 + 8 * lg);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqr, fk[0][ks], s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqr, fk[1][ks], s1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgr, fv[0][ks], p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgr, fv[1][ks], p1, 0, 0, 0);
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) sc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqr, fk[kb][ks], sc[kb], 0, 0, 0);
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) pg[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgr, fv[kb][ks], pg[kb], 0, 0, 0);
           }
           const float4 l4 = *reinterpret_cast<const float4*>(Ls + qb * 16 + 4 * lg);
           const float4 d4 = *reinterpret_cast<const float4*>(Ds + qb * 16 + 4 * lg);
           const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float e0 = __builtin_amdgcn_exp2f(s0[r] * c - lv[r]);
-            const float e1 = __builtin_amdgcn_exp2f(s1[r] * c - lv[r]);
-            pm[h2][0][r] = e0;
-            pm[h2][1][r] = e1;
-            dsm[h2][0][r] = e0 * (p0[r] - dv[r]);
-            dsm[h2][1][r] = e1 * (p1[r] - dv[r]);
+            float e[KB];
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) e[kb] = __builtin_amdgcn_exp2f(sc[kb][r] * c - lv[r]);
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) pm[h2][kb][r] = e[kb];
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) dsm[h2][kb][r] = e[kb] * (pg[kb][r] - dv[r]);
           }
         }
         // dV^T[d][key] += dO^T P ; dK^T[d][key] += Q^T dS
-        const bf16x8_t pa0 = pack_pair(pm[0][0], pm[1][0]);
-        const bf16x8_t pa1 = pack_pair(pm[0][1], pm[1][1]);
-        const bf16x8_t da0 = pack_pair(dsm[0][0], dsm[1][0]);
-        const bf16x8_t da1 = pack_pair(dsm[0][1], dsm[1][1]);
+        bf16x8_t pa[KB], da[KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) pa[kb] = pack_pair(pm[0][kb], pm[1][kb]);
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) da[kb] = pack_pair(dsm[0][kb], dsm[1][kb]);
 #pragma unroll
         for (int d = 0; d < DB; ++d) {
           const bf16x8_t fgt = tr_frag<TLD>((const lds_char*)gt, 32 * s, d * 16, li, lg);
           const bf16x8_t fqt = tr_frag<TLD>((const lds_char*)qt, 32 * s, d * 16, li, lg);
-          dvt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgt, pa0, dvt[d][0], 0, 0, 0);
-          dvt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgt, pa1, dvt[d][1], 0, 0, 0);
-          dkt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqt, da0, dkt[d][0], 0, 0, 0);
-          dkt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqt, da1, dkt[d][1], 0, 0, 0);
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) dvt[d][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgt, pa[kb], dvt[d][kb], 0, 0, 0);
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) dkt[d][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqt, da[kb], dkt[d][kb], 0, 0, 0);
         }
       }
     };
@@ -1359,7 +1376,7 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_bf16_kernel(const bf16* __res
     __syncthreads();
   }
 #pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
+  for (int kb = 0; kb < KB; ++kb) {
     const int key = k0 + kb * 16 + li;
     if (key < N) {
       bf16* outk = dqkv + ((int64_t)b * N + key) * ld + I + h * DH;
@@ -1481,7 +1498,8 @@ int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, in
   const int qs = q_prescaled ? 1 : 0;
   if (dh == 64) launch_in_scope(&ts, attn_fwd_bf16_kernel<64>, dim3(grid), dim3(256), 0, s, qkv, o, lse2, B, N, H, qs);
   else if (dh == 32) launch_in_scope(&ts, attn_fwd_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, o, lse2, B, N, H, qs);
-  else AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32 or 64)", dh);
+  else if (dh == 128) launch_in_scope(&ts, attn_fwd_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, o, lse2, B, N, H, qs);
+  else AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32, 64 or 128)", dh);
   return check_launch("attn_fwd_bf16_kernel");
 }
 
@@ -1533,8 +1551,11 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
   } else if (dh == 32) {
     launch_in_scope(&ts, attn_dq_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
     launch_in_scope(&ts, attn_dkv_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
+  } else if (dh == 128) {
+    launch_in_scope(&ts, attn_dq_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
+    launch_in_scope(&ts, attn_dkv_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
   } else {
-    AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32 or 64)", dh);
+    AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32, 64 or 128)", dh);
   }
   return check_launch("attn_bwd_bf16 kernels");
 }

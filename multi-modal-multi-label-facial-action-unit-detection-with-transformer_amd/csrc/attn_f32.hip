@@ -1,6 +1,6 @@
 // attn_f32.hip - parity-mode attention core (fp32 VALU, flash-style: never materialises [B,H,N,N]).
 // (Round 5: fp32 storage without a mask at dim_head 32 / 64 - the parity mode's own calls - runs on attn_f32_mfma.hip instead;
-//  these kernels keep the masked calls, bf16 storage and the other head widths.)
+//  these kernels keep the masked calls, bf16 storage and the other head widths: 8, 16, 32, 64 and 128.)
 //
 // Reference: models/heads.py:222-237 -  dots = q k^T * dh^-0.5 ; softmax(dim=-1) ; out = attn v ;
 // 'b h n d -> b n (h d)'.  No dropout on the probabilities.  The token mask of heads.py:225-232 (dead in the reference: no
@@ -38,6 +38,21 @@ __device__ __forceinline__ void stage_keep(uint8_t* dst, const uint8_t* keep, in
 }
 constexpr float MASKV = -3.4028234663852886e38f;  // -finfo(float32).max, heads.py:225
 
+// dim_head 128: one row per lane would hold 256 (forward, dQ) to 384 (dK) live floats and spill, so two adjacent lanes share
+// a row - lane parity p holds the 16-byte granules 2i + p (columns 8i + 4p .. + 3: the pair reads distinct LDS banks) and
+// dot products are completed across the pair.  SP = lanes per row, DL = columns per lane, col(d) = column of element d.
+template <int DH> constexpr int vec_split() { return DH > 64 ? 2 : 1; }
+template <int DH> constexpr int vec_rows() { return 64 / vec_split<DH>(); }  // rows per 64-lane workgroup
+template <int SP>
+__device__ __forceinline__ int vec_col0() { return SP == 1 ? 0 : 4 * (int)(threadIdx.x & 1); }
+template <int SP>
+__device__ __forceinline__ int vec_col(int d, int c0) { return SP * (d & ~3) + (d & 3) + c0; }
+template <int SP>
+__device__ __forceinline__ float pair_sum(float a) {  // a + the pair partner's a (the same bits in both lanes)
+  if constexpr (SP == 1) return a;
+  else return a + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(a), 0xB1, 0xF, 0xF, true));  // quad_perm [1,0,3,2]
+}
+
 template <int DH, typename T, bool MASKED>
 __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const T* __restrict__ qkv, T* __restrict__ o,
                                                           float* __restrict__ lse2, int /*B*/, int N, int H,
@@ -49,15 +64,17 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const T* __restrict__ 
   const int I = H * DH;
   const int64_t ld = 3 * (int64_t)I;
   const T* base = qkv + (int64_t)b * N * ld + h * DH;
-  const int qi = blockIdx.x * 64 + threadIdx.x;
+  constexpr int SP = vec_split<DH>(), DL = DH / SP;
+  const int c0 = vec_col0<SP>();
+  const int qi = blockIdx.x * vec_rows<DH>() + threadIdx.x / SP;
   const bool valid = qi < N;
   const bool mq = !MASKED || (valid && keep[(int64_t)b * N + qi]);
   const float c = qs ? 1.0f : LOG2E / sqrtf((float)DH);
-  float q[DH], acc[DH];
+  float q[DL], acc[DL];
 #pragma unroll
-  for (int d = 0; d < DH; d += 4) {
+  for (int d = 0; d < DL; d += 4) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) v = load4<T>(base + (int64_t)qi * ld + d);
+    if (valid) v = load4<T>(base + (int64_t)qi * ld + vec_col<SP>(d, c0));
     q[d] = v.x * c; q[d + 1] = v.y * c; q[d + 2] = v.z * c; q[d + 3] = v.w * c;
     acc[d] = acc[d + 1] = acc[d + 2] = acc[d + 3] = 0.f;
   }
@@ -74,7 +91,8 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const T* __restrict__ 
     for (int j = 0; j < KT; ++j) {
       float a = 0.f;
 #pragma unroll
-      for (int d = 0; d < DH; ++d) a = fmaf(q[d], Ks[j * DH + d], a);
+      for (int d = 0; d < DL; ++d) a = fmaf(q[d], Ks[j * DH + vec_col<SP>(d, c0)], a);
+      a = pair_sum<SP>(a);
       if (MASKED) s[j] = (j < nk) ? ((mq && Ms[j]) ? a : MASKV) : -INFINITY;
       else s[j] = (j < nk) ? a : -INFINITY;
       tmax = fmaxf(tmax, s[j]);
@@ -83,13 +101,13 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const T* __restrict__ 
     const float alpha = exp2f(m - mn);
     l *= alpha;
 #pragma unroll
-    for (int d = 0; d < DH; ++d) acc[d] *= alpha;
+    for (int d = 0; d < DL; ++d) acc[d] *= alpha;
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
       const float pj = exp2f(s[j] - mn);
       l += pj;
 #pragma unroll
-      for (int d = 0; d < DH; ++d) acc[d] = fmaf(pj, Vs[j * DH + d], acc[d]);
+      for (int d = 0; d < DL; ++d) acc[d] = fmaf(pj, Vs[j * DH + vec_col<SP>(d, c0)], acc[d]);
     }
     m = mn;
     __syncthreads();
@@ -98,9 +116,9 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const T* __restrict__ 
     const float inv = 1.0f / l;
     T* orow = o + ((int64_t)b * N + qi) * I + h * DH;
 #pragma unroll
-    for (int d = 0; d < DH; d += 4)
-      store4<T>(orow + d, make_float4(acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv));
-    lse2[(int64_t)bh * N + qi] = m + log2f(l);  // (a dropped query's row: backward uses p = 1/N, not this value)
+    for (int d = 0; d < DL; d += 4)
+      store4<T>(orow + vec_col<SP>(d, c0), make_float4(acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv));
+    if (c0 == 0) lse2[(int64_t)bh * N + qi] = m + log2f(l);  // (a dropped query's row: backward uses p = 1/N, not this value)
   }
 }
 
@@ -117,18 +135,20 @@ __global__ __launch_bounds__(64) void attn_dq_f32_kernel(const T* __restrict__ q
   const int I = H * DH;
   const int64_t ld = 3 * (int64_t)I;
   const T* base = qkv + (int64_t)b * N * ld + h * DH;
-  const int qi = blockIdx.x * 64 + threadIdx.x;
+  constexpr int SP = vec_split<DH>(), DL = DH / SP;
+  const int c0 = vec_col0<SP>();
+  const int qi = blockIdx.x * vec_rows<DH>() + threadIdx.x / SP;
   const bool valid = qi < N;
   const bool mq = !MASKED || (valid && keep[(int64_t)b * N + qi]);
   const float scale = 1.0f / sqrtf((float)DH);
   const float c = qs ? 1.0f : LOG2E * scale;
-  float q[DH], g[DH], dq[DH];
+  float q[DL], g[DL], dq[DL];
 #pragma unroll
-  for (int d = 0; d < DH; d += 4) {
+  for (int d = 0; d < DL; d += 4) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f), w = v;
     if (valid) {
-      v = load4<T>(base + (int64_t)qi * ld + d);
-      w = load4<T>(d_o + ((int64_t)b * N + qi) * I + h * DH + d);
+      v = load4<T>(base + (int64_t)qi * ld + vec_col<SP>(d, c0));
+      w = load4<T>(d_o + ((int64_t)b * N + qi) * I + h * DH + vec_col<SP>(d, c0));
     }
     q[d] = v.x * c; q[d + 1] = v.y * c; q[d + 2] = v.z * c; q[d + 3] = v.w * c;
     g[d] = w.x; g[d + 1] = w.y; g[d + 2] = w.z; g[d + 3] = w.w;
@@ -146,23 +166,25 @@ __global__ __launch_bounds__(64) void attn_dq_f32_kernel(const T* __restrict__ q
     for (int j = 0; j < KT; ++j) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < DH; ++d) {
-        s = fmaf(q[d], Ks[j * DH + d], s);
-        dp = fmaf(g[d], Vs[j * DH + d], dp);
+      for (int d = 0; d < DL; ++d) {
+        s = fmaf(q[d], Ks[j * DH + vec_col<SP>(d, c0)], s);
+        dp = fmaf(g[d], Vs[j * DH + vec_col<SP>(d, c0)], dp);
       }
+      s = pair_sum<SP>(s);
+      dp = pair_sum<SP>(dp);
       const bool live = MASKED ? (j < nk && mq && Ms[j]) : (j < nk);  // filled scores: dS = 0
       const float pj = live ? exp2f(s - L) : 0.f;
       const float ds = pj * (dp - dl);
 #pragma unroll
-      for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, Ks[j * DH + d], dq[d]);
+      for (int d = 0; d < DL; ++d) dq[d] = fmaf(ds, Ks[j * DH + vec_col<SP>(d, c0)], dq[d]);
     }
     __syncthreads();
   }
   if (valid) {
     T* out = dqkv + ((int64_t)b * N + qi) * ld + h * DH;
 #pragma unroll
-    for (int d = 0; d < DH; d += 4)
-      store4<T>(out + d, make_float4(dq[d] * scale, dq[d + 1] * scale, dq[d + 2] * scale, dq[d + 3] * scale));
+    for (int d = 0; d < DL; d += 4)
+      store4<T>(out + vec_col<SP>(d, c0), make_float4(dq[d] * scale, dq[d + 1] * scale, dq[d + 2] * scale, dq[d + 3] * scale));
   }
 }
 
@@ -182,21 +204,23 @@ __global__ __launch_bounds__(64) void attn_dkv_f32_kernel(const T* __restrict__ 
   const int I = H * DH;
   const int64_t ld = 3 * (int64_t)I;
   const T* base = qkv + (int64_t)b * N * ld + h * DH;
-  const int ki = blockIdx.x * 64 + threadIdx.x;
+  constexpr int SP = vec_split<DH>(), DL = DH / SP;
+  const int c0 = vec_col0<SP>();
+  const int ki = blockIdx.x * vec_rows<DH>() + threadIdx.x / SP;
   const bool valid = ki < N;
   const bool mk = !MASKED || (valid && keep[(int64_t)b * N + ki]);
   const float scale = 1.0f / sqrtf((float)DH);
   const float c = qs ? 1.0f : LOG2E * scale;
   const float uniform = 1.0f / (float)N;
-  float k[DH], v[PASS == 1 ? DH : 1], acc[DH];
+  float k[DL], v[PASS == 1 ? DL : 1], acc[DL];
 #pragma unroll
-  for (int d = 0; d < DH; d += 4) {
+  for (int d = 0; d < DL; d += 4) {
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) a = load4<T>(base + I + (int64_t)ki * ld + d);
+    if (valid) a = load4<T>(base + I + (int64_t)ki * ld + vec_col<SP>(d, c0));
     k[d] = a.x * c; k[d + 1] = a.y * c; k[d + 2] = a.z * c; k[d + 3] = a.w * c;
     if (PASS == 1) {
       float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (valid) w = load4<T>(base + 2 * I + (int64_t)ki * ld + d);
+      if (valid) w = load4<T>(base + 2 * I + (int64_t)ki * ld + vec_col<SP>(d, c0));
       v[d] = w.x; v[d + 1] = w.y; v[d + 2] = w.z; v[d + 3] = w.w;
     }
     acc[d] = acc[d + 1] = acc[d + 2] = acc[d + 3] = 0.f;
@@ -216,20 +240,22 @@ __global__ __launch_bounds__(64) void attn_dkv_f32_kernel(const T* __restrict__ 
     for (int j = 0; j < KT; ++j) {
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < DH; ++d) s = fmaf(k[d], Qs[j * DH + d], s);
+      for (int d = 0; d < DL; ++d) s = fmaf(k[d], Qs[j * DH + vec_col<SP>(d, c0)], s);
+      s = pair_sum<SP>(s);
       const bool pair = !MASKED || (Ms[j] && mk);  // Ms[j] = 0 past the end and for a dropped query (Ls = inf past the end)
       float pj = pair ? exp2f(s - Ls[j]) : 0.f;
       if (MASKED && j < nq && !Ms[j]) pj = uniform;  // dropped query: every score was filled, softmax is uniform over all N keys
       if (PASS == 0) {
 #pragma unroll
-        for (int d = 0; d < DH; ++d) acc[d] = fmaf(pj, Gs[j * DH + d], acc[d]);
+        for (int d = 0; d < DL; ++d) acc[d] = fmaf(pj, Gs[j * DH + vec_col<SP>(d, c0)], acc[d]);
       } else {
         float dp = 0.f;
 #pragma unroll
-        for (int d = 0; d < DH; ++d) dp = fmaf(Gs[j * DH + d], v[d], dp);
+        for (int d = 0; d < DL; ++d) dp = fmaf(Gs[j * DH + vec_col<SP>(d, c0)], v[d], dp);
+        dp = pair_sum<SP>(dp);
         const float ds = pair ? pj * (dp - Ds[j]) : 0.f;
 #pragma unroll
-        for (int d = 0; d < DH; ++d) acc[d] = fmaf(ds, Qs[j * DH + d], acc[d]);
+        for (int d = 0; d < DL; ++d) acc[d] = fmaf(ds, Qs[j * DH + vec_col<SP>(d, c0)], acc[d]);
       }
     }
     __syncthreads();
@@ -238,8 +264,8 @@ __global__ __launch_bounds__(64) void attn_dkv_f32_kernel(const T* __restrict__ 
     const float f = PASS == 1 ? (qs ? 1.0f / LOG2E : scale) : 1.0f;  // qs: q' = q log2(e) scale, dk = dS^T q' / log2(e)
     T* out = dqkv + ((int64_t)b * N + ki) * ld + (PASS == 1 ? I : 2 * I) + h * DH;
 #pragma unroll
-    for (int d = 0; d < DH; d += 4)
-      store4<T>(out + d, make_float4(acc[d] * f, acc[d + 1] * f, acc[d + 2] * f, acc[d + 3] * f));
+    for (int d = 0; d < DL; d += 4)
+      store4<T>(out + vec_col<SP>(d, c0), make_float4(acc[d] * f, acc[d + 1] * f, acc[d + 2] * f, acc[d + 3] * f));
   }
 }
 
@@ -293,7 +319,8 @@ int attn_delta(int dtype, const void* o, const void* d_o, float* delta, int B, i
     case 16: MACRO(16); break;                                                                \
     case 32: MACRO(32); break;                                                                \
     case 64: MACRO(64); break;                                                                \
-    default: AVF_REQUIRE(false, "attention (fp32): unsupported dim_head %d (8,16,32,64)", dh); \
+    case 128: MACRO(128); break;                                                              \
+    default: AVF_REQUIRE(false, "attention (fp32): unsupported dim_head %d (8,16,32,64,128)", dh); \
   }
 
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s) {
@@ -311,10 +338,9 @@ int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N,
     return attn_fwd_f32x3((const float*)qkv, (float*)o, lse2, B, N, H, s);
   if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, o))  // fp32 storage, no mask, dim_head 32 / 64: the fp32 matrix pipe
     return attn_fwd_f32_mfma((const float*)qkv, (float*)o, lse2, B, N, H, dh, s, q_prescaled);
-  dim3 grid((unsigned)ceil_div(N, 64), (unsigned)(B * H));
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
-#define LT(D, T, MK) attn_fwd_f32_kernel<D, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (T*)o, lse2, B, N, H, kp, qs)
+#define LT(D, T, MK) attn_fwd_f32_kernel<D, T, MK><<<dim3((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H)), 64, 0, s>>>((const T*)qkv, (T*)o, lse2, B, N, H, kp, qs)
 #define L(D)                                                  \
   if (dtype == AVF_F32) {                                     \
     if (kp) LT(D, float, true); else LT(D, float, false);     \
@@ -343,10 +369,10 @@ int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, con
   AVF_TRY(attn_delta(dtype, o, d_o, delta, B, N, H, dh, s));
   if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, d_o) && ((uintptr_t)dqkv & 15) == 0)
     return attn_bwd_f32_mfma((const float*)qkv, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, dh, s, q_prescaled);
-  dim3 grid((unsigned)ceil_div(N, 64), (unsigned)(B * H));
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
 #define LT(D, T, MK)                                                                                                       \
+  const dim3 grid((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H));                                                  \
   attn_dq_f32_kernel<D, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs);     \
   attn_dkv_f32_kernel<D, 0, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs); \
   attn_dkv_f32_kernel<D, 1, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs)

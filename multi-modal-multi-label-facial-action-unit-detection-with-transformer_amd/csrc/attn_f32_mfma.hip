@@ -316,9 +316,9 @@ __global__ __launch_bounds__(256) void attn_dkv_f32m_kernel(const float* __restr
 
 }  // namespace
 
-// shapes these kernels take: fp32 storage, no token mask, dim_head 32 or 64, 16-byte aligned rows
+// shapes these kernels take: fp32 storage, no token mask, dim_head 32, 64 or 128, 16-byte aligned rows
 bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other) {
-  return dtype == AVF_F32 && !keep && (dh == 32 || dh == 64) && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)other & 15) == 0 &&
+  return dtype == AVF_F32 && !keep && (dh == 32 || dh == 64 || dh == 128) && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)other & 15) == 0 &&
          ((H * dh) % 4) == 0;
 }
 
@@ -326,6 +326,7 @@ int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int
   dim3 grid((unsigned)ceil_div(N, 64), (unsigned)(B * H));
   const int qs = q_prescaled ? 1 : 0;
   if (dh == 64) attn_fwd_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
+  else if (dh == 128) attn_fwd_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
   else attn_fwd_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
   return check_launch("attn_fwd_f32m_kernel");
 }
@@ -337,6 +338,9 @@ int attn_bwd_f32_mfma(const float* qkv, const float* d_o, const float* lse2, con
   if (dh == 64) {
     attn_dq_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
     attn_dkv_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
+  } else if (dh == 128) {
+    attn_dq_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
+    attn_dkv_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
   } else {
     attn_dq_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
     attn_dkv_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);

@@ -6,7 +6,8 @@
 // RNE; x - hi is exact in fp32) and a b ~ hi hi + hi lo + lo hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: <= 3 * 2^-16 = 4.6e-5
 // relative error per product in the worst case (4e-6 typical), 3 MFMAs of 16 cycles where the f32-input MFMA kernels of attn_f32_mfma.hip spend 8 of 32.  The
 // softmax statistics, exp2 and every elementwise step stay fp32; P and dS are split like any other operand.  fp32 storage, no
-// token mask, dim_head 64, q not pre-scaled (the masked / bf16-storage / dim_head 32 calls stay on the f32 kernels).
+// token mask, dim_head 64, q not pre-scaled (the masked / bf16-storage / dim_head 32 calls stay on the f32 kernels).  A dim_head-128
+// parity-mode attention takes the f32-input MFMA kernels (attn_f32_mfma.hip) under this arithmetic too: at least as accurate.
 //
 // One workgroup = 4 wavefronts = 64 queries (forward, dQ) or 64 keys (dK/dV) of one (clip, head); the opposite operand streams
 // through LDS in tiles of 32 rows, split while it is staged.  As in attn_f32_mfma.hip everything is computed TRANSPOSED, so the row

@@ -92,7 +92,7 @@ int make_dims(const avf_layer_cfg* c, Dims* d) {
               "layer: resid_bf16 needs the bf16 path, dim %% 8 == 0 and dim <= 1536 (dim=%d)", c->dim);
   if (c->dtype == AVF_BF16) {
     AVF_REQUIRE(d->D % 8 == 0 && d->I % 8 == 0 && d->M % 8 == 0, "layer(bf16): dim, inner and mlp_dim must be multiples of 8");
-    AVF_REQUIRE(d->dh == 32 || d->dh == 64, "layer(bf16): dim_head must be 32 or 64 (got %d)", d->dh);
+    AVF_REQUIRE(d->dh == 32 || d->dh == 64 || d->dh == 128, "layer(bf16): dim_head must be 32, 64 or 128 (got %d)", d->dh);
   } else {
     AVF_REQUIRE(d->D % 4 == 0 && d->I % 4 == 0 && d->M % 4 == 0, "layer(f32): dim, inner and mlp_dim must be multiples of 4");
   }

@@ -12,6 +12,9 @@ Extra keyword ``compute_dtype``: ``"mx8"`` (the bf16 mode with MX-FP8 operands o
 and net.3 and the backward dX GEMMs of net.3, net.0 and to_out - BASELINE config 5; tolerance against the bf16 mode stated in tests/test_gpu_mx8.py), ``"bf16"`` (throughput mode: bf16 MFMA, fp32 accumulate / LayerNorm /
 softmax statistics / residual stream) or ``"f32"`` (parity mode: fp32 MFMA + fp32 attention; matches the
 fp32 CPU reference to ~1e-5).
+
+Head widths (``dim_head``): ``"bf16"``, ``"mx8"`` and ``residual_dtype="bf16"`` take 32, 64 and 128; ``"f32"`` takes 8, 16, 32,
+64 and 128.  Any other width fails at the first forward with a library error naming dim_head.
 """
 from __future__ import annotations
 
