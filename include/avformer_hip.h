@@ -312,6 +312,50 @@ int avf_au_loss_sum(const float* logits, int64_t ld_logits, const float* labels,
 int avf_au_loss_wide(const float* logits, int64_t ld_logits, const float* labels, int64_t ld_labels, const float* pos_weight,
                      float ignore, int rows, int ncls, int width, int sum_mode, float* loss, float* grad_wide, void* stream);
 
+/* ---- the task losses of the multi-task step (train.py:146,229; models/loss.py) ----------------
+ * One single-workgroup launch computes the expression (EX), action-unit (AU) and valence / arousal (VA) losses on the model's
+ * output rows out [rows, width] (row stride ld_out) and their gradient in that layout; nothing synchronises with the host.
+ *   y_ex  int64 [rows]            class 0..6, or ex_ignore; null: no EX loss
+ *   y_au  fp32 [rows, 12] (ld_au) rows whose FIRST label == au_ignore are dropped; null: no AU loss
+ *   y_va  fp32 [rows, va_ncols] (ld_va) labels == va_ignore are dropped per column; null: no VA loss
+ *   losses[3] = (ex, au, va); counts[3] = valid EX rows, AU labels != au_ignore, VA labels != va_ignore (as fp32);
+ *   grad_wide [rows, width] contiguous: columns ex_col..+6 hold d losses[0] / d out, au_col..+11 d losses[1] / d out,
+ *   va_col..+va_ncols-1 d losses[2] / d out; zero everywhere else and in the block of a task whose labels are null.
+ * EX: cross-entropy with class weights ex_weight (nn.CrossEntropyLoss) or the focal loss of loss.py:398-466 (ex_weight = alpha;
+ * 'mean' = sum / (rows x valid rows), ignored rows gather class 0 and are masked).  AU: AULoss (loss.py:63-103) or DiceAULoss
+ * (loss.py:149-176: unweighted per-unit Dice + 5 x the pos-weighted BCE mean).  VA: va_weight[0] CCC(column 0) + va_weight[1]
+ * CCC(column 1) with CCCLoss of loss.py:271-313 (unbiased variances, divided by `rows` as counted before the drop, 0 without a
+ * gradient when at most one row is left), on tanh(out) when va_tanh is set.  Every row ignored: NaN for EX and AU as the
+ * reference.  normalize: each loss (and its gradient) is divided by its count, and is 0 where the count is 0. */
+#define AVF_TASK_LOSS_EX_CLASSES 7
+#define AVF_TASK_LOSS_AU_UNITS 12
+enum { AVF_EX_CROSS_ENTROPY = 0, AVF_EX_FOCAL = 1 };
+enum { AVF_AU_BCE = 0, AVF_AU_DICE_BCE = 1 };
+typedef struct avf_task_loss_cfg {
+  int32_t ex_mode, au_mode;
+  int32_t ex_col, au_col, va_col; /* first column of each block in the row: 12, 0, 19 in the reference's layout */
+  int32_t va_ncols;               /* 2 (valence, arousal) or 1 */
+  int32_t va_tanh;                /* 1: the CCC is taken on tanh(out), derivative included */
+  int32_t normalize;
+  int32_t ex_use_ignore;          /* 0: no ignore index (then focal 'mean' = sum / rows) */
+  int32_t reserved;
+  int64_t ex_ignore;
+  float gamma, smooth;            /* focal */
+  float ex_weight[AVF_TASK_LOSS_EX_CLASSES];
+  float pos_weight[AVF_TASK_LOSS_AU_UNITS];
+  float au_ignore, va_ignore;
+  float va_weight[2];
+  float reserved2;
+} avf_task_loss_cfg;
+size_t avf_sizeof_task_loss_cfg(void);
+int avf_task_loss(const float* out, int64_t ld_out, const int64_t* y_ex, const float* y_au, int64_t ld_au, const float* y_va,
+                  int64_t ld_va, const avf_task_loss_cfg* cfg, int rows, int width, float* losses, float* counts,
+                  float* grad_wide, void* stream);
+/* Backward of the above in one launch: dout [rows, width] = grad_wide scaled per column block by the incoming gradients of the
+ * three losses (device scalars; null: that block is zero).  Columns outside the blocks are zero. */
+int avf_task_loss_bwd(const float* grad_wide, const float* g_ex, const float* g_au, const float* g_va,
+                      const avf_task_loss_cfg* cfg, int rows, int width, float* dout, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

@@ -38,6 +38,18 @@ class LayerPtrs(C.Structure):
     _fields_ = [(n, _vp) for n in PARAM_FIELDS]
 
 
+class TaskLossCfg(C.Structure):
+    """avf_task_loss_cfg"""
+    _fields_ = [("ex_mode", C.c_int32), ("au_mode", C.c_int32), ("ex_col", C.c_int32), ("au_col", C.c_int32), ("va_col", C.c_int32),
+                ("va_ncols", C.c_int32), ("va_tanh", C.c_int32), ("normalize", C.c_int32), ("ex_use_ignore", C.c_int32),
+                ("reserved", C.c_int32), ("ex_ignore", C.c_int64), ("gamma", C.c_float), ("smooth", C.c_float),
+                ("ex_weight", C.c_float * 7), ("pos_weight", C.c_float * 12), ("au_ignore", C.c_float), ("va_ignore", C.c_float),
+                ("va_weight", C.c_float * 2), ("reserved2", C.c_float)]
+
+
+EX_CROSS_ENTROPY, EX_FOCAL = 0, 1
+AU_BCE, AU_DICE_BCE = 0, 1
+
 # name -> (restype, argtypes); every symbol declared in include/avformer_hip.h
 SIGNATURES = {
     "avf_version": (_int, []),
@@ -93,6 +105,9 @@ SIGNATURES = {
     "avf_au_loss": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _vp, _vp, _vp]),
     "avf_au_loss_sum": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _vp, _vp, _vp]),
     "avf_au_loss_wide": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "avf_sizeof_task_loss_cfg": (_sz, []),
+    "avf_task_loss": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "avf_task_loss_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
@@ -172,6 +187,9 @@ def load(build_if_missing: bool = True):
             fn.restype = res
             fn.argtypes = args
         # a stale .so (or an edited struct) must not be called with structs of another layout
+        if lib.avf_sizeof_task_loss_cfg() != C.sizeof(TaskLossCfg):
+            raise HipLibraryError(f"{path}: avf_task_loss_cfg is {lib.avf_sizeof_task_loss_cfg()} bytes in the library but "
+                                  f"{C.sizeof(TaskLossCfg)} in this binding - rebuild with python __graft_entry__.py")
         if lib.avf_sizeof_layer_cfg() != C.sizeof(LayerCfg) or lib.avf_sizeof_layer_params() != C.sizeof(LayerPtrs):
             raise HipLibraryError(
                 f"{path}: avf_layer_cfg / avf_layer_params are {lib.avf_sizeof_layer_cfg()} / "

@@ -19,8 +19,7 @@ import torch
 from torch import nn
 
 from .heads import AU_former, ResFormerTokens, TFormer, VA_former, tformer_AU_head
-from .loss import AULoss
-from .models import _TaskLossMixin
+from .models import REFERENCE_TASK_LOSSES, _TaskLossMixin
 
 
 class _PoolTile(nn.Module):
@@ -78,7 +77,7 @@ class _FormerTask(nn.Module, _TaskLossMixin):
 class SpatialFormerModel(_FormerTask):
     """registry name ``sformer`` (sformer.py:338-382): per-frame features -> fc head, AU logits from ``AU_former``"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
         self.base_model = ResFormerShell(backbone, dropout=0.2, compute_dtype=compute_dtype)
@@ -87,10 +86,9 @@ class SpatialFormerModel(_FormerTask):
         self.fc = _fc_head(512)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype)
         self.va_head = VA_former(dropout=0.2, compute_dtype=compute_dtype)   # sformer.py:358
-        # DEVIATION, on purpose: the reference's SpatialFormer trains AU with DiceAULoss (multi-label Dice + 5 x weighted BCE,
-        # sformer.py:362, loss.py:149-176); this entry uses the AULoss of the path SURVEY.md section 8 scopes (loss.py:63-103,
-        # what avformer / vformer / tformer use).  INTEGRATION.md section 4 says so.
-        self.loss_AU = AULoss()
+        # task_losses="plain" keeps the AULoss of the path SURVEY.md section 8 scopes; "reference" builds what the reference's
+        # SpatialFormer trains with: DiceAULoss, cross-entropy and CCC (sformer.py:359-363)
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['sformer'])
 
     def forward(self, x):
         features = self.base_model(self._select(x))
@@ -122,14 +120,14 @@ class _VideoModel(nn.Module):
 class VisualFormerModel(_FormerTask):
     """registry name ``vformer`` (vformer.py:358-387): S-Former frames -> ``TFormer`` over 16 frames -> fc head"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
         self.video_model = _VideoModel(backbone, 512, False, compute_dtype)
         self._config(modality, task)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
-        self.loss_AU = AULoss()
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vformer'])
 
     def forward(self, x):
         return self.fc(self.video_model(self._select(x)))
@@ -139,7 +137,7 @@ class SpatialTemporalFormerModel(_FormerTask):
     """registry name ``tformer`` (tformer.py:405-436): per-frame AU tokens -> ``TFormer(dim=1536)`` -> fc head, AU logits
     from ``tformer_AU_head`` on the [B, 12, 128] view of the temporal feature"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
         self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype)
@@ -147,7 +145,7 @@ class SpatialTemporalFormerModel(_FormerTask):
         self.task, self.modes = task, ["clip"]
         self.au_head = tformer_AU_head(dropout=0.2, compute_dtype=compute_dtype)
         self.fc = _fc_head(128 * 12)
-        self.loss_AU = AULoss()
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['tformer'])
 
     def forward(self, x):
         f = self.video_model(self._select(x))

@@ -22,7 +22,7 @@ from torch import nn
 
 from . import ops
 from .heads import AU_former, TFormer, former_AU_head, tformer_AU_head  # noqa: F401
-from .loss import AULoss
+from .loss import AULoss, CCCLoss, CrossEntropyEX, DiceAULoss, FocalLoss_Ori, MultiTaskLoss
 from .transformer import Transformer
 
 
@@ -58,18 +58,70 @@ class VisualFormer(nn.Module):
         return self.au_head.tokens(self.video_model(x))  # avformer.py:99
 
 
+# the criteria each task model of the reference owns (loss_EX, loss_AU, VA weights): avformer.py:89-91 and 122, sformer.py:359-363
+# and 420, vformer.py:375-379 and 404, tformer.py:423-427 and 454
+REFERENCE_TASK_LOSSES = {
+    'avformer': ('focal', 'bce', (2.0, 1.0)),
+    'sformer': ('ce', 'dice', (1.0, 1.0)),
+    'vformer': ('ce', 'bce', (2.0, 1.0)),
+    'tformer': ('ce', 'bce', (2.0, 1.0)),
+}
+
+
 class _TaskLossMixin:
+    """``get_au_loss`` / ``get_ex_loss`` / ``get_va_loss`` / ``get_mt_loss`` on the [B, 21] row, as train.py:136-147 calls them.
+
+    ``task_losses="plain"`` (default): AULoss on its kernel, a plain cross-entropy and a plain-torch CCC with biased variances.
+    ``task_losses="reference"``: the model owns ``loss_EX`` / ``loss_AU`` / ``loss_VA`` as its reference counterpart does
+    (REFERENCE_TASK_LOSSES) and the three methods run on the fused loss kernel.  ``get_mt_loss`` uses the reference's criteria
+    in either setting (sformer.py:423-449; the reference defines it for ``sformer`` only)."""
+    task_losses = "plain"
+    _recipe = ('ce', 'bce', (2.0, 1.0))
+
+    def _init_task_losses(self, task_losses, recipe):
+        if task_losses not in ("plain", "reference"):
+            raise ValueError(f"task_losses must be 'plain' or 'reference', got {task_losses!r}")
+        self.task_losses, self._recipe = task_losses, recipe
+        self.loss_AU = AULoss()
+        if task_losses == "reference":
+            ex, au, va_weights = recipe
+            self.loss_EX = FocalLoss_Ori(num_class=7, gamma=2.0, ignore_index=7, reduction='mean') if ex == 'focal' \
+                else CrossEntropyEX(ignore_index=7)
+            if au == 'dice':
+                self.loss_AU = DiceAULoss()
+            self.loss_VA = CCCLoss()
+            self.loss_MT = MultiTaskLoss(self.loss_EX, self.loss_AU, self.loss_VA, va_weights)
+
+    def _mt(self):
+        mt = self._modules.get('loss_MT') or self.__dict__.get('_plain_mt')
+        if mt is None:  # "plain": the reference's criteria, built on first use and kept out of the module tree
+            ex, au, va_weights = self._recipe
+            mt = MultiTaskLoss(FocalLoss_Ori(num_class=7, gamma=2.0, ignore_index=7) if ex == 'focal' else CrossEntropyEX(ignore_index=7),
+                               DiceAULoss() if au == 'dice' else AULoss(), CCCLoss(), va_weights)
+            self.__dict__['_plain_mt'] = mt
+        return mt
+
+    def _au_on_own_kernel(self):
+        # an AULoss wrapped by dp.DataParallel keeps its (sum, count) collective, which lives on its own kernel
+        return isinstance(self.loss_AU, AULoss) and (self.task_losses == "plain" or self.loss_AU.global_mean is not None)
+
     def get_au_loss(self, y_pred, y_true):
         # loss on the AU slots 0..11 of the [B,21] row (train.py:136-138 / the reference models' get_au_loss)
-        if y_true.dim() == 2 and y_true.shape[1] == 12 and hasattr(self.loss_AU, "forward_rows"):
-            return self.loss_AU.forward_rows(y_pred, y_true)
-        return self.loss_AU(y_pred[:, :12], y_true)
+        if self._au_on_own_kernel():
+            if y_true.dim() == 2 and y_true.shape[1] == 12 and hasattr(self.loss_AU, "forward_rows"):
+                return self.loss_AU.forward_rows(y_pred, y_true)
+            return self.loss_AU(y_pred[:, :12], y_true)
+        return self._mt()(y_pred, y_au=y_true)[1]
 
     def get_ex_loss(self, y_pred, y_true):
-        # EX / VA tasks are outside the hot path; plain PyTorch equivalents
+        if self.task_losses == "reference":
+            return self._mt()(y_pred, y_ex=y_true)[0]
         return nn.functional.cross_entropy(y_pred[:, 12:19], y_true.view(-1), ignore_index=7)
 
     def get_va_loss(self, y_pred, y_true):
+        if self.task_losses == "reference":
+            return self._mt()(y_pred, y_va=y_true)[2]
+
         def ccc_loss(p, t):
             pm, tm = p.mean(), t.mean()
             cov = ((p - pm) * (t - tm)).mean()
@@ -77,10 +129,16 @@ class _TaskLossMixin:
         v, a = torch.tanh(y_pred[:, 19]), torch.tanh(y_pred[:, 20])
         return 2 * ccc_loss(v, y_true[:, 0]) + ccc_loss(a, y_true[:, 1])
 
+    def get_mt_loss(self, y_pred, y_true, normalize=False):
+        """``[loss_ex, loss_au, loss_va]`` for the label dict ``{'EX', 'AU', 'VA'}`` of train.py:208-213: one launch, and one more
+        in backward.  ``normalize=True`` divides each by its count of valid labels on the device (0 for a count of 0); the
+        reference counts through numpy on the host."""
+        return self._mt()(y_pred, y_true['EX'], y_true['AU'], y_true['VA'], normalize=normalize)
+
 
 class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
     def __init__(self, modality='A;V;M', video_pretrained=True, audio_pretrained=True, task='EX',
-                 video_weights=None, audio_weights=None, compute_dtype="bf16"):
+                 video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.audio_model = AudioFormer(compute_dtype=compute_dtype)
         self.video_model = VisualFormer(compute_dtype=compute_dtype)
@@ -93,7 +151,7 @@ class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
         self.task = task
         self.au_head = former_AU_head(emb_dim=256, dropout=0.2, compute_dtype=compute_dtype)
         self.modes = ['clip', 'audio_features']
-        self.loss_AU = AULoss()
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['avformer'])
         self.concurrent_streams = True
         self._side_streams = {}
 
@@ -160,7 +218,7 @@ class SyntheticAVFormer(nn.Module, _TaskLossMixin):
     [B, T_v + T_a, dim] token sequence, mean pooling, 12 AU logits in the reference's [B,21] layout."""
 
     def __init__(self, dim=512, depth=6, heads=8, dim_head=64, mlp_dim=1024, t_video=196, t_audio=128, task='AU',
-                 compute_dtype="bf16", residual_dtype="f32", dropout=0.0):
+                 compute_dtype="bf16", residual_dtype="f32", dropout=0.0, task_losses="plain"):
         super().__init__()
         self.task = task
         self.modes = ['clip', 'audio_features']
@@ -170,7 +228,7 @@ class SyntheticAVFormer(nn.Module, _TaskLossMixin):
         self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout, compute_dtype=compute_dtype,
                                        residual_dtype=residual_dtype)
         self.au_fc = nn.Linear(dim, 12)
-        self.loss_AU = AULoss()
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['avformer'])
 
     def forward(self, x):
         # fusion on the SEQUENCE axis + positional embedding: cat([clip, audio], 1) + pos_embedding, then the stack and

@@ -591,6 +591,40 @@ def au_loss_wide(out: torch.Tensor, labels: torch.Tensor, pos_weight: torch.Tens
     return loss, grad
 
 
+def task_loss(out: torch.Tensor, y_ex: Optional[torch.Tensor], y_au: Optional[torch.Tensor], y_va: Optional[torch.Tensor],
+              cfg: "_lib.TaskLossCfg"):
+    """The EX / AU / VA losses on the model's output rows ``out`` [rows, width] in one launch (avf_task_loss) ->
+    (losses [3], counts [3], grad_wide [rows, width]).  A label tensor that is None switches its task off: its loss is 0 and its
+    column block of grad_wide zero.  y_ex int64 [rows]; y_au fp32 [rows, 12]; y_va fp32 [rows, cfg.va_ncols]."""
+    _need_cuda(out, y_ex, y_au, y_va)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.dtype == torch.float32
+    rows, width = out.shape
+    assert y_ex is None or (y_ex.dtype == torch.int64 and y_ex.shape == (rows,) and y_ex.is_contiguous())
+    assert y_au is None or (y_au.dtype == torch.float32 and y_au.shape == (rows, 12) and y_au.stride(1) == 1)
+    assert y_va is None or (y_va.dtype == torch.float32 and y_va.shape == (rows, cfg.va_ncols) and y_va.stride(1) == 1)
+    res = torch.empty(6, dtype=torch.float32, device=out.device)
+    grad = torch.empty((rows, width), dtype=torch.float32, device=out.device)
+    _lib.check(_lib.load().avf_task_loss(_ptr(out), out.stride(0), _ptr(y_ex), _ptr(y_au), 0 if y_au is None else y_au.stride(0),
+                                         _ptr(y_va), 0 if y_va is None else y_va.stride(0), C.byref(cfg), rows, width,
+                                         C.c_void_p(res.data_ptr()), C.c_void_p(res.data_ptr() + 12), _ptr(grad), _stream()),
+               "task_loss")
+    return res[:3], res[3:], grad
+
+
+def task_loss_bwd(grad_wide: torch.Tensor, g_ex: Optional[torch.Tensor], g_au: Optional[torch.Tensor],
+                  g_va: Optional[torch.Tensor], cfg: "_lib.TaskLossCfg") -> torch.Tensor:
+    """grad_wide of task_loss scaled per column block by the incoming gradients of the three losses (fp32 device scalars; None:
+    that block is zero) -> d / d out [rows, width], one launch (avf_task_loss_bwd)"""
+    _need_cuda(grad_wide, g_ex, g_au, g_va)
+    assert grad_wide.dim() == 2 and grad_wide.is_contiguous() and grad_wide.dtype == torch.float32
+    assert all(g is None or (g.dtype == torch.float32 and g.numel() == 1) for g in (g_ex, g_au, g_va))
+    rows, width = grad_wide.shape
+    dout = torch.empty_like(grad_wide)
+    _lib.check(_lib.load().avf_task_loss_bwd(_ptr(grad_wide), _ptr(g_ex), _ptr(g_au), _ptr(g_va), C.byref(cfg), rows, width,
+                                             _ptr(dout), _stream()), "task_loss_bwd")
+    return dout
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
