@@ -111,7 +111,8 @@ int avf_device_ok(void);
 
 /* ---- per-operator entry points --------------------------------------------------------- */
 
-/* nn.LayerNorm(dim) forward - heads.py:178-185.  x fp32 [rows,dim] -> y (y_dtype) ; mean/rstd fp32 [rows]. */
+/* nn.LayerNorm(dim) forward - heads.py:178-185.  x fp32 [rows,dim] -> y (y_dtype) ; mean/rstd fp32 [rows].
+ * (fp32 x only, here and in avf_layernorm_bwd; a bf16 x goes through avf_layernorm_fwd_ex / avf_layernorm_bwd_ex below) */
 int avf_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype,
                       float* mean, float* rstd, int64_t rows, int dim, float eps, void* stream);
 
@@ -122,6 +123,28 @@ size_t avf_layernorm_bwd_workspace_bytes(int64_t rows, int dim);
 int avf_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
                       const float* rstd, const float* dres, float* dx, void* dx_lo, float* dgamma,
                       float* dbeta, float* dcolsum, void* workspace, int64_t rows, int dim, void* stream);
+
+/* The general LayerNorm door: every storage type and option that the layer calls use (the two entry points above pin x to
+ * fp32 and have no dropout).  Same math, same workspace size query.
+ *   forward:  x_dtype AVF_F32 | AVF_BF16.  A bf16 x needs a bf16 y, dim % 4 == 0 and dim <= 1536 (error otherwise).
+ *   backward: x_dtype / dres_dtype AVF_F32 | AVF_BF16 (dres nullable; its dtype is then ignored).  A bf16 x needs bf16 dy,
+ *             dim % 4 == 0, dim <= 1536; a bf16 dres needs bf16 dy, dx_lo, dim % 4 == 0, dim <= 1536.  Outputs: dx (fp32,
+ *             nullable when dim % 4 == 0 and dim <= 1536), dx_lo (bf16, nullable), dx_m (bf16, nullable), at least one of
+ *             dx / dx_lo; dgamma / dbeta [dim]; dcolsum (nullable).
+ *   dropout:  (seed_lo, seed_hi, layer_index, site, p) name a dropout site exactly as avf_dropout_factors does; p == 0 is
+ *             no dropout.  With f = those factors and g = dres + LN'(dy) the outputs are
+ *               without dx_m (one-row-per-wave kernels):   dx = g, dx_lo = bf16(f * g),                dcolsum = sum_r f * g
+ *               with dx_m (all-bf16 streams, dim % 8 == 0): dx = g, dx_lo = bf16(g), dx_m = bf16(f * g), dcolsum = sum_r f * g
+ *             i.e. dx is never masked, the column sums always are, and dx_lo is the masked image only when there is no dx_m.
+ *             dx_m needs p > 0, bf16 dy / x / dres and dx_lo (error otherwise).
+ * dgamma / dbeta / dcolsum are sums of the fp32 values (before any bf16 store), combined in a fixed order: the same inputs
+ * give the same bits.  No MX-FP8 image here (see avf_layernorm_fwd_mx8 / avf_layernorm_bwd_mx8). */
+int avf_layernorm_fwd_ex(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
+                         float* rstd, int64_t rows, int dim, float eps, void* stream);
+int avf_layernorm_bwd_ex(const void* dy, int dy_dtype, const void* x, int x_dtype, const float* gamma, const float* mean,
+                         const float* rstd, const void* dres, int dres_dtype, float* dx, void* dx_lo, void* dx_m, float* dgamma,
+                         float* dbeta, float* dcolsum, void* workspace, int64_t rows, int dim, uint32_t seed_lo,
+                         uint32_t seed_hi, int layer_index, int site, float p, void* stream);
 
 /* column sums (bias gradients): out[c] = sum_r in[r,c].  workspace >= avf_colsum_workspace_bytes. */
 size_t avf_colsum_workspace_bytes(int64_t rows, int cols);

@@ -60,6 +60,9 @@ SIGNATURES = {
     "avf_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _f, _vp]),
     "avf_layernorm_bwd_workspace_bytes": (_sz, [_i64, _int]),
     "avf_layernorm_bwd": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    "avf_layernorm_fwd_ex": (_int, [_vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _f, _vp]),
+    "avf_layernorm_bwd_ex": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int,
+                                    C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
     "avf_colsum_workspace_bytes": (_sz, [_i64, _int]),
     "avf_colsum": (_int, [_vp, _int, _i64, _int, _i64, _vp, _vp, _vp]),
     "avf_cast_f32_to_bf16": (_int, [_vp, _vp, _i64, _vp]),

@@ -194,6 +194,26 @@ extern "C" int avf_layernorm_bwd(const void* dy, int dy_dtype, const float* x, c
   return layernorm_bwd(dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dx_lo, dgamma, dbeta, dcolsum, workspace, rows,
                        dim, (hipStream_t)stream);
 }
+extern "C" int avf_layernorm_fwd_ex(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype,
+                                    float* mean, float* rstd, int64_t rows, int dim, float eps, void* stream) {
+  AVF_REQUIRE(x && gamma && beta && y && mean && rstd, "layernorm_fwd_ex: null pointer");
+  AVF_REQUIRE(x_dtype == AVF_F32 || x_dtype == AVF_BF16, "layernorm_fwd_ex: bad x_dtype %d", x_dtype);
+  return layernorm_fwd(x, gamma, beta, y, y_dtype, mean, rstd, rows, dim, eps, (hipStream_t)stream, nullptr, nullptr, x_dtype);
+}
+extern "C" int avf_layernorm_bwd_ex(const void* dy, int dy_dtype, const void* x, int x_dtype, const float* gamma,
+                                    const float* mean, const float* rstd, const void* dres, int dres_dtype, float* dx,
+                                    void* dx_lo, void* dx_m, float* dgamma, float* dbeta, float* dcolsum, void* workspace,
+                                    int64_t rows, int dim, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site,
+                                    float p, void* stream) {
+  AVF_REQUIRE(dy && x && gamma && mean && rstd && dgamma && dbeta && workspace, "layernorm_bwd_ex: null pointer");
+  AVF_REQUIRE((x_dtype == AVF_F32 || x_dtype == AVF_BF16) && (dres_dtype == AVF_F32 || dres_dtype == AVF_BF16),
+              "layernorm_bwd_ex: bad x_dtype %d / dres_dtype %d", x_dtype, dres_dtype);
+  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "layernorm_bwd_ex: bad dropout site %d / p %g", site,
+              (double)p);
+  const DropCfg d = p > 0.f ? make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site) : kNoDrop;
+  return layernorm_bwd(dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dx_lo, dgamma, dbeta, dcolsum, workspace, rows, dim,
+                       (hipStream_t)stream, d, nullptr, dres ? dres_dtype : AVF_F32, x_dtype, nullptr, nullptr, dx_m);
+}
 extern "C" size_t avf_colsum_workspace_bytes(int64_t rows, int cols) { return colsum_ws(rows, cols); }
 extern "C" int avf_colsum(const void* in, int in_dtype, int64_t rows, int cols, int64_t ld, float* out,
                           void* workspace, void* stream) {

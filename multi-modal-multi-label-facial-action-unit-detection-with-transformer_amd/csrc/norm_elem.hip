@@ -775,6 +775,7 @@ int layernorm_bwd(const void* dy, int dy_dtype, const void* xv, const float* gam
               "layernorm_bwd: a bf16 residual gradient needs bf16 dy, a bf16 output, dim %% 4 == 0, dim <= 1536, and with dropout a "
               "separate masked image");
   AVF_REQUIRE(dx || dx_lo, "layernorm_bwd: no output");
+  AVF_REQUIRE(dx || (dim % 4 == 0 && dim <= 1536), "layernorm_bwd: dim %d runs the general kernel, which needs the fp32 dx", dim);
   AVF_REQUIRE(!drop.thresh16 || (dim % 4 == 0 && dim <= 1536), "layernorm_bwd: dropout needs dim %% 4 == 0 and dim <= 1536");
   AVF_REQUIRE((size_t)3 * dim * sizeof(float) <= 64 * 1024, "layernorm_bwd: dim %d too large", dim);
   TimingScope ts(KC_LAYERNORM, 0.0,

@@ -88,6 +88,50 @@ def layernorm_bwd(dy, x, weight, mean, rstd, dres=None, want_lo=False, want_cols
     return dx, dx_lo, dg, db, cs
 
 
+def layernorm_fwd_ex(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, out_dtype=torch.float32,
+                     y: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """layernorm_fwd for an fp32 or bf16 x [rows, D] (avf_layernorm_fwd_ex); y: optional preallocated [rows, D] output."""
+    _need_cuda(x, weight, bias, y)
+    lib = _lib.load()
+    assert x.is_contiguous() and x.dim() == 2 and (y is None or (y.is_contiguous() and y.shape == x.shape))
+    rows, D = x.shape
+    if y is None:
+        y = torch.empty(x.shape, dtype=torch_dtype(out_dtype), device=x.device)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _lib.check(lib.avf_layernorm_fwd_ex(_ptr(x), avf_dtype(x.dtype), _ptr(weight), _ptr(bias), _ptr(y), avf_dtype(y.dtype),
+                                        _ptr(mean), _ptr(rstd), rows, D, float(eps), _stream()), "layernorm_fwd_ex")
+    return y, mean, rstd
+
+
+def layernorm_bwd_ex(dy, x, weight, mean, rstd, dres=None, want_dx=True, want_lo=False, want_m=False, want_colsum=False,
+                     drop=None, dx_lo=None, dx_m=None):
+    """avf_layernorm_bwd_ex on [rows, D] tensors of any accepted storage type -> dx (fp32 or None), dx_lo, dx_m (bf16 or
+    None), dgamma, dbeta, colsum or None.  drop: (seed, layer, site, p) as ops.dropout_factors takes them, or None.
+    dx_lo / dx_m: optional preallocated [rows, D] bf16 outputs (they imply want_lo / want_m)."""
+    _need_cuda(dy, x, weight, mean, rstd, dres, dx_lo, dx_m)
+    lib = _lib.load()
+    assert all(t is None or (t.is_contiguous() and t.shape == x.shape) for t in (dy, x, dres, dx_lo, dx_m)) and x.dim() == 2
+    rows, D = x.shape
+    dev = x.device
+    dx = torch.empty(x.shape, dtype=torch.float32, device=dev) if want_dx else None
+    if dx_lo is None and want_lo:
+        dx_lo = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+    if dx_m is None and want_m:
+        dx_m = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+    dg = torch.empty(D, dtype=torch.float32, device=dev)
+    db = torch.empty(D, dtype=torch.float32, device=dev)
+    cs = torch.empty(D, dtype=torch.float32, device=dev) if want_colsum else None
+    ws = _bytes(lib.avf_layernorm_bwd_workspace_bytes(rows, D), dev)
+    seed, layer, site, p = drop if drop is not None else (0, 0, 0, 0.0)
+    _lib.check(lib.avf_layernorm_bwd_ex(_ptr(dy), avf_dtype(dy.dtype), _ptr(x), avf_dtype(x.dtype), _ptr(weight), _ptr(mean),
+                                        _ptr(rstd), _ptr(dres), avf_dtype(dres.dtype) if dres is not None else F32, _ptr(dx),
+                                        _ptr(dx_lo), _ptr(dx_m), _ptr(dg), _ptr(db), _ptr(cs), _ptr(ws), rows, D,
+                                        seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, layer, site, float(p), _stream()),
+               "layernorm_bwd_ex")
+    return dx, dx_lo, dx_m, dg, db, cs
+
+
 def colsum(t: torch.Tensor) -> torch.Tensor:
     """column sums over all leading axes; a 2-D view whose rows are a constant stride apart (unit column stride) is read
     in place"""
