@@ -379,6 +379,57 @@ int avf_task_loss(const float* out, int64_t ld_out, const int64_t* y_ex, const f
 int avf_task_loss_bwd(const float* grad_wide, const float* g_ex, const float* g_au, const float* g_va,
                       const avf_task_loss_cfg* cfg, int rows, int width, float* dout, void* stream);
 
+/* ---- the evaluation metrics of the validation loop (train.py:106-169; metrics/accf1.py, metrics/cccmetric.py) ----
+ * avf_eval_update: ONE single-workgroup launch per validation batch.  It reads the model's rows out [rows, >= 21] (fp32, row
+ * stride ld_out) and the label arrays in the layout of the task losses above (any of them null: that task is skipped and its
+ * slots are left as they were) and ADDS the batch's sufficient statistics into state, a device array of
+ * AVF_EVAL_STATE_WORDS fp64 words which the caller zeroes once per evaluation.  Counts are held as fp64 so that the state is one
+ * dtype - one buffer, one collective; they are exact up to 2^53 rows.  Layout:
+ *   [AVF_EVAL_EX_CONF + 7 t + p]     EX confusion counts, t the label, p = argmax of the seven EX logits by torch's rule (first
+ *                                    maximal index; a NaN logit counts as maximal).  A row whose label equals ex_ignore, or
+ *                                    lies outside 0..6, is dropped.
+ *   [AVF_EVAL_AU_STATS + 12 k + u]   k = 0..4: true positives, false positives, false negatives, correct, labelled of unit u,
+ *                                    over the ENTRIES whose label differs from au_ignore.  The prediction is the reference's
+ *                                    round(sigmoid(x)) in fp32: 1 for x > 2^-23 (where a correctly rounded fp32 sigmoid leaves
+ *                                    0.5), 0 otherwise.  fp32 sigmoid implementations differ inside (0, 2^-22); outside that band
+ *                                    they all agree with this rule.
+ *   [AVF_EVAL_VA_MOMENTS + 6 j + k]  column j: n, sum x, sum y, sum x^2, sum y^2, sum x y over the rows whose label differs from
+ *                                    va_ignore; x = tanhf(out) in fp32 (out itself when va_tanh is 0), products and sums in fp64.
+ *   [AVF_EVAL_LOSS_SUM], [AVF_EVAL_LOSS_STEPS]  sum of *loss and the number of updates that carried one (loss: optional device
+ *                                    fp32 scalar; null: both words are left alone).
+ *   the remaining words are reserved and never written.
+ * Optional per-row outputs, each may be null: pred_au uint8 [rows, 12], pred_ex int64 [rows], pred_va fp32 [rows, 2] (the tanh
+ * values).  With state null the call only predicts.  Integer counts are folded through integer additions and the fp64 moments
+ * in a fixed order (lane tree, then the waves in index order), so the same sequence of calls gives the same words every time.
+ * Neither entry point allocates or synchronises; both can be captured.
+ *
+ * avf_eval_scores: ONE launch, state -> scores, AVF_EVAL_SCORE_WORDS fp64 words on the device, all arithmetic in fp64:
+ *   0 ex_acc, 1 ex_f1, 2 ex_score, 3 au_acc, 4 au_f1, 5 au_score, 6 ccc_v, 7 ccc_a, 8 va_score, 9 avg_loss, 10 ex_kept_rows,
+ *   11 au_labelled.
+ * EX: accuracy over the kept rows; macro F1 over the classes that occur among the kept rows' labels or predictions (sklearn's
+ * label set); score = 0.67 f1 + 0.33 acc; no kept row: NaN.  AU: accuracy over all labelled entries, mean over the 12 units of
+ * the binary F1 (0 where 2 tp + fp + fn = 0); score = 0.5 f1 + 0.5 acc.  VA: per column 0 for n <= 1, else with the biased
+ * moments 2 cov / (var_x + var_y + (m_x - m_y)^2 + 1e-8); score = their mean.  This is the METRIC's CCC (cccmetric.py:4-34), not
+ * the loss's. */
+#define AVF_EVAL_STATE_WORDS 128
+#define AVF_EVAL_EX_CONF 0
+#define AVF_EVAL_AU_STATS 49
+#define AVF_EVAL_VA_MOMENTS 109
+#define AVF_EVAL_LOSS_SUM 121
+#define AVF_EVAL_LOSS_STEPS 122
+#define AVF_EVAL_SCORE_WORDS 12
+typedef struct avf_eval_cfg {
+  int32_t ex_col, au_col, va_col; /* first column of each block in the row: 12, 0, 19 in the reference's layout */
+  int32_t va_tanh;                /* 1: predictions and moments on tanh(out) (train.py:154) */
+  int64_t ex_ignore;              /* 7 */
+  float au_ignore, va_ignore;     /* -1, -5 */
+} avf_eval_cfg;
+size_t avf_sizeof_eval_cfg(void);
+int avf_eval_update(const float* out, int64_t ld_out, const int64_t* y_ex, const float* y_au, int64_t ld_au, const float* y_va,
+                    int64_t ld_va, const float* loss, const avf_eval_cfg* cfg, int rows, double* state, uint8_t* pred_au,
+                    int64_t* pred_ex, float* pred_va, void* stream);
+int avf_eval_scores(const double* state, const avf_eval_cfg* cfg, double* scores, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

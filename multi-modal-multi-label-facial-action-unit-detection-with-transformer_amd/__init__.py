@@ -9,11 +9,12 @@ from . import _build, _lib, audio, checkpoint, dp, graphs, metrics, ops, optim  
 from ._lib import get_f32_arithmetic, set_f32_arithmetic  # noqa: F401
 from .heads import AU_former, ResFormerTokens, TFormer, VA_former, former_AU_head, tformer_AU_head  # noqa: F401
 from .loss import AULoss, CCCLoss, CrossEntropyEX, DiceAULoss, FocalLoss_Ori, MultiTaskLoss  # noqa: F401
+from .metrics import AccF1Metric, CCCMetric, EvalMetrics, MultiLabelAccF1, evaluate  # noqa: F401
 from .models import (MODEL_REGISTRY, AudioFormer, SyntheticAVFormer, TwoStreamAuralVisualFormer,  # noqa: F401
                      VisualFormer, build_model)
 from .transformer import Transformer  # noqa: F401
 
 __all__ = ["Transformer", "AU_former", "VA_former", "tformer_AU_head", "former_AU_head", "TFormer", "AULoss", "CCCLoss", "CrossEntropyEX",
-           "DiceAULoss", "FocalLoss_Ori", "MultiTaskLoss",
+           "DiceAULoss", "FocalLoss_Ori", "MultiTaskLoss", "AccF1Metric", "CCCMetric", "EvalMetrics", "MultiLabelAccF1", "evaluate",
            "ResFormerTokens", "TwoStreamAuralVisualFormer", "SyntheticAVFormer", "AudioFormer", "VisualFormer", "MODEL_REGISTRY",
            "build_model", "ops", "optim", "set_f32_arithmetic", "get_f32_arithmetic"]

@@ -47,6 +47,12 @@ class TaskLossCfg(C.Structure):
                 ("va_weight", C.c_float * 2), ("reserved2", C.c_float)]
 
 
+class EvalCfg(C.Structure):
+    """avf_eval_cfg"""
+    _fields_ = [("ex_col", C.c_int32), ("au_col", C.c_int32), ("va_col", C.c_int32), ("va_tanh", C.c_int32),
+                ("ex_ignore", C.c_int64), ("au_ignore", C.c_float), ("va_ignore", C.c_float)]
+
+
 EX_CROSS_ENTROPY, EX_FOCAL = 0, 1
 AU_BCE, AU_DICE_BCE = 0, 1
 
@@ -111,6 +117,9 @@ SIGNATURES = {
     "avf_sizeof_task_loss_cfg": (_sz, []),
     "avf_task_loss": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
     "avf_task_loss_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "avf_sizeof_eval_cfg": (_sz, []),
+    "avf_eval_update": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "avf_eval_scores": (_int, [_vp, _vp, _vp, _vp]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
@@ -193,6 +202,9 @@ def load(build_if_missing: bool = True):
         if lib.avf_sizeof_task_loss_cfg() != C.sizeof(TaskLossCfg):
             raise HipLibraryError(f"{path}: avf_task_loss_cfg is {lib.avf_sizeof_task_loss_cfg()} bytes in the library but "
                                   f"{C.sizeof(TaskLossCfg)} in this binding - rebuild with python __graft_entry__.py")
+        if lib.avf_sizeof_eval_cfg() != C.sizeof(EvalCfg):
+            raise HipLibraryError(f"{path}: avf_eval_cfg is {lib.avf_sizeof_eval_cfg()} bytes in the library but "
+                                  f"{C.sizeof(EvalCfg)} in this binding - rebuild with python __graft_entry__.py")
         if lib.avf_sizeof_layer_cfg() != C.sizeof(LayerCfg) or lib.avf_sizeof_layer_params() != C.sizeof(LayerPtrs):
             raise HipLibraryError(
                 f"{path}: avf_layer_cfg / avf_layer_params are {lib.avf_sizeof_layer_cfg()} / "

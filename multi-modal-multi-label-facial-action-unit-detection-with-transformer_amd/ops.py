@@ -669,6 +669,42 @@ def task_loss_bwd(grad_wide: torch.Tensor, g_ex: Optional[torch.Tensor], g_au: O
     return dout
 
 
+def eval_update(out: torch.Tensor, y_ex: Optional[torch.Tensor], y_au: Optional[torch.Tensor], y_va: Optional[torch.Tensor],
+                loss: Optional[torch.Tensor], cfg: "_lib.EvalCfg", state: Optional[torch.Tensor],
+                pred_au: Optional[torch.Tensor] = None, pred_ex: Optional[torch.Tensor] = None,
+                pred_va: Optional[torch.Tensor] = None) -> None:
+    """One launch (avf_eval_update): adds the sufficient statistics of the rows ``out`` [rows, >= 21] and their labels into
+    ``state`` (fp64 [128], layout in include/avformer_hip.h) and / or writes the per-row predictions.  A label tensor that is
+    None leaves its task's slots alone; ``loss`` is an fp32 device scalar or None.  Allocates nothing, synchronises nothing."""
+    _need_cuda(out, y_ex, y_au, y_va, loss, state, pred_au, pred_ex, pred_va)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.dtype == torch.float32
+    rows, width = out.shape
+    assert width >= max(cfg.ex_col + 7, cfg.au_col + 12, cfg.va_col + 2) and min(cfg.ex_col, cfg.au_col, cfg.va_col) >= 0
+    assert y_ex is None or (y_ex.dtype == torch.int64 and y_ex.shape == (rows,) and y_ex.is_contiguous())
+    assert y_au is None or (y_au.dtype == torch.float32 and y_au.shape == (rows, 12) and y_au.stride(1) == 1)
+    assert y_va is None or (y_va.dtype == torch.float32 and y_va.shape == (rows, 2) and y_va.stride(1) == 1)
+    assert loss is None or (loss.dtype == torch.float32 and loss.numel() == 1)
+    assert state is None or (state.dtype == torch.float64 and state.shape == (128,) and state.is_contiguous())
+    assert pred_au is None or (pred_au.dtype == torch.uint8 and pred_au.shape == (rows, 12) and pred_au.is_contiguous())
+    assert pred_ex is None or (pred_ex.dtype == torch.int64 and pred_ex.shape == (rows,) and pred_ex.is_contiguous())
+    assert pred_va is None or (pred_va.dtype == torch.float32 and pred_va.shape == (rows, 2) and pred_va.is_contiguous())
+    _lib.check(_lib.load().avf_eval_update(_ptr(out), out.stride(0), _ptr(y_ex), _ptr(y_au), 0 if y_au is None else y_au.stride(0),
+                                           _ptr(y_va), 0 if y_va is None else y_va.stride(0), _ptr(loss), C.byref(cfg), rows,
+                                           _ptr(state), _ptr(pred_au), _ptr(pred_ex), _ptr(pred_va), _stream()), "eval_update")
+
+
+def eval_scores(state: torch.Tensor, cfg: "_lib.EvalCfg", scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """state [128] -> the twelve fp64 scores on the device in one launch (avf_eval_scores): ex_acc, ex_f1, ex_score, au_acc, au_f1,
+    au_score, ccc_v, ccc_a, va_score, avg_loss, ex_kept_rows, au_labelled"""
+    _need_cuda(state, scores)
+    assert state.dtype == torch.float64 and state.shape == (128,) and state.is_contiguous()
+    if scores is None:
+        scores = torch.empty(12, dtype=torch.float64, device=state.device)
+    assert scores.dtype == torch.float64 and scores.shape == (12,) and scores.is_contiguous()
+    _lib.check(_lib.load().avf_eval_scores(_ptr(state), C.byref(cfg), _ptr(scores), _stream()), "eval_scores")
+    return scores
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""

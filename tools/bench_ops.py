@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-operator micro-benchmarks on the MI355X (tuning aid; not part of the product path).
-usage: python tools/bench_ops.py [gemm_nt|gemm_tn|attn|ln|all] [--rows R]"""
+usage: python tools/bench_ops.py [gemm_nt|gemm_tn|attn|ln|all] [--rows R]
+       python tools/bench_ops.py eval --batch ROWS     (the evaluation metrics; not part of "all")"""
 import argparse
 import os
 import sys
@@ -93,6 +94,64 @@ def ln(R):
     print(f"ln_bwd R={R}: {t * 1e6:8.1f} us  {R * D * 16 / t / 1e9:7.1f} GB/s")
 
 
+def _profiled(fn, iters=20, warm=3):
+    """(kernel launches, device microseconds, wall microseconds) per call of fn, from the torch profiler's device events"""
+    import time
+    from torch.profiler import ProfilerActivity, profile
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / iters * 1e6
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "Memcpy" not in e.name
+          and "Memset" not in e.name]
+    return len(ev) / iters, sum(e.time_range.elapsed_us() for e in ev) / iters, wall
+
+
+def eval_metrics(rows):
+    """one validation batch of `rows` rows: (a) EvalMetrics.update - the fused kernel; (b) the same statistics as plain torch ops
+    on the device: MultiLabelAccF1.update_from_logits plus the EX and VA parts of update_torch; (c) the reference's host recipe of
+    train.py:150-155 with its three device-to-host copies (wall time; the sklearn scoring at the end of the epoch is not in it)"""
+    import numpy as np
+    g = torch.Generator().manual_seed(0)
+    out = torch.randn(rows, 21, generator=g).cuda()
+    labels = {"EX": torch.randint(0, 8, (rows,), generator=g).cuda(), "AU": (torch.rand(rows, 12, generator=g) > 0.6).float().cuda(),
+              "VA": (torch.rand(rows, 2, generator=g) * 2 - 1).cuda()}
+    loss = torch.tensor(0.5, device="cuda")
+    fused = A.EvalMetrics(device="cuda")
+    M = A.metrics
+    au, st = M.MultiLabelAccF1(ignore_index=-1), torch.zeros(128, dtype=torch.float64, device="cuda")
+
+    def plain():
+        au.update_from_logits(out, labels["AU"])
+        st[M.EX_CONF:M.AU_STATS] += M.ex_confusion(torch.argmax(out[:, 12:19], dim=1), labels["EX"], 7).reshape(-1)
+        st[M.VA_MOMENTS:M.LOSS_SUM] += M.va_moments(torch.tanh(out[:, 19:21]), labels["VA"], -5.0).reshape(-1)
+        st[M.LOSS_SUM] += loss.double()
+        st[M.LOSS_STEPS] += 1.0
+
+    host = {"ex": [], "va": [], "au": [], "loss": 0.0}
+
+    def reference():
+        host["loss"] += loss.item()
+        host["ex"].append((torch.argmax(out[:, 12:19], dim=1).detach().cpu().numpy().reshape(-1), labels["EX"].detach().cpu().numpy()))
+        host["va"].append((torch.tanh(out[:, 19:21]).detach().cpu().numpy(), labels["VA"].detach().cpu().numpy()))
+        host["au"].append((np.round(torch.sigmoid(out[:, :12]).detach().cpu().numpy()), labels["AU"].detach().cpu().numpy()))
+        for v in (host["ex"], host["va"], host["au"]):
+            del v[:-1]
+
+    for name, fn in (("fused update", lambda: fused.update(out, labels, loss)), ("plain torch on the device", plain),
+                     ("reference host recipe", reference)):
+        n, dev_us, wall_us = _profiled(fn)
+        print(f"eval rows={rows} {name:26s}: {n:5.1f} launches  {dev_us:8.1f} us device  {wall_us:8.1f} us wall per batch")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
@@ -112,3 +171,5 @@ if __name__ == "__main__":
         attn(a.batch, a.tokens, a.heads, a.dim_head)
     if a.what in ("ln", "all"):
         ln(R)
+    if a.what == "eval":
+        eval_metrics(a.batch)
