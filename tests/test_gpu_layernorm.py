@@ -1,8 +1,8 @@
-"""-m gpu: every LayerNorm kernel that csrc/norm_elem.hip can launch, forward and backward, element by element against the
+"""-m gpu: every LayerNorm kernel that csrc/layernorm.hip can launch, forward and backward, element by element against the
 fp64 reference of tests/layernorm_util.py (bounds and their reasons: that module's docstring; tests/test_layernorm_ref_cpu.py
 shows without a device that they bite).  Reached through avf_layernorm_fwd_ex / avf_layernorm_bwd_ex.
 
-host branch (norm_elem.hip)                       kernels                                             cases below
+host branch (layernorm.hip)                       kernels                                             cases below
 bf16 x, D % 8 == 0                                ln_fwd_row8_kernel<1..3,4>, ln_bwd_row8_kernel      ROW8_CASES
                                                   <1,4>/<2,2>/<3,1> and their DROP forms
 bf16 x, D % 4 == 0 (D % 8 != 0, fp32 dres, or     ln_fwd_reg_kernel<bf16,NV,false,bf16>,              REG16_CASES, test_row8_switched_off
@@ -205,7 +205,7 @@ for D, rows in [(512, 300), (40, 4097), (1048, 8193), (1536, 33), (1024, 8192)]:
     # all-bf16 streams at D %% 8 == 0, which the parent process runs on the row8 kernels
     T.run_case(A.ops, "reg_bf16x(row8 off)", D, rows, T.BF, V(T.BF, T.BF, T.BF, False, True, False, True, 0.0))
     T.run_case(A.ops, "reg_bf16x(row8 off)", D, rows, T.BF, V(T.BF, None, T.BF, True, True, False, True, 0.2))
-# a separate masked image still takes the row8 DROP form (norm_elem.hip: ln_row8_on() || dx_m)
+# a separate masked image still takes the row8 DROP form (layernorm.hip: ln_row8_on() || dx_m)
 T.run_case(A.ops, "row8(row8 off)", 520, 300, T.BF, V(T.BF, T.BF, T.BF, True, True, True, True, 0.2))
 print("ROW8_OFF_OK")
 '''
