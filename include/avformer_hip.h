@@ -476,6 +476,29 @@ int avf_adam_batch_end(void);
 int avf_adam_batch_abort(void);
 int avf_selftest_adam_table(void* stream);
 
+/* Gradient clipping and the learning-rate schedule of a step, decided on the device (opts.py --grad_clip / --n_warmup_steps,
+ * the epoch decays of train()).  ctl is a device block of four floats:
+ *   ctl[0] (out) learning-rate multiplier of this update = ctl[3] * min(1, step / n_warmup_steps)  (1 * ctl[3] without warm-up:
+ *                LambdaLR(lambda s: min(1, (s + 1) / n)), `step` being the device counter the Adam calls take, from 1)
+ *   ctl[1] (out) gradient multiplier min(1, max_norm / (norm + 1e-6)) - torch.nn.utils.clip_grad_norm_'s, in fp32; NaN for a NaN
+ *                norm, 0 for an infinite one, 1 when clipping is off
+ *   ctl[2] (out) the total L2 norm of the `count` gradients before clipping (0 when clipping is off)
+ *   ctl[3] (in)  the caller's learning-rate scale
+ * The norm is summed in fp64 in a fixed order (no atomics): the same gradients give the same bits.  g / numel are host arrays;
+ * a null gradient pointer or a numel <= 0 is skipped; gradients are fp32, 4-byte aligned, of any length.  max_norm <= 0: no
+ * clipping - nothing is read, count may be 0 and ws null.  Otherwise ws holds avf_grad_control_workspace_bytes(count, numel)
+ * bytes (8 per 4096 elements of each tensor, skipped tensors included).  Nothing is allocated or synchronised (capturable).
+ * The gradients are NOT modified: the multiplier is applied by the Adam kernel (avf_adam_batch_control). */
+size_t avf_grad_control_workspace_bytes(int count, const int64_t* numel);
+int avf_grad_control(int count, const float* const* g, const int64_t* numel, float max_norm, int n_warmup_steps,
+                     const float* step, float* ctl, void* ws, void* stream);
+
+/* Attach a control block to the open Adam session (between avf_adam_batch_begin and _end, same thread): every table collected
+ * afterwards runs with lr * ctl[0] and with ctl[1] * g in place of each gradient g (before the weight decay is added), both read
+ * at run time.  A change of pointer launches the pending table first, like a change of hyper-parameters; null detaches.  The
+ * session ends with the pointer reset to null; without this call the Adam kernel's arithmetic is what it always was. */
+int avf_adam_batch_control(const float* ctl);
+
 /* x_out = layer(x_in); x_in, x_out [B*N, D] (may not alias): fp32, or bf16 when cfg.resid_bf16 is set. */
 int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
                   void* x_out, void* saved, void* workspace, void* stream);

@@ -6,6 +6,9 @@
 // Here ONE launch per layer reads p, g, m, v once and writes p, m, v AND the two bf16 images (the transpose through a
 // 64x64 LDS tile), with 16-byte loads and 8-byte bf16 stores.  The arithmetic follows torch's fused kernel
 // (exp_avg by lerp, exp_avg_sq by the two-term form) so the two optimizers agree to rounding.
+// A step under a control block (grad_control.hip; avf_adam_batch_control) reads two device floats more: lr is multiplied by
+// ctl[0] (warm-up, lr scale) and every gradient by ctl[1] (clipping) on its way into the update - the gradients in memory
+// are not written.  Without a block the kernel's arithmetic is unchanged.
 #include "common.hpp"
 
 namespace avf {
@@ -50,13 +53,17 @@ struct AdamBatch {
   int count;
   float lr, b1, b2, eps, wd;
   const float* step;  // device scalar: the step number of THIS update (>= 1)
+  const float* ctl;   // control block of grad_control.hip (nullable): ctl[0] multiplies lr, ctl[1] every gradient
 };
 
 struct AdamCoef {
   float lr_c, rsq_c2, b1, b2, eps, wd;
+  float gmul;   // gradient multiplier of a controlled step (clipping); the gradients in memory keep their values
+  bool scaled;  // a control block is attached
 };
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamCoef& k) {
+  if (k.scaled) g *= k.gmul;  // what clip_grad_norm_ writes back into .grad, here on the way through
   g = fmaf(k.wd, p, g);
   const float w = 1.0f - k.b1;  // lerp(m, g, w) as torch: a + w (b - a) for w < 0.5
   m = w < 0.5f ? fmaf(w, g - m, m) : g - (g - m) * (1.0f - w);
@@ -82,7 +89,9 @@ __global__ __launch_bounds__(256) void adam_layer_kernel(AdamBatch b) {
   const float step = b.step ? b.step[0] : 1.0f;
   AdamCoef k;
   k.b1 = b.b1; k.b2 = b.b2; k.eps = b.eps; k.wd = b.wd;
-  k.lr_c = b.lr / (1.0f - powf(b.b1, step));
+  k.scaled = b.ctl != nullptr;
+  k.gmul = k.scaled ? b.ctl[1] : 1.0f;
+  k.lr_c = (k.scaled ? b.lr * b.ctl[0] : b.lr) / (1.0f - powf(b.b1, step));
   k.rsq_c2 = 1.0f / sqrtf(1.0f - powf(b.b2, step));
   const bool upd = d.g != nullptr;
 
@@ -255,6 +264,7 @@ struct AdamPending {
   AdamBatch b;
   int n = 0, tiles = 0;
   hipStream_t stream = nullptr;
+  const float* ctl = nullptr;  // avf_adam_batch_control: carried by every table of the session collected after it
 };
 thread_local AdamPending g_adam_pending;
 
@@ -276,6 +286,7 @@ AdamPending& adam_target(AdamPending& local, float lr, float b1, float b2, float
     *rc = adam_flush(P);
   if (P.n == 0) memset(&P.b, 0, sizeof(P.b));
   P.b.lr = lr; P.b.b1 = b1; P.b.b2 = b2; P.b.eps = eps; P.b.wd = wd; P.b.step = step;
+  P.b.ctl = P.ctl;  // (null outside a session; avf_adam_batch_control flushed the pending table before changing it)
   P.stream = s;
   return P;
 }
@@ -288,6 +299,15 @@ extern "C" int avf_adam_batch_begin(void) {
   g_adam_pending.active = true;
   g_adam_pending.n = 0;
   g_adam_pending.tiles = 0;
+  g_adam_pending.ctl = nullptr;
+  return 0;
+}
+
+extern "C" int avf_adam_batch_control(const float* ctl) {
+  using namespace avf;
+  AVF_REQUIRE(g_adam_pending.active, "adam_batch_control: no batch is open on this thread");
+  if (g_adam_pending.ctl != ctl) AVF_TRY(adam_flush(g_adam_pending));  // (a pending table keeps the block it was collected under)
+  g_adam_pending.ctl = ctl;
   return 0;
 }
 
@@ -295,6 +315,7 @@ extern "C" int avf_adam_batch_end(void) {
   using namespace avf;
   AVF_REQUIRE(g_adam_pending.active, "adam_batch_end: no batch is open on this thread");
   g_adam_pending.active = false;
+  g_adam_pending.ctl = nullptr;
   return adam_flush(g_adam_pending);
 }
 
@@ -306,6 +327,7 @@ extern "C" int avf_adam_batch_abort(void) {
   g_adam_pending.active = false;
   g_adam_pending.n = 0;
   g_adam_pending.tiles = 0;
+  g_adam_pending.ctl = nullptr;
   return 0;
 }
 
