@@ -526,7 +526,7 @@ int avf_dropout_factors(uint32_t seed_lo, uint32_t seed_hi, int layer_index, int
  *           v_mfma_f32_16x16x32_bf16 with fp32 accumulation: <= 3 * 2^-16 = 4.6e-5 relative error per product in the worst case,
  *           4e-6 typical (measured relative Frobenius error of a GEMM), 3 MFMAs per product;
  *   mode 0 ("f32"): the f32-input MFMA v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain, 1/16 of the bf16 rate).
- * Both hold north_star's logits rtol 1e-3; shapes the bf16x3 kernels do not take (tiles below 64 rows, ragged K on the
+ * Both hold north_star's logits rtol 1e-3; shapes the bf16x3 kernels do not take (fewer than 96 rows or columns, ragged K on the
  * contiguous axis, token masks, bf16 storage) run the mode-0 kernels in either mode.  Returns the previous mode. */
 int avf_set_f32_arith(int mode);
 int avf_get_f32_arith(void);

@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/avformer_hip.h"
 
 namespace avf {
@@ -30,6 +32,20 @@ inline const char* tuning_env(const char* name) {
   }();
   return on ? getenv(name) : nullptr;
 }
+// an integer switch, `def` where it is unset or empty.  A site reads its switch once per process:
+//   static const int x = tuning_int("AVF_...", D);
+inline int tuning_int(const char* name, int def) {
+  const char* e = tuning_env(name);
+  return (e && *e) ? atoi(e) : def;
+}
+// The chip's workgroup slots as the GEMM heuristics count them: 256 CUs, each hosting two workgroups of the 56 - 72 KiB of LDS
+// the tiled kernels take (kWorkgroupSlots / 2: one workgroup per CU).  A grid below it leaves CUs without work, one above
+// it runs a second round.  A constant of the MI355X, not read from the device: deriving it would change dispatch on other parts.
+constexpr int kWorkgroupSlots = 512;
+// a run-time integer as a compile-time one: helpers switch over the values a template is instantiated for and hand a generic
+// lambda an int_c<V>{}
+template <int N>
+using int_c = std::integral_constant<int, N>;
 
 #define AVF_REQUIRE(cond, ...)          \
   do {                                  \

@@ -281,26 +281,19 @@ int launch_nt_glds(const NtParams& p, hipStream_t s, int* part_rows, TimingScope
   const int tiles_m = (p.M + BMT - 1) / BMT, tiles_n = (p.N + BNT - 1) / BNT;
   const int nwg = tiles_m * tiles_n;
   *part_rows = tiles_m * WM;
-  if (shape_log_on()) {
-    const double csz = sizeof(CT);
-    const double epi_b = (EPI == AVF_EPI_BIAS_RES || EPI == AVF_EPI_BIAS_GELU || EPI == AVF_EPI_DGELU) ? csz * p.M * p.N : 0.0;
+  if (shape_log_on())
     shape_log("gemm_bf16_nt,gemm_bf16_nt_glds_kernel<%d, %s, %d, %d, %d, %d, %d, %d>,%d,%d,%d,%d,%d,%.0f,%.0f", EPI,
               sizeof(CT) == 4 ? "float" : "bf16", WM, WN, MI, NI, NS, LEAN, nwg, p.M, p.N, p.K,
-              EPI, 2.0 * p.M * p.N * p.K,
-              2.0 * ((double)p.M * p.K + (double)p.N * p.K) + csz * p.M * p.N + epi_b);
-  }
+              EPI, 2.0 * p.M * p.N * p.K, nt_algorithmic_bytes(p.M, p.N, p.K, 2.0, sizeof(CT), EPI, false));
   // Weight warm-up (see the kernel): on for launches that leave workgroup slots of the chip empty (C2: 432 workgroups on 512
   // slots).  It turns stall time into MFMA-dense time, and the replayed step runs against the package power limit (amd-smi: PPT
   // violation active during replay, shader clock 2.15 - 2.37 GHz of 2.4): on the full launches of C3 the tiled shapes ran 6 -
   // 12 % shorter and the firmware lowered the clock of the WHOLE step by 6 % (2305 -> 2155 MHz) - C3 +3.0 %, C4 +0.5 %,
   // C5 +0.3 % in wall time, C2 -1.9 ... -3.8 % (profiles/r05_weight_warmup.txt).
-  static const int wpf_env = [] {
-    const char* e = tuning_env("AVF_NT_WPF");  // A/B aid: 0 = never, 2 = every launch
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int wpf_env = tuning_int("AVF_NT_WPF", 1);  // A/B aid: 0 = never, 2 = every launch
   // the 8-wave tiles only: on the small-M tile (four workgroups of 8 K-steps per CU, the reference's 17-token layers) the warm-up
   // loads queue in front of a short K loop's own - TFormer 133 -> 140 us per layer
-  constexpr int kSlots = (WM * WN == 8) ? 512 : 0;  // two 8-wave workgroups per CU, 256 CUs
+  constexpr int kSlots = (WM * WN == 8) ? kWorkgroupSlots : 0;
   const int wpf = (wpf_env && (wpf_env == 2 || nwg < kSlots) && p.ldb == p.K && p.K >= TK) ? 1 : 0;  // (K >= TK: the K loop's
                                                                                                        //  first wait retires the loads)
   launch_in_scope(ts, gemm_bf16_nt_glds_kernel<EPI, CT, WM, WN, MI, NI, NS, LEAN>, dim3(nwg), dim3(WM * WN * 64), SMEM, s, p,
@@ -308,43 +301,37 @@ int launch_nt_glds(const NtParams& p, hipStream_t s, int* part_rows, TimingScope
   return 0;
 }
 
+// LEAN code of the instantiation that serves (dropout site, column sums) on epilogue EPI; 0 = none, the general epilogue.
+// Column sums ride on the dGELU epilogue only, a dropout site on a fused epilogue only (the reference's real instantiations
+// train at p = 0.2, heads.py:277: the same lean path + the mask).
+constexpr bool nt_lean_exists(int epi, int lean) {
+  return lean == 0 || (((lean & 3) != 2 || epi == AVF_EPI_DGELU) && (!(lean & 4) || epi != AVF_EPI_NONE));
+}
 template <int EPI, typename CT>
 int launch_nt_glds_any(const NtParams& p, hipStream_t s, int* part_rows, TimingScope* ts) {
-  const int tile = pick_nt_tile_bf16(p.M, p.N, p.K);
-  // the two 8-wave tiles with the lean epilogue when nothing asks for the general one's options
-  if ((tile == 2 || tile == 5) && nt_lean_ok<EPI, CT>(p, 128, false, /*drop_ok=*/true)) {
-    constexpr bool csv = EPI == AVF_EPI_DGELU;  // column sums ride on the dGELU epilogue only
-    if constexpr (EPI != AVF_EPI_NONE) {
-      if (p.drop.thresh16) {  // the reference's real instantiations train at p = 0.2 (heads.py:277): same lean path + the mask
-        if (p.cs_partial == nullptr) {
-          if (tile == 5) return launch_nt_glds<EPI, CT, 2, 4, 3, 2, 2, 5>(p, s, part_rows, ts);
-          return launch_nt_glds<EPI, CT, 2, 4, 4, 2, 2, 5>(p, s, part_rows, ts);
-        }
-        if constexpr (csv) {
-          if (tile == 5) return launch_nt_glds<EPI, CT, 2, 4, 3, 2, 2, 6>(p, s, part_rows, ts);
-          return launch_nt_glds<EPI, CT, 2, 4, 4, 2, 2, 6>(p, s, part_rows, ts);
-        }
-      }
+  const int tile = pick_nt_tile_bf16(p.M, p.N, p.K), ti = nt_tile_index(tile);
+  // The instantiations are (tile, LEAN): every tile with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every epilogue),
+  // 5 (every fused epilogue) and 2, 6 (DGELU).  The lean epilogue runs when nothing asks for the general one's options (and
+  // never on an id that only runs as tile 2 because the table does not hold it).
+  int lean = (p.cs_partial ? 2 : 1) + (p.drop.thresh16 ? 4 : 0);
+  if (kNtTiles[ti].id != tile || !kNtTiles[ti].lean() || !nt_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(p, kNtTiles[ti].bn(), false, /*drop_ok=*/true))
+    lean = 0;
+  return with_nt_tile(ti, [&](auto ic) {
+    const auto launch = [&](auto lc) {
+      constexpr NtTile t = kNtTiles[decltype(ic)::value];
+      constexpr int LEAN = decltype(lc)::value;
+      if constexpr (nt_lean_exists(EPI, LEAN) && (LEAN == 0 || t.lean()))
+        return launch_nt_glds<EPI, CT, t.WM, t.WN, t.MI, t.NI, t.NS, LEAN>(p, s, part_rows, ts);
+      else AVF_REQUIRE(false, "gemm_bf16_nt: no lean instantiation %d of tile %d (internal error)", LEAN, t.id);
+    };
+    switch (lean) {
+      case 1: return launch(int_c<1>{});
+      case 2: return launch(int_c<2>{});
+      case 5: return launch(int_c<5>{});
+      case 6: return launch(int_c<6>{});
+      default: return launch(int_c<0>{});
     }
-    if (!p.drop.thresh16) {
-      if (p.cs_partial == nullptr) {
-        if (tile == 5) return launch_nt_glds<EPI, CT, 2, 4, 3, 2, 2, 1>(p, s, part_rows, ts);
-        return launch_nt_glds<EPI, CT, 2, 4, 4, 2, 2, 1>(p, s, part_rows, ts);
-      }
-      if constexpr (csv) {
-        if (tile == 5) return launch_nt_glds<EPI, CT, 2, 4, 3, 2, 2, 2>(p, s, part_rows, ts);
-        return launch_nt_glds<EPI, CT, 2, 4, 4, 2, 2, 2>(p, s, part_rows, ts);
-      }
-    }
-  }
-  switch (tile) {
-    case 6: return launch_nt_glds<EPI, CT, 1, 4, 2, 1, 3>(p, s, part_rows, ts);  // 36 KiB: four workgroups per CU
-    case 0: return launch_nt_glds<EPI, CT, 2, 2, 4, 4, 2>(p, s, part_rows, ts);
-    case 1: return launch_nt_glds<EPI, CT, 2, 2, 2, 4, 2>(p, s, part_rows, ts);
-    case 3: return launch_nt_glds<EPI, CT, 2, 2, 3, 4, 2>(p, s, part_rows, ts);
-    case 5: return launch_nt_glds<EPI, CT, 2, 4, 3, 2, 2>(p, s, part_rows, ts);
-    default: return launch_nt_glds<EPI, CT, 2, 4, 4, 2, 2>(p, s, part_rows, ts);
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -845,13 +832,25 @@ __global__ __launch_bounds__(256) void fold_group_kernel(TnGroup g, int nslab, F
   }
 }
 
-int tn_group_splits(int total_tiles, int64_t K, int slots = 512) {
-  static const int forced = [] {
-    const char* e = tuning_env("AVF_TN_SPLITS");  // tuning aid
-    return (e && *e) ? atoi(e) : 0;
-  }();
+// f(int_c<SS>{}) for fold_group_kernel<SS>: the split counts it is unrolled for (2 .. 8), else 0 = the run-time loop
+template <typename F>
+int with_fold_splits(int S, F&& f) {
+  switch (S) {
+    case 2: return f(int_c<2>{});
+    case 3: return f(int_c<3>{});
+    case 4: return f(int_c<4>{});
+    case 5: return f(int_c<5>{});
+    case 6: return f(int_c<6>{});
+    case 7: return f(int_c<7>{});
+    case 8: return f(int_c<8>{});
+    default: return f(int_c<0>{});
+  }
+}
+
+int tn_group_splits(int total_tiles, int64_t K, int slots = kWorkgroupSlots) {
+  static const int forced = tuning_int("AVF_TN_SPLITS", 0);  // tuning aid
   if (forced > 0) return forced;
-  // 512 workgroup slots (2 per CU at 72 KiB of LDS).  Pick the split count whose total workgroup count fills whole rounds of
+  // kWorkgroupSlots (2 per CU at 72 KiB of LDS).  Pick the split count whose total workgroup count fills whole rounds of
   // them best, charging 5 % per extra slab for the fold's traffic: 128 tiles (d = 512) -> 4 splits = exactly one round;
   // 288 tiles (d = 768) -> 3 splits = 1.7 rounds (84 % full) instead of 2 splits = 1.125 rounds (56 %): 3.90 -> 3.13 ms per
   // step at C4 (measured sweep: 3 splits 3.13, 4: 3.22, 5: 3.26, 6: 3.20, 8: 3.17 ms)
@@ -874,7 +873,7 @@ int tn_group_splits(int total_tiles, int64_t K, int slots = 512) {
 
 int tn_splits(int64_t M, int64_t N, int64_t K) {
   const int64_t tiles = ceil_div(M, TB) * ceil_div(N, TB);
-  int64_t s = ceil_div(512, tiles);
+  int64_t s = ceil_div(kWorkgroupSlots, tiles);
   const int64_t maxs = K / 256 > 0 ? K / 256 : 1;  // at least 256 reduction rows per split
   if (s > maxs) s = maxs;
   if (s > 32) s = 32;
@@ -901,85 +900,43 @@ int gemm_bf16_nt(const GemmArgs& a, hipStream_t s) {
   AVF_REQUIRE(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0 && ((uintptr_t)a.C & 15) == 0,
               "gemm_bf16_nt: operands must be 16-byte aligned");
   AVF_REQUIRE(a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31), "gemm_bf16_nt: shape too large");
-  NtParams p;
-  // algorithmic bytes: both operands once, C once, plus what the fused epilogue reads / writes beside C (fp32 residual;
-  // the saved pre-activation, in C's type)
-  const double csz = a.c_dtype == AVF_F32 ? 4.0 : 2.0;
-  const double epi_bytes = a.epilogue == AVF_EPI_BIAS_RES ? csz * a.M * a.N
-                           : (a.epilogue == AVF_EPI_BIAS_GELU || a.epilogue == AVF_EPI_DGELU) ? csz * a.M * a.N : 0.0;
-  TimingScope ts(KC_GEMM_BF16_NT, 2.0 * a.M * a.N * a.K, 2.0 * (a.M * a.K + a.N * a.K) + csz * a.M * a.N + epi_bytes, s,
-                 /*per_kernel=*/true);
-  p.A = (const bf16*)a.A; p.lda = a.lda; p.B = (const bf16*)a.B; p.ldb = a.ldb;
-  p.C = a.C; p.ldc = a.ldc; p.bias = a.bias; p.residual = a.residual; p.ldres = a.ldres;
-  p.aux = a.aux; p.ldaux = a.ldaux;
-  p.drop = a.drop;
-  p.mxq = nullptr; p.mxs = nullptr;
-  p.wide = nt_wide_stores();
+  TimingScope ts(KC_GEMM_BF16_NT, 2.0 * a.M * a.N * a.K,
+                 nt_algorithmic_bytes(a.M, a.N, a.K, 2.0, a.c_dtype == AVF_F32 ? 4.0 : 2.0, a.epilogue, false), s, /*per_kernel=*/true);
   AVF_REQUIRE(!a.drop.thresh16 || a.epilogue != AVF_EPI_NONE, "gemm_bf16_nt: dropout needs a fused epilogue");
-  p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
   dim3 grid((unsigned)ceil_div(a.N, TB), (unsigned)ceil_div(a.M, TB));
   AVF_REQUIRE(grid.y < 65536, "gemm_bf16_nt: M too large for grid");
-  const bool cf32 = a.c_dtype == AVF_F32;
-  AVF_REQUIRE(cf32 || a.c_dtype == AVF_BF16, "gemm_bf16_nt: bad c_dtype");
+  AVF_REQUIRE(a.c_dtype == AVF_F32 || a.c_dtype == AVF_BF16, "gemm_bf16_nt: bad c_dtype");
   AVF_REQUIRE(!a.mx_q || gemm_bf16_nt_ws_ok(a), "gemm_bf16_nt: an MX-FP8 image of C exists on the weight-stationary kernel only "
               "(ask gemm_bf16_nt_ws_ok first)");
   // K = 512 with a fragment-major weight image: the weight-stationary persistent kernel - where it is the faster one, or asked for
   if ((a.ws_force || a.mx_q) ? gemm_bf16_nt_ws_ok(a) : gemm_bf16_nt_ws_preferred(a)) {
     int ws_rows = 0;
     AVF_TRY(gemm_bf16_nt_ws(a, s, &ws_rows));
-    if (a.colsum) {
-      if (a.defer_fold) *a.defer_fold = FoldJob{(float*)a.workspace, ws_rows, (int)a.N, (int)a.N, a.colsum, nullptr, nullptr};
-      else AVF_TRY(fold_partials((float*)a.workspace, ws_rows, (int)a.N, a.colsum, s));
-    }
-    return 0;
+    return finish_colsum(a, (float*)a.workspace, ws_rows, s);
   }
+  const NtParams p = nt_params_from(a);  // (mxq is null here: an image of C went to the persistent kernel above)
   const bool dma = (a.K % TK == 0);
   int part_rows = (int)grid.y * 2;  // register-staged kernel: 2 wave rows per 128-row tile
-  p.cs_partial = nullptr;
   if (a.colsum) {
     AVF_REQUIRE(a.workspace, "gemm_bf16_nt: column-sum workspace missing");
-    p.cs_partial = (float*)a.workspace;
     // the partial rows the chosen tile will write must fit the workspace - checked BEFORE anything is enqueued
-    int planned = part_rows;
-    if (dma) {
-      const int t = pick_nt_tile_bf16(a.M, a.N, a.K);
-      const int bmt = (t == 0 || t == 2) ? 128 : (t == 1 ? 64 : (t == 6 ? 32 : 96));
-      planned = (int)ceil_div(a.M, bmt) * (t == 6 ? 1 : 2);  // two wave rows per block tile (the small-M tile: one)
-    }
+    const NtTile& t = kNtTiles[nt_tile_index(pick_nt_tile_bf16(a.M, a.N, a.K))];
+    const int planned = dma ? (int)ceil_div(a.M, t.bm()) * t.part_rows() : part_rows;
     AVF_REQUIRE((size_t)planned * a.N * sizeof(float) <= gemm_nt_colsum_ws(a.M, a.N),
                 "gemm_bf16_nt: column-sum partials exceed their workspace (internal error)");
   }
-#define LAUNCH(E)                                                         \
-  do {                                                                    \
-    if (dma) {                                                            \
-      if (cf32) AVF_TRY((launch_nt_glds_any<E, float>(p, s, &part_rows, &ts))); \
-      else AVF_TRY((launch_nt_glds_any<E, bf16>(p, s, &part_rows, &ts)));      \
-    } else if (cf32) launch_in_scope(&ts, gemm_bf16_nt_kernel<E, float>, grid, dim3(256), 0, s, p); \
-    else launch_in_scope(&ts, gemm_bf16_nt_kernel<E, bf16>, grid, dim3(256), 0, s, p); \
-  } while (0)
-  switch (a.epilogue) {
-    case AVF_EPI_NONE: LAUNCH(AVF_EPI_NONE); break;
-    case AVF_EPI_BIAS_RES:
-      AVF_REQUIRE(a.residual && a.ldres % 4 == 0, "gemm_bf16_nt: BIAS_RES needs a residual (in C's storage type)");
-      LAUNCH(AVF_EPI_BIAS_RES);
-      break;
-    case AVF_EPI_BIAS_GELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0, "gemm_bf16_nt: aux missing");
-      LAUNCH(AVF_EPI_BIAS_GELU);
-      break;
-    case AVF_EPI_DGELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0, "gemm_bf16_nt: aux missing");
-      LAUNCH(AVF_EPI_DGELU);
-      break;
-    default: AVF_REQUIRE(false, "gemm_bf16_nt: bad epilogue %d", a.epilogue);
-  }
-#undef LAUNCH
+  AVF_TRY(require_epilogue_operands(a, "gemm_bf16_nt", 4));
+  AVF_TRY(with_epilogue(a.epilogue, "gemm_bf16_nt", [&](auto epi) {
+    return with_c_type(a.c_dtype, "gemm_bf16_nt", [&](auto ct) {
+      constexpr int E = decltype(epi)::value;
+      using CT = decltype(ct);
+      if (dma) return launch_nt_glds_any<E, CT>(p, s, &part_rows, &ts);
+      launch_in_scope(&ts, gemm_bf16_nt_kernel<E, CT>, grid, dim3(256), 0, s, p);
+      return 0;
+    });
+  }));
   AVF_TRY(check_launch("gemm_bf16_nt_kernel"));
-  if (a.colsum) {
-    if (a.defer_fold) *a.defer_fold = FoldJob{p.cs_partial, part_rows, (int)a.N, (int)a.N, a.colsum, nullptr, nullptr};
-    else AVF_TRY(fold_partials(p.cs_partial, part_rows, (int)a.N, a.colsum, s));
-  }
-  return 0;
+  return finish_colsum(a, p.cs_partial, part_rows, s);
 }
 
 int gemm_bf16_tn(const GemmArgs& a, hipStream_t s) {
@@ -1003,7 +960,7 @@ int gemm_bf16_tn(const GemmArgs& a, hipStream_t s) {
   TimingScope ts(KC_GEMM_BF16_TN, 2.0 * a.M * a.N * a.K, 2.0 * (a.M * a.K + a.N * a.K) + 4.0 * a.M * a.N, s, /*per_kernel=*/true);
   p.A = (const bf16*)a.A; p.lda = a.lda; p.B = (const bf16*)a.B; p.ldb = a.ldb;
   p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
-  p.kchunk = (int)(ceil_div(ceil_div(a.K, S), TR) * TR);
+  p.kchunk = split_plan(a.K, S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
   if (S > 1) { p.C = (float*)a.workspace; p.ldc = a.N; p.slab = a.M * a.N; }
   else { p.C = (float*)a.C; p.ldc = a.ldc; p.slab = 0; }
   dim3 grid((unsigned)ceil_div(a.N, TB), (unsigned)ceil_div(a.M, TB), (unsigned)S);
@@ -1032,10 +989,7 @@ bool gemm_bf16_tn_group_ok(const TnGroupArgs& a) {
 
 // 256 x 128 tiles (one 8-wave workgroup per CU) when the group has enough work to fill the chip with them
 static bool tn_group_big(const TnGroupArgs& a) {
-  static const int forced = [] {
-    const char* e = tuning_env("AVF_TN_BIG");  // tuning aid: 0 = always the 128 x 128 kernel, 1 = always the 256 x 128 one
-    return (e && *e) ? atoi(e) : -1;
-  }();
+  static const int forced = tuning_int("AVF_TN_BIG", -1);  // tuning aid: 0 = always the 128 x 128 kernel, 1 = always the 256 x 128 one
   if (forced >= 0) return forced != 0;
   int64_t tiles = 0;
   for (int i = 0; i < a.count; ++i) tiles += ceil_div(a.M[i], TBM) * ceil_div(a.N[i], TB);
@@ -1053,7 +1007,8 @@ size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a) {
   size_t elems = 0;
   for (int i = 0; i < a.count; ++i) elems += (size_t)a.M[i] * a.N[i];
   // the larger of the two kernels' needs (the choice can be overridden by the environment at run time)
-  const int S0 = tn_group_splits(tn_group_tiles(a, false), a.K, 512), S1 = tn_group_splits(tn_group_tiles(a, true), a.K, 256);
+  const int S0 = tn_group_splits(tn_group_tiles(a, false), a.K, kWorkgroupSlots);
+  const int S1 = tn_group_splits(tn_group_tiles(a, true), a.K, kWorkgroupSlots / 2);
   const int S = S0 > S1 ? S0 : S1;
   return S > 1 ? (size_t)S * elems * sizeof(float) : 0;
 }
@@ -1078,8 +1033,8 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
     bytes += 2.0 * (a.M[i] + a.N[i]) * a.K + 4.0 * a.M[i] * a.N[i];
   }
   g.total_tiles = tiles;
-  g.S = tn_group_splits(tiles, a.K, big ? 256 : 512);
-  g.kchunk = (int)(ceil_div(ceil_div(a.K, g.S), TR) * TR);
+  g.S = tn_group_splits(tiles, a.K, big ? kWorkgroupSlots / 2 : kWorkgroupSlots);
+  g.kchunk = split_plan(a.K, g.S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
   if (g.S > 1) {
     AVF_REQUIRE(a.workspace, "gemm_bf16_tn_group: split-K workspace missing");
     float* w = (float*)a.workspace;
@@ -1092,10 +1047,7 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
   if (shape_log_on())
     shape_log("gemm_bf16_tn,gemm_bf16_tn_group%s,%d,%d,%d,%lld,%d,%.0f,%.0f", big ? "_big_kernel<3>" : "_kernel", tiles * g.S,
               a.count, g.S, (long long)a.K, -1, flops, bytes);
-  static const int tn_waves = [] {
-    const char* e = tuning_env("AVF_TN_WAVES");  // tuning aid
-    return (e && *e) ? atoi(e) : 4;  // 8 waves measured 5 % slower here (unlike the NT kernel)
-  }();
+  static const int tn_waves = tuning_int("AVF_TN_WAVES", 4);  // tuning aid; 8 waves measured 5 % slower here (unlike the NT kernel)
   if (big) {
     static PerDeviceOnce raised3;
     if (raised3.need()) {
@@ -1103,10 +1055,7 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
                                       3 * 48 * 1024) == hipSuccess, "gemm_bf16_tn_group: cannot raise dynamic LDS limit");
       raised3.mark();
     }
-    static const int xcd_order = [] {
-      const char* e = tuning_env("AVF_TN_XCD");  // tuning aid: 0 = tile-major block ids
-      return (e && *e) ? atoi(e) : 1;
-    }();
+    static const int xcd_order = tuning_int("AVF_TN_XCD", 1);  // tuning aid: 0 = tile-major block ids
     int nblocks = tiles * g.S;
     g.xcd_groups = 0;
     if (xcd_order && (g.S == 1 || g.S == 2 || g.S == 4 || g.S == 8)) {
@@ -1137,16 +1086,10 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
   const int nslab = g.S > 1 ? a.count : 0;
   if (nslab + fl.count > 0) {
     dim3 grid(256, nslab + fl.count);
-    switch (nslab ? g.S : 0) {
-      case 2: launch_in_scope(&ts, fold_group_kernel<2>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 3: launch_in_scope(&ts, fold_group_kernel<3>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 4: launch_in_scope(&ts, fold_group_kernel<4>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 5: launch_in_scope(&ts, fold_group_kernel<5>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 6: launch_in_scope(&ts, fold_group_kernel<6>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 7: launch_in_scope(&ts, fold_group_kernel<7>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      case 8: launch_in_scope(&ts, fold_group_kernel<8>, grid, dim3(256), 0, s, g, nslab, fl); break;
-      default: launch_in_scope(&ts, fold_group_kernel<0>, grid, dim3(256), 0, s, g, nslab, fl); break;
-    }
+    with_fold_splits(nslab ? g.S : 0, [&](auto ss) {
+      launch_in_scope(&ts, fold_group_kernel<decltype(ss)::value>, grid, dim3(256), 0, s, g, nslab, fl);
+      return 0;
+    });
     AVF_TRY(check_launch("fold_group_kernel"));
   }
   return 0;

@@ -6,6 +6,7 @@
 // fragment is ONE value per lane (A[i=l&15][k=l>>4], B[k=l>>4][j=l&15]) and needs no particular
 // LDS layout.  Replaces aten mm/addmm under models/heads.py:191-196, 212, 214-217.
 #include "common.hpp"
+#include "gemm_dispatch.hpp"
 
 namespace avf {
 
@@ -504,14 +505,14 @@ bool f32x3_ok(const F32GemmParams& p) {
   if (bkf && (p.K % 32 != 0 || p.b_sn % 4 != 0 || ((uintptr_t)p.B & 15))) return false;
   return true;
 }
-// split count over K for the 128 x 128 tiles: as many splits as keep tiles x splits within ONE round of the chip's 512 workgroup
-// slots (two per CU) - 48 tiles x 11 splits = 528 workgroups ran a second, almost empty round (119 us; 10 splits: 85) - with at
+// split count over K for the 128 x 128 tiles: as many splits as keep tiles x splits within ONE round of the chip's workgroup
+// slots (kWorkgroupSlots) - 48 tiles x 11 splits = 528 workgroups ran a second, almost empty round (119 us; 10 splits: 85) - with at
 // least 8 K-steps per split
 int f32x3_splits(int64_t M, int64_t N, int64_t K, int epilogue) {
   if (epilogue != AVF_EPI_NONE && epilogue != AVF_EPI_BIAS_RES) return 1;
   const int64_t tiles = ceil_div(M, SBM) * ceil_div(N, SBN);
-  if (tiles >= 256 || K < 512) return 1;
-  int64_t sp = 512 / tiles;
+  if (tiles >= kWorkgroupSlots / 2 || K < 512) return 1;
+  int64_t sp = kWorkgroupSlots / tiles;
   if (sp > K / 256) sp = K / 256;
   if (sp > 32) sp = 32;
   return sp < 2 ? 1 : (int)sp;
@@ -524,14 +525,30 @@ int launch_f32x3(const F32GemmParams& p, int epilogue, int S, int vec, hipStream
     gemm_f32x3_kernel<AKF, BKF, AVF_EPI_NONE, true><<<grid, 256, 0, s>>>(p, vec);
     return check_launch("gemm_f32x3_kernel(split)");
   }
-  switch (epilogue) {
-    case AVF_EPI_NONE: gemm_f32x3_kernel<AKF, BKF, AVF_EPI_NONE, false><<<grid, 256, 0, s>>>(p, vec); break;
-    case AVF_EPI_BIAS_RES: gemm_f32x3_kernel<AKF, BKF, AVF_EPI_BIAS_RES, false><<<grid, 256, 0, s>>>(p, vec); break;
-    case AVF_EPI_BIAS_GELU: gemm_f32x3_kernel<AKF, BKF, AVF_EPI_BIAS_GELU, false><<<grid, 256, 0, s>>>(p, vec); break;
-    case AVF_EPI_DGELU: gemm_f32x3_kernel<AKF, BKF, AVF_EPI_DGELU, false><<<grid, 256, 0, s>>>(p, vec); break;
-    default: AVF_REQUIRE(false, "gemm_f32x3: bad epilogue %d", epilogue);
-  }
+  AVF_TRY(with_epilogue(epilogue, "gemm_f32", [&](auto epi) {
+    gemm_f32x3_kernel<AKF, BKF, decltype(epi)::value, false><<<grid, 256, 0, s>>>(p, vec);
+    return 0;
+  }));
   return check_launch("gemm_f32x3_kernel");
+}
+
+// the second half of a split-K launch: C = the sum of the slabs (+ bias, + residual)
+int launch_f32_fold(const F32GemmParams& p, const GemmArgs& a, int S, hipStream_t s) {
+  gemm_f32_fold_kernel<<<(unsigned)ceil_div(a.M * a.N, 256), 256, 0, s>>>(p, S, a.epilogue == AVF_EPI_BIAS_RES ? 1 : 0);
+  return check_launch("gemm_f32_fold_kernel");
+}
+// K split `wanted` ways over the grid on (32 T) x (32 T) tiles of the f32-input MFMA kernel: raw partials into the caller's
+// workspace, one fold launch with the epilogue - deterministic (no atomics)
+template <int T>
+int launch_f32_split(F32GemmParams p, const GemmArgs& a, int wanted, const char* what, hipStream_t s) {
+  const SplitPlan plan = split_plan(a.K, wanted, 32);
+  p.slabs = (float*)a.workspace;
+  p.kchunk = plan.kchunk;
+  dim3 grid((unsigned)ceil_div(a.N, 32 * T), (unsigned)ceil_div(a.M, 32 * T), (unsigned)plan.S);
+  AVF_REQUIRE(grid.y < 65536, "gemm_f32: M too large for grid");
+  gemm_f32_kernel<AVF_EPI_NONE, T, true><<<grid, 256, 0, s>>>(p);
+  AVF_TRY(check_launch(what));
+  return launch_f32_fold(p, a, plan.S, s);
 }
 
 }  // namespace
@@ -572,13 +589,13 @@ int f32x3_group_setup(const TnGroupArgs& a, F32GroupParams* g, bool any_arith = 
   g->el0[a.count] = el;
   g->count = a.count;
   g->vec = 1;
-  int64_t sp = 512 / tiles;   // tiles x splits within one round of the 512 workgroup slots, at least 8 K-steps per split
+  int64_t sp = kWorkgroupSlots / tiles;  // tiles x splits within one round of the workgroup slots, at least 8 K-steps per split
   if (sp > a.K / 256) sp = a.K / 256;
   if (sp > 32) sp = 32;
   if (sp < 2) return 0;       // enough tiles to fill the chip unsplit: the per-problem launches serve that case
-  const int kchunk = (int)(ceil_div(ceil_div(a.K, sp), SBK) * SBK);
-  g->S = (int)ceil_div(a.K, kchunk);
-  for (int i = 0; i < a.count; ++i) g->p[i].kchunk = kchunk;
+  const SplitPlan plan = split_plan(a.K, sp, SBK);
+  g->S = plan.S;
+  for (int i = 0; i < a.count; ++i) g->p[i].kchunk = plan.kchunk;
   return 1;
 }
 }  // namespace
@@ -631,15 +648,15 @@ int gemm_f32(const GemmArgs& a, hipStream_t s) {
   p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
   p.drop = a.drop;
   p.kchunk = 0; p.slabs = nullptr;
+  AVF_TRY(require_epilogue_operands(a, "gemm_f32", 0));  // (no leading-dimension multiple: scalar accesses where they are odd)
   if (g_f32_arith == 1 && f32x3_ok(p)) {  // bf16x3 on the bf16 matrix pipe (round 6)
-    AVF_REQUIRE(a.epilogue != AVF_EPI_BIAS_RES || a.residual, "gemm_f32: residual missing");
-    AVF_REQUIRE((a.epilogue != AVF_EPI_BIAS_GELU && a.epilogue != AVF_EPI_DGELU) || a.aux, "gemm_f32: aux missing");
     const int S0 = a.workspace ? f32x3_splits(a.M, a.N, a.K, a.epilogue) : 1;
     int S = 1;
     if (S0 > 1) {
+      const SplitPlan plan = split_plan(a.K, S0, SBK);
       p.slabs = (float*)a.workspace;
-      p.kchunk = (int)(ceil_div(ceil_div(a.K, S0), SBK) * SBK);
-      S = (int)ceil_div(a.K, p.kchunk);
+      p.kchunk = plan.kchunk;
+      S = plan.S;
     }
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     int vec = (p.N % 4 == 0);
@@ -656,67 +673,24 @@ int gemm_f32(const GemmArgs& a, hipStream_t s) {
     else if (bkf) rc = launch_f32x3<false, true>(p, a.epilogue, S, vec, s);
     else rc = launch_f32x3<false, false>(p, a.epilogue, S, vec, s);
     AVF_TRY(rc);
-    if (S > 1) {
-      gemm_f32_fold_kernel<<<(unsigned)ceil_div(a.M * a.N, 256), 256, 0, s>>>(p, S, a.epilogue == AVF_EPI_BIAS_RES ? 1 : 0);
-      return check_launch("gemm_f32_fold_kernel");
-    }
-    return 0;
+    return S > 1 ? launch_f32_fold(p, a, S, s) : 0;
   }
-  // skinny GEMMs with a long reduction (the heads' projections on a few dozen clips): split K over the grid, raw partials
-  // into the caller's workspace, one fold launch with the epilogue - deterministic (no atomics)
+  // skinny GEMMs with a long reduction (the heads' projections on a few dozen clips): split K on the 32 x 32 tiles
   const int sp = a.workspace ? f32_splits(a.M, a.N, a.K, a.epilogue) : 1;
-  if (sp > 1) {
-    p.slabs = (float*)a.workspace;
-    p.kchunk = (int)(ceil_div(ceil_div(a.K, sp), 32) * 32);
-    const int S = (int)ceil_div(a.K, p.kchunk);
-    dim3 grid((unsigned)ceil_div(a.N, 32), (unsigned)ceil_div(a.M, 32), (unsigned)S);
-    gemm_f32_kernel<AVF_EPI_NONE, 1, true><<<grid, 256, 0, s>>>(p);
-    AVF_TRY(check_launch("gemm_f32_kernel(split)"));
-    AVF_REQUIRE(a.epilogue == AVF_EPI_NONE || a.residual, "gemm_f32: residual missing");
-    gemm_f32_fold_kernel<<<(unsigned)ceil_div(a.M * a.N, 256), 256, 0, s>>>(p, S, a.epilogue == AVF_EPI_BIAS_RES ? 1 : 0);
-    return check_launch("gemm_f32_fold_kernel");
-  }
+  if (sp > 1) return launch_f32_split<1>(p, a, sp, "gemm_f32_kernel(split)", s);
   // weight-gradient-shaped GEMMs: 64 x 64 tiles, split K (f32_split64)
   const int sp64 = a.workspace ? f32_split64(a.M, a.N, a.K, a.epilogue) : 1;
-  if (sp64 > 1) {
-    p.slabs = (float*)a.workspace;
-    p.kchunk = (int)(ceil_div(ceil_div(a.K, sp64), 32) * 32);
-    const int S = (int)ceil_div(a.K, p.kchunk);
-    dim3 grid((unsigned)ceil_div(a.N, 64), (unsigned)ceil_div(a.M, 64), (unsigned)S);
-    AVF_REQUIRE(grid.y < 65536, "gemm_f32: M too large for grid");
-    gemm_f32_kernel<AVF_EPI_NONE, 2, true><<<grid, 256, 0, s>>>(p);
-    AVF_TRY(check_launch("gemm_f32_kernel(split64)"));
-    AVF_REQUIRE(a.epilogue == AVF_EPI_NONE || a.residual, "gemm_f32: residual missing");
-    gemm_f32_fold_kernel<<<(unsigned)ceil_div(a.M * a.N, 256), 256, 0, s>>>(p, S, a.epilogue == AVF_EPI_BIAS_RES ? 1 : 0);
-    return check_launch("gemm_f32_fold_kernel");
-  }
+  if (sp64 > 1) return launch_f32_split<2>(p, a, sp64, "gemm_f32_kernel(split64)", s);
   // 32 x 32 tiles when 64 x 64 ones would not give every CU a workgroup (the small GEMMs of the heads)
   const bool small = ceil_div(a.N, 64) * ceil_div(a.M, 64) < 256;
   const int bt = small ? 32 : 64;
   dim3 grid((unsigned)ceil_div(a.N, bt), (unsigned)ceil_div(a.M, bt));
   AVF_REQUIRE(grid.y < 65536, "gemm_f32: M too large for grid");
-#define LAUNCH_F32(E)                                             \
-  do {                                                            \
-    if (small) gemm_f32_kernel<E, 1><<<grid, 256, 0, s>>>(p);     \
-    else gemm_f32_kernel<E, 2><<<grid, 256, 0, s>>>(p);           \
-  } while (0)
-  switch (a.epilogue) {
-    case AVF_EPI_NONE: LAUNCH_F32(AVF_EPI_NONE); break;
-    case AVF_EPI_BIAS_RES:
-      AVF_REQUIRE(a.residual, "gemm_f32: residual missing");
-      LAUNCH_F32(AVF_EPI_BIAS_RES);
-      break;
-    case AVF_EPI_BIAS_GELU:
-      AVF_REQUIRE(a.aux, "gemm_f32: aux missing");
-      LAUNCH_F32(AVF_EPI_BIAS_GELU);
-      break;
-    case AVF_EPI_DGELU:
-      AVF_REQUIRE(a.aux, "gemm_f32: aux missing");
-      LAUNCH_F32(AVF_EPI_DGELU);
-      break;
-    default: AVF_REQUIRE(false, "gemm_f32: bad epilogue %d", a.epilogue);
-  }
-#undef LAUNCH_F32
+  AVF_TRY(with_epilogue(a.epilogue, "gemm_f32", [&](auto epi) {
+    if (small) gemm_f32_kernel<decltype(epi)::value, 1><<<grid, 256, 0, s>>>(p);
+    else gemm_f32_kernel<decltype(epi)::value, 2><<<grid, 256, 0, s>>>(p);
+    return 0;
+  }));
   return check_launch("gemm_f32_kernel");
 }
 

@@ -185,46 +185,44 @@ int launch_mx8(const Mx8Params& q, hipStream_t s, int* part_rows, TimingScope* t
   *part_rows = tiles_m * WM;
   if (shape_log_on()) {
     const NtParams& p = q.nt;
-    const double csz = sizeof(CT);
-    const double epi_b = (EPI == AVF_EPI_BIAS_RES || EPI == AVF_EPI_BIAS_GELU || EPI == AVF_EPI_DGELU) ? csz * p.M * p.N : 0.0;
     shape_log("gemm_mx8_nt,gemm_mx8_nt_kernel<%d, %s, %d, %d, %d, %d, %d>,%d,%d,%d,%d,%d,%.0f,%.0f", EPI,
               sizeof(CT) == 4 ? "float" : "bf16", WM, WN, MI, NI, LEAN, nwg, p.M, p.N, p.K, EPI + (p.mxq ? 10 : 0), 2.0 * p.M * p.N * p.K,
-              ((double)p.M * p.K + (double)p.N * p.K) * (1.0 + 1.0 / 32) + csz * p.M * p.N + epi_b + (p.mxq ? (double)p.M * p.N * (1.0 + 1.0 / 32) : 0.0));
+              nt_algorithmic_bytes(p.M, p.N, p.K, kMx8Bytes, sizeof(CT), EPI, p.mxq != nullptr));
   }
   launch_in_scope(ts, gemm_mx8_nt_kernel<EPI, CT, WM, WN, MI, NI, LEAN>, dim3(nwg), dim3(WM * WN * 64), SMEM, s, q, tiles_n, nwg);
   return 0;
 }
 
+// column sums ride on the dGELU epilogue only, the MX-FP8 image of C on the two GELU epilogues
+constexpr bool mx8_lean_exists(int epi, int lean) {
+  return lean == 0 || ((!(lean & 2) || epi == AVF_EPI_DGELU) && (!(lean & 4) || epi == AVF_EPI_BIAS_GELU || epi == AVF_EPI_DGELU));
+}
 template <int EPI, typename CT>
 int launch_mx8_any(const Mx8Params& q, hipStream_t s, int* part_rows, TimingScope* ts) {
-  const int tile = pick_nt_tile(q.nt.M, q.nt.N, q.nt.K / 2);  // K/2: the same LDS bytes per row as a bf16 problem of that depth
-  // the two 8-wave tiles with the lean epilogue (options fixed at compile time) when nothing asks for the general one's
-  if ((tile == 2 || tile == 5) && nt_lean_ok<EPI, CT>(q.nt, 128, /*mx_ok=*/true)) {
-    constexpr bool can_mx = EPI == AVF_EPI_BIAS_GELU || EPI == AVF_EPI_DGELU;
-    constexpr bool can_cs = EPI == AVF_EPI_DGELU;
-    const bool mx = q.nt.mxq != nullptr, cs = q.nt.cs_partial != nullptr;
-#define AVF_MX8_LEAN(F)                                                                 \
-    do {                                                                                \
-      if (tile == 5) return launch_mx8<EPI, CT, 2, 4, 3, 2, F>(q, s, part_rows, ts);    \
-      return launch_mx8<EPI, CT, 2, 4, 4, 2, F>(q, s, part_rows, ts);                   \
-    } while (0)
-    if (!mx && !cs) AVF_MX8_LEAN(1);
-    if constexpr (can_mx) {
-      if (mx && !cs) AVF_MX8_LEAN(5);
+  // K/2: the same LDS bytes per row as a bf16 problem of that depth; the kernel has two LDS stages
+  const int tile = pick_nt_tile(q.nt.M, q.nt.N, q.nt.K / 2), ti = nt_tile_index(tile, /*max_stages=*/2);
+  // The instantiations are (tile, LEAN): tiles 0, 1, 2, 3, 5 with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every
+  // epilogue), 5 (BIAS_GELU, DGELU) and 3, 7 (DGELU).  The lean epilogue (options fixed at compile time) runs when nothing asks
+  // for the general one's (and never on an id that only runs as tile 2 because this kernel does not have it).
+  int lean = 1 + (q.nt.cs_partial ? 2 : 0) + (q.nt.mxq ? 4 : 0);
+  if (kNtTiles[ti].id != tile || !kNtTiles[ti].lean() || !mx8_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(q.nt, kNtTiles[ti].bn(), /*mx_ok=*/true))
+    lean = 0;
+  return with_nt_tile(ti, [&](auto ic) {
+    const auto launch = [&](auto lc) {
+      constexpr NtTile t = kNtTiles[decltype(ic)::value];
+      constexpr int LEAN = decltype(lc)::value;
+      if constexpr (t.NS == 2 && mx8_lean_exists(EPI, LEAN) && (LEAN == 0 || t.lean()))
+        return launch_mx8<EPI, CT, t.WM, t.WN, t.MI, t.NI, LEAN>(q, s, part_rows, ts);
+      else AVF_REQUIRE(false, "gemm_mx8_nt: no instantiation %d of tile %d (internal error)", LEAN, t.id);
+    };
+    switch (lean) {
+      case 1: return launch(int_c<1>{});
+      case 3: return launch(int_c<3>{});
+      case 5: return launch(int_c<5>{});
+      case 7: return launch(int_c<7>{});
+      default: return launch(int_c<0>{});
     }
-    if constexpr (can_cs) {
-      if (!mx && cs) AVF_MX8_LEAN(3);
-      if (mx && cs) AVF_MX8_LEAN(7);
-    }
-#undef AVF_MX8_LEAN
-  }
-  switch (tile) {
-    case 0: return launch_mx8<EPI, CT, 2, 2, 4, 4>(q, s, part_rows, ts);
-    case 1: return launch_mx8<EPI, CT, 2, 2, 2, 4>(q, s, part_rows, ts);
-    case 3: return launch_mx8<EPI, CT, 2, 2, 3, 4>(q, s, part_rows, ts);
-    case 5: return launch_mx8<EPI, CT, 2, 4, 3, 2>(q, s, part_rows, ts);
-    default: return launch_mx8<EPI, CT, 2, 4, 4, 2>(q, s, part_rows, ts);
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -337,65 +335,35 @@ int gemm_mx8_nt(const GemmArgs& a, const void* a_scales, const void* b_scales, h
   AVF_REQUIRE(a_scales && b_scales && ((uintptr_t)a_scales & 3) == 0 && ((uintptr_t)b_scales & 3) == 0,
               "gemm_mx8_nt: scale images missing or not 4-byte aligned");
   AVF_REQUIRE(a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31), "gemm_mx8_nt: shape too large");
+  TimingScope ts(KC_GEMM_MX8_NT, 2.0 * a.M * a.N * a.K,
+                 nt_algorithmic_bytes(a.M, a.N, a.K, kMx8Bytes, a.c_dtype == AVF_F32 ? 4.0 : 2.0, a.epilogue, mx_q != nullptr), s,
+                 /*per_kernel=*/true);
   Mx8Params q;
   NtParams& p = q.nt;
-  const double csz = a.c_dtype == AVF_F32 ? 4.0 : 2.0;
-  const double epi_bytes = a.epilogue == AVF_EPI_NONE ? 0.0 : csz * a.M * a.N;  // residual / saved pre-activation
-  TimingScope ts(KC_GEMM_MX8_NT, 2.0 * a.M * a.N * a.K,
-                 1.0 * (a.M * a.K + a.N * a.K) * (1.0 + 1.0 / 32) + csz * a.M * a.N + epi_bytes + (mx_q ? a.M * a.N * (1.0 + 1.0 / 32) : 0.0),
-                 s, /*per_kernel=*/true);
-  p.A = (const bf16*)a.A; p.lda = a.lda; p.B = (const bf16*)a.B; p.ldb = a.ldb;
-  p.C = a.C; p.ldc = a.ldc; p.bias = a.bias; p.residual = a.residual; p.ldres = a.ldres;
-  p.aux = a.aux; p.ldaux = a.ldaux;
-  p.drop = a.drop;
+  p = nt_params_from(a);
   p.mxq = (uint8_t*)mx_q; p.mxs = (uint8_t*)mx_s;
-  p.wide = nt_wide_stores();
   AVF_REQUIRE(!mx_q || (mx_s && (a.epilogue == AVF_EPI_BIAS_GELU || a.epilogue == AVF_EPI_DGELU) && a.N % 32 == 0 &&
                         ((uintptr_t)mx_q & 7) == 0),
               "gemm_mx8_nt: the MX-FP8 output image needs the BIAS_GELU / DGELU epilogue and N %% 32 == 0");
   AVF_REQUIRE(!a.drop.thresh16 || a.epilogue != AVF_EPI_NONE, "gemm_mx8_nt: dropout needs a fused epilogue");
-  p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
   q.As = (const uint8_t*)a_scales; q.Bs = (const uint8_t*)b_scales;
-  const bool cf32 = a.c_dtype == AVF_F32;
-  AVF_REQUIRE(cf32 || a.c_dtype == AVF_BF16, "gemm_mx8_nt: bad c_dtype");
+  AVF_REQUIRE(a.c_dtype == AVF_F32 || a.c_dtype == AVF_BF16, "gemm_mx8_nt: bad c_dtype");
   int part_rows = 0;
-  p.cs_partial = nullptr;
   if (a.colsum) {
     AVF_REQUIRE(a.workspace, "gemm_mx8_nt: column-sum workspace missing");
     AVF_REQUIRE((size_t)ceil_div(a.M, 32) * a.N * sizeof(float) <= gemm_nt_colsum_ws(a.M, a.N),
                 "gemm_mx8_nt: column-sum partials exceed their workspace (internal error)");
-    p.cs_partial = (float*)a.workspace;
   }
-#define LAUNCH(E)                                                     \
-  do {                                                                \
-    if (cf32) AVF_TRY((launch_mx8_any<E, float>(q, s, &part_rows, &ts)));   \
-    else AVF_TRY((launch_mx8_any<E, bf16>(q, s, &part_rows, &ts)));        \
-  } while (0)
-  switch (a.epilogue) {
-    case AVF_EPI_NONE: LAUNCH(AVF_EPI_NONE); break;
-    case AVF_EPI_BIAS_RES:
-      AVF_REQUIRE(a.residual && a.ldres % 4 == 0, "gemm_mx8_nt: BIAS_RES needs a residual (in C's storage type)");
-      LAUNCH(AVF_EPI_BIAS_RES);
-      break;
-    case AVF_EPI_BIAS_GELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0, "gemm_mx8_nt: aux missing");
-      LAUNCH(AVF_EPI_BIAS_GELU);
-      break;
-    case AVF_EPI_DGELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0, "gemm_mx8_nt: DGELU needs the saved pre-activation (in C's type)");
-      LAUNCH(AVF_EPI_DGELU);
-      break;
-    default: AVF_REQUIRE(false, "gemm_mx8_nt: bad epilogue %d", a.epilogue);
-  }
-#undef LAUNCH
+  AVF_TRY(require_epilogue_operands(a, "gemm_mx8_nt", 4));
+  AVF_TRY(with_epilogue(a.epilogue, "gemm_mx8_nt", [&](auto epi) {
+    return with_c_type(a.c_dtype, "gemm_mx8_nt", [&](auto ct) {
+      return launch_mx8_any<decltype(epi)::value, decltype(ct)>(q, s, &part_rows, &ts);
+    });
+  }));
   AVF_TRY(check_launch("gemm_mx8_nt_kernel"));
   AVF_REQUIRE(!a.colsum || (size_t)part_rows * a.N * sizeof(float) <= gemm_nt_colsum_ws(a.M, a.N),
               "gemm_mx8_nt: column-sum partials exceed their workspace (internal error)");
-  if (a.colsum) {
-    if (a.defer_fold) *a.defer_fold = FoldJob{p.cs_partial, part_rows, (int)a.N, (int)a.N, a.colsum, nullptr, nullptr};
-    else AVF_TRY(fold_partials(p.cs_partial, part_rows, (int)a.N, a.colsum, s));
-  }
-  return 0;
+  return finish_colsum(a, p.cs_partial, part_rows, s);
 }
 
 }  // namespace avf

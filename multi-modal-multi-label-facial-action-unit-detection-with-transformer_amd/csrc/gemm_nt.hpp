@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "gemm_dispatch.hpp"
 
 namespace avf {
 namespace {
@@ -587,11 +588,42 @@ __device__ __forceinline__ void lds_read_words(uint32_t* dst, uint32_t addr, std
 // (3- and 4-stage rings, 256x128 / 256x256 / 192x128 tiles, 64x64 tiles and a persistent tile loop were all measured slower
 //  on this path's shapes - M = 10k..16k, N = 512..1536, K = 512..1536 - and removed: the waves wait ~55 % of their
 //  cycles (SQ_WAIT_ANY) on LDS/barrier latency, which more resident waves hide better than deeper DMA rings)
+//   6:  32x 64, 4 waves of 32x16, 3 stages (36 KiB, 4/CU)   - the bf16 kernel's small-M tile (pick_nt_tile_bf16)
+// The table is the one place that knows a tile's shape: the launchers take their template arguments from it, the entry points
+// the partial rows a launch will write.
+struct NtTile {
+  int id, WM, WN, MI, NI, NS;  // WM x WN wavefronts of (16 MI) x (16 NI) outputs each, NS LDS stages
+  constexpr int bm() const { return 16 * MI * WM; }  // block rows
+  constexpr int bn() const { return 16 * NI * WN; }  // block columns
+  constexpr int part_rows() const { return WM; }     // column-sum partial rows per block tile: one per wave row
+  constexpr bool lean() const { return WM * WN == 8; }  // the 8-wave tiles have the lean-epilogue instantiations
+};
+constexpr NtTile kNtTiles[] = {{0, 2, 2, 4, 4, 2}, {1, 2, 2, 2, 4, 2}, {2, 2, 4, 4, 2, 2},
+                               {3, 2, 2, 3, 4, 2}, {5, 2, 4, 3, 2, 2}, {6, 1, 4, 2, 1, 3}};
+constexpr int kNtTileCount = sizeof(kNtTiles) / sizeof(kNtTiles[0]);
+// index of tile `id`; an id the table does not hold, or one with a deeper ring than the kernel has stages, runs as tile 2
+constexpr int nt_tile_index(int id, int max_stages = 8) {
+  int def = 0;
+  for (int i = 0; i < kNtTileCount; ++i) {
+    if (kNtTiles[i].id == id && kNtTiles[i].NS <= max_stages) return i;
+    if (kNtTiles[i].id == 2) def = i;
+  }
+  return def;
+}
+template <typename F>
+int with_nt_tile(int index, F&& f) {  // f(int_c<index>{}): kNtTiles[index] as a compile-time value
+  static_assert(kNtTileCount == 6, "one case per table entry");
+  switch (index) {
+    case 0: return f(int_c<0>{});
+    case 1: return f(int_c<1>{});
+    case 2: return f(int_c<2>{});
+    case 3: return f(int_c<3>{});
+    case 4: return f(int_c<4>{});
+    default: return f(int_c<5>{});
+  }
+}
 int nt_lean_on() {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_NT_LEAN");  // A/B aid: 0 = the general epilogue everywhere in the tiled kernels
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_NT_LEAN", 1);  // A/B aid: 0 = the general epilogue everywhere in the tiled kernels
   return on;
 }
 int nt_wide_stores();
@@ -616,23 +648,20 @@ bool nt_lean_ok(const NtParams& p, int bn, bool mx_ok = false, bool drop_ok = fa
   return true;
 }
 int nt_wide_stores() {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_NT_WIDE");  // tuning aid: 0 = the plain per-block stores
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_NT_WIDE", 1);  // tuning aid: 0 = the plain per-block stores
   return on;
 }
 
+int nt_tile_forced() {
+  static const int tile = tuning_int("AVF_NT_TILE", -1);  // tuning aid: force one configuration
+  return tile;
+}
 int pick_nt_tile(int64_t M, int64_t N, int64_t K) {
-  static const int override_tile = [] {
-    const char* e = tuning_env("AVF_NT_TILE");  // tuning aid: force one configuration
-    return (e && *e) ? atoi(e) : -1;
-  }();
-  if (override_tile >= 0) return override_tile;
+  if (nt_tile_forced() >= 0) return nt_tile_forced();
   const int64_t wg128 = ceil_div(M, 128) * ceil_div(N, 128);
-  if (wg128 >= 512) return 2;
+  if (wg128 >= kWorkgroupSlots) return 2;
   (void)K;
-  return ceil_div(M, 96) * ceil_div(N, 128) <= 512 ? 5 : 1;
+  return ceil_div(M, 96) * ceil_div(N, 128) <= kWorkgroupSlots ? 5 : 1;
 }
 
 // bf16 NT kernel only: problems with few token rows (the reference's 12- / 17-token stacks at batch 64: ~1 k rows) put a few
@@ -642,16 +671,39 @@ int pick_nt_tile(int64_t M, int64_t N, int64_t K) {
 // 1088-row layer (816 workgroups at N = 1536) then fit the chip's slots in one round, and co-resident workgroups hide a round trip as
 // well as ring depth does: TFormer (17 tokens, d = 512, B = 64) 144 -> 133 us per layer replayed (2 slots 146, 4 slots 134).
 int pick_nt_tile_bf16(int64_t M, int64_t N, int64_t K) {
-  static const int small_on = [] {
-    const char* e = tuning_env("AVF_NT_SMALL_M");  // A/B aid: 0 = the large tiles for every shape
-    return (e && *e) ? atoi(e) : 1;
-  }();
-  static const int forced = [] {
-    const char* e = tuning_env("AVF_NT_TILE");
-    return (e && *e) ? atoi(e) : -1;
-  }();
-  if (forced < 0 && small_on && M <= 2048 && ceil_div(M, 96) * ceil_div(N, 128) <= 160) return 6;
+  static const int small_on = tuning_int("AVF_NT_SMALL_M", 1);  // A/B aid: 0 = the large tiles for every shape
+  if (nt_tile_forced() < 0 && small_on && M <= 2048 && ceil_div(M, 96) * ceil_div(N, 128) <= 160) return 6;
   return pick_nt_tile(M, N, K);
+}
+
+// ---- host plumbing of the three NT entry points (gemm_bf16_nt, gemm_bf16_nt_ws, gemm_mx8_nt) ----
+// every field from the caller's arguments (B, ldb: the row-major weight; mxq / mxs: GemmArgs' image of C)
+NtParams nt_params_from(const GemmArgs& a) {
+  NtParams p;
+  p.A = (const bf16*)a.A; p.lda = a.lda; p.B = (const bf16*)a.B; p.ldb = a.ldb;
+  p.C = a.C; p.ldc = a.ldc; p.bias = a.bias; p.residual = a.residual; p.ldres = a.ldres;
+  p.aux = a.aux; p.ldaux = a.ldaux;
+  p.cs_partial = a.colsum ? (float*)a.workspace : nullptr;
+  p.drop = a.drop;
+  p.wide = nt_wide_stores();
+  p.mxq = (uint8_t*)a.mx_q; p.mxs = (uint8_t*)a.mx_s;
+  p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
+  return p;
+}
+// algorithmic bytes (TimingScope, the shape log): both operands once at operand_bytes per element (bf16: 2; MX-FP8: 1 + 1/32,
+// the scale bytes), C once, what the fused epilogue reads / writes beside C (the residual or the saved pre-activation, in C's
+// type) and the MX-FP8 image of C where one is written
+constexpr double kMx8Bytes = 1.0 + 1.0 / 32;
+double nt_algorithmic_bytes(double M, double N, double K, double operand_bytes, double c_bytes, int epi, bool mx_image) {
+  const bool beside = epi == AVF_EPI_BIAS_RES || epi == AVF_EPI_BIAS_GELU || epi == AVF_EPI_DGELU;
+  return operand_bytes * (M * K + N * K) + c_bytes * M * N + (beside ? c_bytes * M * N : 0.0) + (mx_image ? M * N * kMx8Bytes : 0.0);
+}
+// the tail of a GEMM with column sums: hand the fold of its partial rows back to the caller, or run it now
+int finish_colsum(const GemmArgs& a, const float* partials, int part_rows, hipStream_t s) {
+  if (!a.colsum) return 0;
+  if (!a.defer_fold) return fold_partials(partials, part_rows, (int)a.N, a.colsum, s);
+  *a.defer_fold = FoldJob{partials, part_rows, (int)a.N, (int)a.N, a.colsum, nullptr, nullptr};
+  return 0;
 }
 
 }  // namespace

@@ -308,16 +308,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
 }
 
 int ws_enabled() {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_NT_WS");  // 0: every NT GEMM on the tiled kernel (A/B aid)
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_NT_WS", 1);  // 0: every NT GEMM on the tiled kernel (A/B aid)
   return on;
 }
 int ws_grid() {
   static const int n = [] {
-    const char* e = tuning_env("AVF_NT_WS_GRID");  // tuning aid: persistent workgroups (a multiple of 8)
-    int v = (e && *e) ? atoi(e) : 0;
+    int v = tuning_int("AVF_NT_WS_GRID", 0);  // tuning aid: persistent workgroups (a multiple of 8)
     if (v <= 0) {
       int dev = 0, cus = 256;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
@@ -351,13 +347,10 @@ int launch_ws(const NtParams& p, const void* bp, hipStream_t s, int* part_rows, 
   // ... which must fit the caller's workspace (avf_gemm_nt_ws_workspace_bytes / gemm_nt_colsum_ws) - checked BEFORE the launch
   AVF_REQUIRE(!CS || (size_t)G * p.N * sizeof(float) <= gemm_nt_colsum_ws(p.M, p.N),
               "gemm_bf16_nt_ws: column-sum partials exceed their workspace (internal error)");
-  if (shape_log_on()) {
-    const double csz = sizeof(CT);
-    const double epi_b = (EPI == AVF_EPI_BIAS_RES || EPI == AVF_EPI_BIAS_GELU || EPI == AVF_EPI_DGELU) ? csz * p.M * p.N : 0.0;
+  if (shape_log_on())
     shape_log("gemm_bf16_nt,gemm_bf16_nt_ws_kernel<%d, %s, %d, %d, %s, %s, %s>,%d,%d,%d,%d,%d,%.0f,%.0f", EPI,
               sizeof(CT) == 4 ? "float" : "bf16", MI, NSLOT, CS ? "true" : "false", MXO ? "true" : "false", DROP ? "true" : "false", nwg, p.M, p.N, p.K, EPI, 2.0 * p.M * p.N * p.K,
-              2.0 * ((double)p.M * p.K + (double)p.N * p.K) + csz * p.M * p.N + epi_b);
-  }
+              nt_algorithmic_bytes(p.M, p.N, p.K, 2.0, sizeof(CT), EPI, false));
   launch_in_scope(ts, gemm_bf16_nt_ws_kernel<EPI, CT, MI, NSLOT, CS, MXO, DROP>, dim3(nwg), dim3(512), SMEM, s, p, (const uint4*)bp, P, G, T / G, T % G);
   return 0;
 }
@@ -432,10 +425,7 @@ bool gemm_bf16_nt_ws_ok(const GemmArgs& a) {
 bool gemm_bf16_nt_ws_preferred(const GemmArgs& a) {
   if (!gemm_bf16_nt_ws_ok(a)) return false;
   {
-    static const int mask = [] {
-      const char* e = tuning_env("AVF_NT_WS_EPI");  // tuning aid: bit e set = epilogue e (AVF_EPI_*) may take the persistent kernel
-      return (e && *e) ? atoi(e) : 15;
-    }();
+    static const int mask = tuning_int("AVF_NT_WS_EPI", 15);  // tuning aid: bit e set = epilogue e (AVF_EPI_*) may take the persistent kernel
     if (!((mask >> a.epilogue) & 1) && !a.mx_q) return false;
   }
   // bias + residual (the out-projection, N = dim): the persistent kernel pays its prologue (a CU's 256 KiB of weights out of
@@ -445,10 +435,7 @@ bool gemm_bf16_nt_ws_preferred(const GemmArgs& a) {
     const int64_t P = a.N / WS_BN, T = (a.M + 31) / 32;
     int64_t G = ws_grid() / P;
     G = G > T ? T : G;
-    static const int min_tiles = [] {
-      const char* e = tuning_env("AVF_NT_WS_RES_TILES");  // tuning aid
-      return (e && *e) ? atoi(e) : 6;
-    }();
+    static const int min_tiles = tuning_int("AVF_NT_WS_RES_TILES", 6);  // tuning aid
     if (T / G < min_tiles) return false;
   }
   // plain, N = dim (d_o in backward): the same prologue serves two column panels only - below three row tiles per workgroup the
@@ -459,10 +446,7 @@ bool gemm_bf16_nt_ws_preferred(const GemmArgs& a) {
     const int64_t P = a.N / WS_BN, T = (a.M + 31) / 32;
     int64_t G = ws_grid() / P;
     G = G > T ? T : G;
-    static const int min_tiles0 = [] {
-      const char* e = tuning_env("AVF_NT_WS_PLAIN_TILES");  // tuning aid
-      return (e && *e) ? atoi(e) : 3;
-    }();
+    static const int min_tiles0 = tuning_int("AVF_NT_WS_PLAIN_TILES", 3);  // tuning aid
     if (T < min_tiles0 * G) return false;
   }
   return true;
@@ -470,45 +454,22 @@ bool gemm_bf16_nt_ws_preferred(const GemmArgs& a) {
 
 int gemm_bf16_nt_ws(const GemmArgs& a, hipStream_t s, int* part_rows_out) {
   AVF_REQUIRE(gemm_bf16_nt_ws_ok(a), "gemm_bf16_nt_ws: unsupported shape / arguments");
-  NtParams p;
-  const double csz = a.c_dtype == AVF_F32 ? 4.0 : 2.0;
-  const double epi_bytes = (a.epilogue == AVF_EPI_BIAS_RES || a.epilogue == AVF_EPI_BIAS_GELU || a.epilogue == AVF_EPI_DGELU)
-                               ? csz * a.M * a.N : 0.0;
-  TimingScope ts(KC_GEMM_BF16_NT, 2.0 * a.M * a.N * a.K, 2.0 * (a.M * a.K + a.N * a.K) + csz * a.M * a.N + epi_bytes, s,
-                 /*per_kernel=*/true);
-  p.A = (const bf16*)a.A; p.lda = a.lda; p.B = nullptr; p.ldb = 0;
-  p.C = a.C; p.ldc = a.ldc; p.bias = a.bias; p.residual = a.residual; p.ldres = a.ldres;
-  p.aux = a.aux; p.ldaux = a.ldaux;
-  p.drop = a.drop;
-  p.mxq = (uint8_t*)a.mx_q; p.mxs = (uint8_t*)a.mx_s;
-  p.wide = nt_wide_stores();
-  p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
-  p.cs_partial = a.colsum ? (float*)a.workspace : nullptr;
+  TimingScope ts(KC_GEMM_BF16_NT, 2.0 * a.M * a.N * a.K,
+                 nt_algorithmic_bytes(a.M, a.N, a.K, 2.0, a.c_dtype == AVF_F32 ? 4.0 : 2.0, a.epilogue, false), s, /*per_kernel=*/true);
+  NtParams p = nt_params_from(a);
+  p.B = nullptr; p.ldb = 0;  // (the kernel reads the fragment-major image a.Bp)
   AVF_REQUIRE(!a.colsum || a.workspace, "gemm_bf16_nt_ws: column-sum workspace missing");
-  const bool cf32 = a.c_dtype == AVF_F32;
+  AVF_TRY(require_epilogue_operands(a, "gemm_bf16_nt_ws", 4));
   int part_rows = 0;
-#define LAUNCH_WS(E)                                                               \
-  do {                                                                             \
-    if (cf32) AVF_TRY((launch_ws_any<E, float>(p, a.Bp, s, &part_rows, &ts)));     \
-    else AVF_TRY((launch_ws_any<E, bf16>(p, a.Bp, s, &part_rows, &ts)));           \
-  } while (0)
-  switch (a.epilogue) {
-    case AVF_EPI_NONE: LAUNCH_WS(AVF_EPI_NONE); break;
-    case AVF_EPI_BIAS_RES:
-      AVF_REQUIRE(a.residual && a.ldres % 4 == 0, "gemm_bf16_nt_ws: BIAS_RES needs a residual (in C's storage type)");
-      LAUNCH_WS(AVF_EPI_BIAS_RES);
-      break;
-    case AVF_EPI_BIAS_GELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0, "gemm_bf16_nt_ws: aux missing");
-      LAUNCH_WS(AVF_EPI_BIAS_GELU);
-      break;
-    case AVF_EPI_DGELU:
-      AVF_REQUIRE(a.aux && a.ldaux % 4 == 0 && !cf32, "gemm_bf16_nt_ws: aux missing (or an fp32 C)");
-      AVF_TRY((launch_ws_any<AVF_EPI_DGELU, bf16>(p, a.Bp, s, &part_rows, &ts)));
-      break;
-    default: AVF_REQUIRE(false, "gemm_bf16_nt_ws: bad epilogue %d", a.epilogue);
-  }
-#undef LAUNCH_WS
+  AVF_TRY(with_epilogue(a.epilogue, "gemm_bf16_nt_ws", [&](auto epi) {
+    return with_c_type(a.c_dtype, "gemm_bf16_nt_ws", [&](auto ct) {
+      constexpr int E = decltype(epi)::value;
+      using CT = decltype(ct);
+      // the kernel has no <DGELU, float> form (gemm_bf16_nt_ws_ok sends a dGELU with an fp32 C to the tiled kernel)
+      if constexpr (E == AVF_EPI_DGELU && sizeof(CT) == 4) AVF_REQUIRE(false, "gemm_bf16_nt_ws: DGELU needs a bf16 C");
+      else return launch_ws_any<E, CT>(p, a.Bp, s, &part_rows, &ts);
+    });
+  }));
   *part_rows_out = part_rows;
   return check_launch("gemm_bf16_nt_ws_kernel");
 }

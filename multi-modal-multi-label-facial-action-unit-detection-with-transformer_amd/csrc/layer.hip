@@ -477,10 +477,7 @@ extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p
     AVF_TRY(linear_fwd_mx(d, w.hq, w.hs, d.D, l.wqkv_q, l.wqkv_s, 3 * d.I, sv.qkv, d.dt, AVF_EPI_NONE, nullptr, nullptr,
                           nullptr, s, kNoDrop));
     // out-proj: its A operand is produced per head; the head-resident attention kernel writes the image from its epilogue
-    static const int o_mx_on = [] {
-      const char* e = tuning_env("AVF_MX8_OUTPROJ");  // tuning / A-B aid: 0 = out-projection on bf16 operands
-      return (e && *e) ? atoi(e) : 1;
-    }();
+    static const int o_mx_on = tuning_int("AVF_MX8_OUTPROJ", 1);  // tuning / A-B aid: 0 = out-projection on bf16 operands
     const bool o_mx = o_mx_on && !d.keep && attn_fwd_emits_mx8(d.N, d.dh) && d.I % 128 == 0;
     if (d.keep)
       AVF_TRY(attn_fwd_vec(AVF_BF16, sv.qkv, sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.keep, attn_q_prescale_on()));
@@ -553,10 +550,7 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   const DropCfg dr_prev2 = d.layer > 0 ? make_drop(d.p, d.seed, d.layer - 1, 2, d.seed_dev) : kNoDrop;
   // short sequences (the reference's 12-token stacks): the six dependent launches around the attention backward run as two
   // fused kernels (layer_small.hip), which also make the bf16 image of the incoming gradient when the caller gave none
-  static const int small_bwd_on = [] {
-    const char* e = tuning_env("AVF_LAYER_SMALL_BWD");  // tuning / A-B aid
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int small_bwd_on = tuning_int("AVF_LAYER_SMALL_BWD", 1);  // tuning / A-B aid
   const bool small_bwd = lo && !d.rs16 && !d.mx && !d.keep && small_bwd_on && small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M);
   const void* gy = dx_out;
   const void* gy_stream = nullptr;  // gsd: the unmasked bf16 stream (LayerNorm-2 backward's residual gradient); gy is the masked image
@@ -620,10 +614,7 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
       if (d.p > 0.f || !dx_out) AVF_TRY(colsum(gy, AVF_BF16, d.R, d.D, d.D, g->b2, w.cs_ws, s));
       else AVF_TRY(colsum(dx_out, AVF_F32, d.R, d.D, d.D, g->b2, w.cs_ws, s));
     }
-    static const int small_att_on = [] {
-      const char* e = tuning_env("AVF_LAYER_SMALL_ATT");  // tuning / A-B aid: 0 = per-operator attention backward
-      return (e && *e) ? atoi(e) : 1;
-    }();
+    static const int small_att_on = tuning_int("AVF_LAYER_SMALL_ATT", 1);  // tuning / A-B aid: 0 = per-operator attention backward
     const bool fuse_att = small_att_on && d.H <= 16;
     if (!fuse_att)
       AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
@@ -700,10 +691,7 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
     a.bias = nullptr; a.residual = nullptr; a.ldres = 0; a.aux = (void*)sv.u; a.ldaux = d.M; a.workspace = w.cs_ws; a.colsum = g->b1;
     a.drop = dr1; a.defer_fold = grouped ? &folds.job[0] : nullptr;
     a.Bp = l.ws.w2t_p; a.mx_q = w.duq; a.mx_s = w.dus;
-    static const int dgelu_ws = [] {
-      const char* e = tuning_env("AVF_MX8_DGELU_WS");  // A/B aid: 0 = the dGELU GEMM of the fp8 mode on MX-FP8 operands
-      return (e && *e) ? atoi(e) : 1;
-    }();
+    static const int dgelu_ws = tuning_int("AVF_MX8_DGELU_WS", 1);  // A/B aid: 0 = the dGELU GEMM of the fp8 mode on MX-FP8 operands
     if (dgelu_ws && gemm_bf16_nt_ws_ok(a)) AVF_TRY(gemm(a, s));
     else
       AVF_TRY(linear_dx_mx(d, gyq, gys, d.D, l.w2t_q, l.w2t_s, d.M, w.du, AVF_EPI_DGELU, sv.u, s, g->b1, w.cs_ws, dr1,
@@ -742,8 +730,7 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   // built and bit-exact, but the image costs the attention kernel 18 us at B = 64, N = 512 (50 us before its stores were
   // made 16 bytes wide and dQ's 32-blocks wave-local) while the K = 1536 GEMM, already at 0.87 PFLOP/s on bf16 operands,
   // gains ~9 us: C5 5.06 ms per step with it against 4.93 without - OFF unless AVF_MX8_DQKV=1.
-  const char* dq_env = tuning_env("AVF_MX8_DQKV");  // (read per call: a test flips it inside one process)
-  const int dq_mx_on = (dq_env && *dq_env) ? atoi(dq_env) : 0;
+  const int dq_mx_on = tuning_int("AVF_MX8_DQKV", 0);  // (read per call: a test flips it inside one process)
   const bool dq_mx = d.mxb && dq_mx_on && !d.keep && (3 * d.I) % 128 == 0 && d.D % 128 == 0 &&
                      attn_bwd_emits_mx8(d.N, d.dh, attn_q_prescale_on());
   if (d.keep && lo && !d.mx && attn_masked_bf16_ok(d.N, d.dh, attn_q_prescale_on()))  // (as the forward chose)

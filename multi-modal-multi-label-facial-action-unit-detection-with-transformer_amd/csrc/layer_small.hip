@@ -712,10 +712,7 @@ int launch_small(const SmallArgs& a, int B, hipStream_t s) {
 
 // shapes the single-launch forward covers (AVF_LAYER_SMALL=0 turns it off: tuning / A-B aid)
 bool small_layer_ok(int dtype, int tokens, int dim, int heads, int dim_head, int mlp_dim) {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_LAYER_SMALL");
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_LAYER_SMALL", 1);
   const int inner = heads * dim_head;
   auto ok = [](int v) { return v == 128 || v == 256; };
   return on && dtype == AVF_BF16 && dim_head == 32 && tokens >= 1 && tokens <= 16 && ok(dim) && ok(inner) && ok(mlp_dim);

@@ -11,8 +11,6 @@ namespace avf {
 
 // The runtime -> compile-time step of the row width, written once for each column layout.  f is a generic lambda; the
 // instantiations of a kernel template are exactly the calls the dispatch below makes through these two.
-template <int N>
-using int_c = std::integral_constant<int, N>;
 template <typename F>
 static int ln_nv(int dim, F&& f) {  // NV: float4 chunks per lane (one per 256 columns), dim <= 1536
   switch ((dim + 255) / 256) {
@@ -148,10 +146,7 @@ __global__ __launch_bounds__(256) void ln_fwd_reg_kernel(const InT* __restrict__
 }
 
 static int ln_row8_on() {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_LN_ROW8");  // tuning / A-B aid: 0 = the one-row-per-wave kernels
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_LN_ROW8", 1);  // tuning / A-B aid: 0 = the one-row-per-wave kernels
   return on;
 }
 

@@ -258,6 +258,59 @@ def test_gemm_bf16_tn(ops, M, N, K):
     _close(c, ref.float(), atol=2e-5 * K, rtol=1e-5)
 
 
+_GEMM_FAMILIES = {  # name -> (M, N, K, prefix of every error of its entry point, fp32 arithmetic): the smallest shape that reaches it
+    "bf16_nt": (128, 128, 64, b"gemm_bf16_nt:", None),
+    "bf16_nt_ws": (2048, 256, 512, b"gemm_bf16_nt_ws:", None),
+    "mx8_nt": (128, 128, 128, b"gemm_mx8_nt:", None),
+    "f32_tile32": (32, 32, 32, b"gemm_f32:", "f32"),
+    "f32_bf16x3": (128, 128, 32, b"gemm_f32:", "bf16x3"),
+}
+
+
+@pytest.mark.parametrize("case", ["bias_res_without_residual", "bias_gelu_without_aux", "dgelu_without_aux", "epilogue_99"])
+@pytest.mark.parametrize("family", list(_GEMM_FAMILIES))
+def test_gemm_refuses_an_epilogue_without_its_operands(ops, family, case):
+    """every GEMM entry point refuses, before it launches anything, an epilogue whose operand is missing (BIAS_RES without a
+    residual, BIAS_GELU / DGELU without aux) and an epilogue number it does not know: the call fails, the error names the
+    entry point, C keeps its bytes.  Straight through the C ABI: ops.py would make the missing aux itself."""
+    import ctypes as C
+    from avformer_amd import _lib
+    lib = _lib.load()
+    M, N, K, prefix, arith = _GEMM_FAMILIES[family]
+    epi = {"bias_res_without_residual": ops.EPI_BIAS_RES, "bias_gelu_without_aux": ops.EPI_BIAS_GELU,
+           "dgelu_without_aux": ops.EPI_DGELU, "epilogue_99": 99}[case]
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g = torch.Generator().manual_seed(M + K)
+    cdt = torch.float32 if family.startswith("f32") else torch.bfloat16
+    a = torch.randn(M, K, generator=g).to(cdt).cuda()
+    w = torch.randn(N, K, generator=g).to(cdt).cuda()
+    c = torch.full((M, N), 7.25, dtype=cdt, device="cuda")
+    F32, BF16 = ops.avf_dtype(torch.float32), ops.avf_dtype(torch.bfloat16)
+    prev = _lib.set_f32_arithmetic(arith) if arith else None
+    try:
+        if family == "bf16_nt":
+            rc = lib.avf_gemm(BF16, 0, 1, M, N, K, ptr(a), K, ptr(w), K, ptr(c), N, BF16, epi, None, None, N, None, N, None, stream)
+        elif family == "bf16_nt_ws":
+            wp = ops.pack_ws(w)
+            rc = lib.avf_gemm_nt_ws(M, N, K, ptr(a), K, ptr(wp), ptr(c), N, BF16, epi, None, None, N, None, N, None, None, None,
+                                    None, stream)
+        elif family == "mx8_nt":
+            (aq, as_), (wq, ws_) = ops.quant_mx8(a), ops.quant_mx8(w)
+            rc = lib.avf_gemm_mx8_nt(M, N, K, ptr(aq), ptr(as_), ptr(wq), ptr(ws_), ptr(c), N, BF16, epi, None, None, N, None, N,
+                                     None, None, stream)
+        else:
+            rc = lib.avf_gemm(F32, 0, 1, M, N, K, ptr(a), K, ptr(w), K, ptr(c), N, F32, epi, None, None, N, None, N, None, stream)
+        err = lib.avf_last_error()
+    finally:
+        if prev is not None:
+            _lib.set_f32_arithmetic(prev)
+    assert rc != 0, f"{family}: {case} was accepted"
+    assert err.startswith(prefix), (family, case, err)
+    torch.cuda.synchronize()
+    assert bool((c == 7.25).all()), f"{family}: {case} was refused after C was written"
+
+
 # ---------------------------------------------------------------------------------------------- attention
 def _attn_ref(qkv, B, N, H, dh, d_o=None):
     """fp64 restatement of heads.py:222-237 on the packed projection."""

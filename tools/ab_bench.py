@@ -36,7 +36,8 @@ def run(env_extra, steps, extra):  # extra: bench.py arguments of this arm
         raise RuntimeError(f"bench.py printed no JSON line:\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
     d = json.loads(line[-1])
     ns = d.get("north_star_shape") or {}
-    return {"c2_ms": d["ms_per_step"], "c3_ms": ns.get("ms_per_step"), "value": d["value"]}  # (c2_ms = the main workload's)
+    return {"c2_ms": d["ms_per_step"], "c3_ms": ns.get("ms_per_step"), "value": d["value"],  # (c2_ms = the main workload's)
+            "c2_eager_ms": d.get("eager_ms_per_step"), "c3_eager_ms": ns.get("eager_ms_per_step")}  # host dispatch cost shows here
 
 
 def parse_env(items):
@@ -76,8 +77,10 @@ def main():
             print(f"round {i + 1} arm {arm}: {runs[arm][-1]}", flush=True)  # (a silent GPU-box call is taken for a hung one)
     med = lambda arm, k: statistics.median([r[k] for r in runs[arm] if r[k] is not None]) if any(r[k] is not None for r in runs[arm]) else None
     out = {"name": args.name, "note": args.note, "box": box_id(), "alternations": args.rounds, "steps": args.steps,
-           "arm_A": {"env": ea, "args": args.a_args, "runs": runs["A"], "median_c2_ms": med("A", "c2_ms"), "median_c3_ms": med("A", "c3_ms")},
-           "arm_B": {"env": eb, "args": args.b_args, "runs": runs["B"], "median_c2_ms": med("B", "c2_ms"), "median_c3_ms": med("B", "c3_ms")}}
+           "arm_A": {"env": ea, "args": args.a_args, "runs": runs["A"], "median_c2_ms": med("A", "c2_ms"), "median_c3_ms": med("A", "c3_ms"),
+                     "median_c2_eager_ms": med("A", "c2_eager_ms"), "median_c3_eager_ms": med("A", "c3_eager_ms")},
+           "arm_B": {"env": eb, "args": args.b_args, "runs": runs["B"], "median_c2_ms": med("B", "c2_ms"), "median_c3_ms": med("B", "c3_ms"),
+                     "median_c2_eager_ms": med("B", "c2_eager_ms"), "median_c3_eager_ms": med("B", "c3_eager_ms")}}
     a2, b2, a3, b3 = out["arm_A"]["median_c2_ms"], out["arm_B"]["median_c2_ms"], out["arm_A"]["median_c3_ms"], out["arm_B"]["median_c3_ms"]
     out["B_over_A_c2"] = round(b2 / a2, 4) if a2 and b2 else None
     out["B_over_A_c3"] = round(b3 / a3, 4) if a3 and b3 else None
