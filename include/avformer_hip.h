@@ -256,6 +256,17 @@ int avf_attn_bwd(int dtype, const void* qkv, const void* o, const void* d_o, con
 int avf_attn_fwd_qs(const void* qkv, void* o, float* lse2, int batch, int tokens, int heads, int dim_head, void* stream);
 int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, void* workspace,
                     int batch, int tokens, int heads, int dim_head, void* stream);
+/* ... with the token mask of heads.py:225-232 (keep: device bytes [batch, tokens], 1 = kept - ANY pattern, token 0 and
+ * whole clips included): the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8
+ * stack - one internal helper picks the kernels for the layer and for these calls.  avf_attn_masked_on_mfma(tokens,
+ * dim_head) = 1: the masked head-resident MFMA forward and the masked merged backward (dim_head 64, tokens <= 512);
+ * 0: the fp32-arithmetic kernels on bf16 storage with pre-scaled q.  lse2 of a dropped query: log2(tokens) on the MFMA
+ * kernels, unspecified (finite) otherwise.  workspace >= 2 * avf_attn_bwd_workspace_bytes(...). */
+int avf_attn_masked_on_mfma(int tokens, int dim_head);
+int avf_attn_fwd_masked_qs(const void* qkv, void* o, float* lse2, const void* keep, int batch, int tokens, int heads,
+                           int dim_head, void* stream);
+int avf_attn_bwd_masked_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, void* workspace,
+                           const void* keep, int batch, int tokens, int heads, int dim_head, void* stream);
 
 /* Token-sequence plumbing of the callers either side of the stack (fp32, dim % 4 == 0, 16-byte aligned pointers).
  *  avf_fuse_tokens:   out[b, t, :] = (t < t_video ? clip[b, t, :] : audio[b, t - t_video, :]) + pos[t, :]  (pos nullable)

@@ -95,6 +95,9 @@ SIGNATURES = {
     "avf_attn_bwd": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_fwd_qs": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_bwd_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
+    "avf_attn_masked_on_mfma": (_int, [_int, _int]),
+    "avf_attn_fwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
+    "avf_attn_bwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_fuse_tokens": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_token_mean_fwd": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "avf_token_mean_fwd_bf16": (_int, [_vp, _vp, _int, _int, _int, _vp]),

@@ -419,6 +419,23 @@ extern "C" int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, 
                        dim_head, (hipStream_t)stream, true, w + (size_t)batch * tokens * heads);
 }
 
+// ... with the token mask: the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8 stack
+// (attn_fwd_masked_bf16 / attn_bwd_masked_bf16 choose the kernels for both).  workspace: 2 * avf_attn_bwd_workspace_bytes.
+extern "C" int avf_attn_masked_on_mfma(int tokens, int dim_head) { return attn_masked_bf16_ok(tokens, dim_head, true) ? 1 : 0; }
+extern "C" int avf_attn_fwd_masked_qs(const void* qkv, void* o, float* lse2, const void* keep, int batch, int tokens, int heads,
+                                      int dim_head, void* stream) {
+  AVF_REQUIRE(qkv && o && lse2 && keep, "attn_fwd_masked_qs: null pointer");
+  return attn_fwd_masked_bf16(qkv, o, lse2, keep, batch, tokens, heads, dim_head, (hipStream_t)stream, true);
+}
+extern "C" int avf_attn_bwd_masked_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv,
+                                      void* workspace, const void* keep, int batch, int tokens, int heads, int dim_head,
+                                      void* stream) {
+  AVF_REQUIRE(qkv && o && d_o && lse2 && dqkv && workspace && keep, "attn_bwd_masked_qs: null pointer");
+  float* w = (float*)workspace;
+  return attn_bwd_masked_bf16(qkv, o, d_o, lse2, dqkv, w, w + (size_t)batch * tokens * heads, keep, batch, tokens, heads, dim_head,
+                              (hipStream_t)stream, true);
+}
+
 // After a FAILED stream capture (an operation that cannot be recorded was issued while capturing): end a capture that is still
 // open on `stream` (discarding its graph) and clear the runtime's sticky last-error, which would otherwise surface at the
 // caller's next, unrelated HIP call.  Returns the error code that was pending (0: none).

@@ -1503,6 +1503,14 @@ int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, in
   return check_launch("attn_fwd_bf16_kernel");
 }
 
+int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep, int B, int N, int H, int dh, hipStream_t s,
+                         bool q_prescaled) {
+  AVF_REQUIRE(keep, "attn_fwd_masked_bf16: no mask");
+  if (attn_masked_bf16_ok(N, dh, q_prescaled))
+    return attn_fwd_bf16((const bf16*)qkv, (bf16*)o, lse2, B, N, H, dh, s, true, nullptr, nullptr, keep);
+  return attn_fwd_vec(AVF_BF16, qkv, o, lse2, B, N, H, dh, s, keep, q_prescaled);
+}
+
 bool attn_bwd_emits_mx8(int N, int dh, bool q_prescaled) { return attn_bwd_merged_ok(N, dh, q_prescaled); }
 
 int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv, float* delta, int B,
@@ -1558,6 +1566,15 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
     AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32, 64 or 128)", dh);
   }
   return check_launch("attn_bwd_bf16 kernels");
+}
+
+int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta, float* nlse,
+                         const void* keep, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled) {
+  AVF_REQUIRE(keep, "attn_bwd_masked_bf16: no mask");
+  if (attn_masked_bf16_ok(N, dh, q_prescaled))  // (as the forward chose)
+    return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, delta, B, N, H, dh, s, true, nlse,
+                         keep);
+  return attn_bwd_vec(AVF_BF16, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, keep, q_prescaled);
 }
 
 }  // namespace avf

@@ -588,6 +588,13 @@ bool attn_q_prescale_on();
 int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, int dh, hipStream_t s,
                   bool q_prescaled = false, void* mx_q = nullptr, void* mx_s = nullptr, const void* keep = nullptr);
 bool attn_masked_bf16_ok(int N, int dh, bool q_prescaled);  // head-resident forward + merged backward: dh 64, N <= 512, pre-scaled q
+// the masked attention core of a bf16, non-fp8 stack - the ONE place that picks its kernels (avf_layer_fwd / avf_layer_bwd and
+// the per-operator entry points avf_attn_fwd_masked_qs / avf_attn_bwd_masked_qs call it): the MFMA kernels where
+// attn_masked_bf16_ok holds, else the fp32-arithmetic ones on bf16 storage.  nlse: the B*H*N floats behind delta.
+int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep, int B, int N, int H, int dh, hipStream_t s,
+                         bool q_prescaled);
+int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta, float* nlse,
+                         const void* keep, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled);
 bool attn_fwd_emits_mx8(int N, int dh);  // mx_q / mx_s: MX-FP8 image of o, written by the head-resident kernel only
 int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv, float* delta,
                   int B, int N, int H, int dh, hipStream_t s, bool q_prescaled = false, float* nlse = nullptr,

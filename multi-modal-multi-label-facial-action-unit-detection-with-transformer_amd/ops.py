@@ -441,9 +441,18 @@ def attn_bwd(qkv, o, d_o, lse2, batch: int, tokens: int, heads: int, dim_head: i
     return dqkv
 
 
-def attn_fwd_masked(qkv: torch.Tensor, keep: torch.Tensor, batch: int, tokens: int, heads: int, dim_head: int):
+def attn_masked_on_mfma(tokens: int, dim_head: int) -> bool:
+    """does the masked attention of a bf16 stack (attn_fwd_masked / attn_bwd_masked with q_prescaled=True, and the layer itself)
+    run the masked MFMA kernels at this shape (avf_attn_masked_on_mfma), not the fp32-arithmetic ones"""
+    return bool(_lib.load().avf_attn_masked_on_mfma(int(tokens), int(dim_head)))
+
+
+def attn_fwd_masked(qkv: torch.Tensor, keep: torch.Tensor, batch: int, tokens: int, heads: int, dim_head: int,
+                    q_prescaled: bool = False):
     """attn_fwd with the token mask of heads.py:225-232: keep [B, N] uint8 / bool, 1 = token kept (the reference's mask after
-    its leading-True pad).  fp32 arithmetic on fp32 or bf16 storage."""
+    its leading-True pad).  fp32 arithmetic on fp32 or bf16 storage.
+    q_prescaled (bf16 only): the q columns already carry log2(e)/sqrt(dim_head) and the call runs what a bf16 layer runs
+    (avf_attn_fwd_masked_qs): the masked MFMA kernels where attn_masked_on_mfma says, else the fp32-arithmetic ones."""
     _need_cuda(qkv, keep)
     qkv = qkv.contiguous()
     keep = keep.to(torch.uint8).contiguous()
@@ -451,20 +460,32 @@ def attn_fwd_masked(qkv: torch.Tensor, keep: torch.Tensor, batch: int, tokens: i
     assert qkv.shape == (batch * tokens, 3 * inner) and keep.shape == (batch, tokens)
     o = torch.empty((batch * tokens, inner), dtype=qkv.dtype, device=qkv.device)
     lse2 = torch.empty((batch, heads, tokens), dtype=torch.float32, device=qkv.device)
-    _lib.check(_lib.load().avf_attn_fwd_masked(avf_dtype(qkv.dtype), _ptr(qkv), _ptr(o), _ptr(lse2), _ptr(keep), batch, tokens,
-                                               heads, dim_head, _stream()), "attn_fwd_masked")
+    if q_prescaled:
+        assert qkv.dtype == torch.bfloat16
+        _lib.check(_lib.load().avf_attn_fwd_masked_qs(_ptr(qkv), _ptr(o), _ptr(lse2), _ptr(keep), batch, tokens, heads, dim_head,
+                                                      _stream()), "attn_fwd_masked_qs")
+    else:
+        _lib.check(_lib.load().avf_attn_fwd_masked(avf_dtype(qkv.dtype), _ptr(qkv), _ptr(o), _ptr(lse2), _ptr(keep), batch, tokens,
+                                                   heads, dim_head, _stream()), "attn_fwd_masked")
     return o, lse2
 
 
-def attn_bwd_masked(qkv, o, d_o, lse2, keep, batch: int, tokens: int, heads: int, dim_head: int) -> torch.Tensor:
+def attn_bwd_masked(qkv, o, d_o, lse2, keep, batch: int, tokens: int, heads: int, dim_head: int,
+                    q_prescaled: bool = False) -> torch.Tensor:
     _need_cuda(qkv, o, d_o, lse2, keep)
     lib = _lib.load()
     qkv, o, d_o = qkv.contiguous(), o.contiguous(), d_o.contiguous()
     keep = keep.to(torch.uint8).contiguous()
+    assert keep.shape == (batch, tokens)
     dqkv = torch.empty_like(qkv)
-    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head), qkv.device)
-    _lib.check(lib.avf_attn_bwd_masked(avf_dtype(qkv.dtype), _ptr(qkv), _ptr(o), _ptr(d_o), _ptr(lse2), _ptr(dqkv), _ptr(ws),
-                                       _ptr(keep), batch, tokens, heads, dim_head, _stream()), "attn_bwd_masked")
+    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head) * (2 if q_prescaled else 1), qkv.device)
+    if q_prescaled:
+        assert qkv.dtype == torch.bfloat16
+        _lib.check(lib.avf_attn_bwd_masked_qs(_ptr(qkv), _ptr(o), _ptr(d_o), _ptr(lse2), _ptr(dqkv), _ptr(ws), _ptr(keep), batch,
+                                              tokens, heads, dim_head, _stream()), "attn_bwd_masked_qs")
+    else:
+        _lib.check(lib.avf_attn_bwd_masked(avf_dtype(qkv.dtype), _ptr(qkv), _ptr(o), _ptr(d_o), _ptr(lse2), _ptr(dqkv), _ptr(ws),
+                                           _ptr(keep), batch, tokens, heads, dim_head, _stream()), "attn_bwd_masked")
     return dqkv
 
 

@@ -11,6 +11,7 @@ import torch
 import oracle
 from conftest import load_golden
 from gpu_util import check_abs, check_rel, max_abs, rel_fro
+from mask_attn_util import prescale_q as _prescale_q, regime_qk
 
 pytestmark = pytest.mark.gpu
 
@@ -344,18 +345,6 @@ def test_attention_f32(ops, f32_arith, B, N, H, dh):
     _close(dqkv, dqkv_ref.float(), atol=5e-5, rtol=1e-4)
 
 
-def _prescale_q(qkv, H, dh):
-    """bf16 projection with q' = bf16(q * log2(e)/sqrt(dh)) in the q columns, and the fp32 projection it stands for:
-    (q'/c | k | v) exactly, so that the reference sees the very numbers the kernels see"""
-    c = math.log2(math.e) / math.sqrt(dh)
-    I = H * dh
-    dev = qkv.float().clone()
-    dev[:, :I] = (dev[:, :I] * c).to(torch.bfloat16).float()
-    ref = dev.clone()
-    ref[:, :I] = ref[:, :I] / c
-    return dev.to(torch.bfloat16), ref
-
-
 @pytest.mark.parametrize("qs", [False, True], ids=["raw_q", "prescaled_q"])
 @pytest.mark.parametrize("B,N,H,dh", [(1, 64, 2, 32), (2, 49, 8, 32), (3, 17, 8, 64), (2, 130, 3, 64), (1, 324, 2, 64),
                                       (2, 12, 8, 32), (1, 512, 2, 64), (1, 200, 1, 32)])
@@ -419,21 +408,7 @@ def test_attention_bf16_rescale_paths(ops, mode, qs):
     v = torch.randn(N, dh, generator=g)
     u = torch.randn(dh, generator=g)
     u = u / u.norm()
-    if mode == "ramp":      # score(q_i, k_j) ~ 8 * 6 * j/64 / 8 ... grows ~6 nats per 64 keys
-        q = q * 0.2 + 8.0 * u
-        k = k * 0.2 + u[None, :] * (torch.arange(N).float()[:, None] / 64.0) * 6.0
-    elif mode == "small_steps":  # ~2.5 nats (3.6 in log2) per tile: below the threshold of 6
-        q = q * 0.2 + 8.0 * u
-        k = k * 0.2 + u[None, :] * (torch.arange(N).float()[:, None] / 64.0) * 2.5
-    elif mode == "descending":  # the first tile holds the row maxima; later tiles fall by ~6 nats per 64 keys
-        q = q * 0.2 + 8.0 * u
-        k = k * 0.2 - u[None, :] * (torch.arange(N).float()[:, None] / 64.0) * 6.0
-    elif mode == "very_negative":  # every score ~ -250 nats: the first tile must centre the maximum far below zero
-        q = q * 0.2 + 40.0 * u
-        k = k * 0.2 - 50.0 * u[None, :]
-    else:
-        q = q * 30.0
-        k = k * 30.0
+    q, k = regime_qk(mode, q, k, u)  # (shared with the masked form of this test, tests/test_gpu_mask_core.py)
     qkv = torch.cat([q, k, v], dim=1).to(torch.bfloat16)
     d_o = torch.randn(N, dh, generator=g).to(torch.bfloat16)
     ref_in = qkv.float()
