@@ -441,6 +441,28 @@ int avf_eval_update(const float* out, int64_t ld_out, const int64_t* y_ex, const
                     int64_t* pred_ex, float* pred_va, void* stream);
 int avf_eval_scores(const double* state, const avf_eval_cfg* cfg, double* scores, void* stream);
 
+/* ---- audio front-end: waveform -> normalised log-mel spectrogram (dataloader/aff2compdataset.py:47-68, 214-247:
+ * torchaudio MelSpectrogram + left zero-padding of short clips; dataloader/clip_transforms.py:59-108: AmplitudeToDB('power',
+ * top_db) per clip + Normalize) ---------------------------------------------------------------------------------------------
+ * avf_mel_power: audio fp32 [rows, samples] -> mel fp32 [rows, n_mels, out_frames], out_frames = max(frames, full_frames) with
+ * frames = 1 + samples / hop.  One memset of peak and ONE kernel launch: centred frames with reflect padding (samples > n_fft / 2),
+ * `window` (win_length values, centred in the n_fft-point frame, zero outside), one-sided power spectrum by an fp32 FFT
+ * (n_fft = 1024 only), then mel[m] = sum over bins k in [bin_lo[m], bin_hi[m]) of power[k] * fb[k, m] with fb fp32
+ * [n_fft / 2 + 1, n_mels] row-major.  bin_lo / bin_hi are DEVICE int32 [n_mels] (the kernel clamps them to 0..n_fft/2+1); bins
+ * outside them are taken as zero weights.  A clip with frames < full_frames is written at frame offset full_frames - frames
+ * behind zero frames.  peak: device uint32 [rows / rows_per_clip], the bit pattern of the largest mel power of each group of
+ * rows_per_clip consecutive rows (a clip and its channels).  The same input gives the same bits, call after call.
+ *
+ * avf_mel_db_norm: ONE launch, in place on mel [rows, n_mels, frames]:
+ *   db = 10 log10(max(x, 1e-10));  db = max(db, 10 log10(max(peak[clip], 1e-10)) - top_db);  x = (db - mean) / std
+ * evaluated in fp64 and rounded once to fp32.
+ * Neither entry point allocates or synchronises; both can be captured.  Every argument is checked before anything is enqueued. */
+int avf_mel_power(const float* audio, int64_t rows, int64_t samples, const float* window, int win_length, int n_fft, int hop,
+                  const float* fb, const int32_t* bin_lo, const int32_t* bin_hi, int n_mels, int full_frames, int rows_per_clip,
+                  float* mel, uint32_t* peak, void* stream);
+int avf_mel_db_norm(float* mel, const uint32_t* peak, int64_t rows, int n_mels, int64_t frames, int rows_per_clip, double top_db,
+                    double mean, double std, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

@@ -123,6 +123,8 @@ SIGNATURES = {
     "avf_sizeof_eval_cfg": (_sz, []),
     "avf_eval_update": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "avf_eval_scores": (_int, [_vp, _vp, _vp, _vp]),
+    "avf_mel_power": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
+    "avf_mel_db_norm": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_double, C.c_double, C.c_double, _vp]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

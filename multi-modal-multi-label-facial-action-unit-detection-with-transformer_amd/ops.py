@@ -726,6 +726,39 @@ def eval_scores(state: torch.Tensor, cfg: "_lib.EvalCfg", scores: Optional[torch
     return scores
 
 
+def mel_power(audio: torch.Tensor, window: torch.Tensor, fb: torch.Tensor, bin_lo: torch.Tensor, bin_hi: torch.Tensor, n_fft: int,
+              hop: int, full_frames: int = 0, rows_per_clip: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """avf_mel_power: audio fp32 [rows, samples] -> (mel power fp32 [rows, n_mels, max(1 + samples // hop, full_frames)], peak
+    uint32 bit patterns as int32 [rows // rows_per_clip]).  window [win_length], fb [n_fft // 2 + 1, n_mels] fp32; bin_lo / bin_hi
+    int32 [n_mels] on the device."""
+    _need_cuda(audio, window, fb, bin_lo, bin_hi)
+    assert audio.dim() == 2 and audio.dtype == torch.float32 and audio.is_contiguous()
+    assert window.dtype == torch.float32 and window.is_contiguous() and fb.dtype == torch.float32 and fb.is_contiguous()
+    assert bin_lo.dtype == torch.int32 and bin_hi.dtype == torch.int32 and bin_lo.is_contiguous() and bin_hi.is_contiguous()
+    rows, samples = audio.shape
+    n_mels = fb.shape[1]
+    assert fb.shape[0] == n_fft // 2 + 1 and bin_lo.numel() == n_mels and bin_hi.numel() == n_mels
+    out_frames = max(1 + samples // max(int(hop), 1), int(full_frames))
+    mel = torch.empty(rows, n_mels, out_frames, dtype=torch.float32, device=audio.device)
+    peak = torch.empty(max(rows // max(int(rows_per_clip), 1), 1), dtype=torch.int32, device=audio.device)
+    _lib.check(_lib.load().avf_mel_power(_ptr(audio), rows, samples, _ptr(window), window.numel(), int(n_fft), int(hop), _ptr(fb),
+                                         _ptr(bin_lo), _ptr(bin_hi), n_mels, int(full_frames), int(rows_per_clip), _ptr(mel),
+                                         _ptr(peak), _stream()), "mel_power")
+    return mel, peak
+
+
+def mel_db_norm(mel: torch.Tensor, peak: torch.Tensor, rows_per_clip: int, top_db: float, mean: float, std: float) -> torch.Tensor:
+    """avf_mel_db_norm, IN PLACE on mel [rows, n_mels, frames] with the peak buffer of mel_power: dB, per-clip top_db clamp,
+    (x - mean) / std.  Returns mel."""
+    _need_cuda(mel, peak)
+    assert mel.dim() == 3 and mel.dtype == torch.float32 and mel.is_contiguous() and peak.dtype == torch.int32
+    rows, n_mels, frames = mel.shape
+    assert rows % int(rows_per_clip) == 0 and peak.numel() >= rows // int(rows_per_clip)
+    _lib.check(_lib.load().avf_mel_db_norm(_ptr(mel), _ptr(peak), rows, n_mels, frames, int(rows_per_clip), float(top_db),
+                                           float(mean), float(std), _stream()), "mel_db_norm")
+    return mel
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
