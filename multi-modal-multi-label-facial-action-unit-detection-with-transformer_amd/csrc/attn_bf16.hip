@@ -19,7 +19,7 @@
 // 150 / 162 / 238 VGPRs (forward / dQ / dK-dV), no scratch, one 512-thread workgroup per CU (73.7 KB static LDS each).
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_dispatch.hpp"
 
 namespace avf {
 
@@ -1392,56 +1392,51 @@ store_row_pairs<DB>(outk, lg, [&](int d) { return dkt[d][kb] * kscale; });
 namespace {
 // head-resident kernels: dim_head 64, the head's two operands fit in LDS; AVF_ATTN_RESIDENT=0 forces the streaming ones
 bool use_resident(int N, int dh) {
-  static const int allow = [] {
-    const char* e = tuning_env("AVF_ATTN_RESIDENT");
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int allow = tuning_int("AVF_ATTN_RESIDENT", 1);
   return allow && dh == 64 && N <= RES_MAX_N;
 }
 
-// waves per workgroup: V = ceil(N/32) row groups spread over ceil(V/12) passes (multi-pass kernels: at most 8 waves)
-bool res_multi(int N) { return ceil_div(N, 32) > 12; }
-int res_waves(int N) {
+// The head-resident variant for N tokens.  V = ceil(N/32) row groups: up to 8 take the 8-wave kernel and 9 .. 12 the 12-wave
+// one, a wave per row group in a single pass; more are spread over ceil(V/8) passes of the 8-wave multi-pass kernel.
+// f(int_c<MAXW>{}, std::bool_constant<MULTI>{}, waves per workgroup)
+template <typename F>
+int with_res_variant(int N, F&& f) {
   const int V = (int)ceil_div(N, 32);
-  if (V <= 12) return V;
-  const int passes = (int)ceil_div(V, 8);
-  return (int)ceil_div(V, passes);
+  if (V > 12) return f(int_c<8>{}, std::true_type{}, (int)ceil_div(V, ceil_div(V, 8)));
+  if (V <= 8) return f(int_c<8>{}, std::false_type{}, V);
+  return f(int_c<12>{}, std::false_type{}, V);
+}
+// ... as check_launch and the error messages name it behind the kernel's name: "<8,multi,qs,mask>"
+template <int MAXW, bool MULTI, bool QS, bool MASKED = false>
+constexpr const char* res_tag() {
+  if constexpr (MAXW == 12) return MASKED ? "<12,qs,mask>" : QS ? "<12,qs>" : "<12>";
+  else if constexpr (MULTI) return MASKED ? "<8,multi,qs,mask>" : QS ? "<8,multi,qs>" : "<8,multi>";
+  else return MASKED ? "<8,qs,mask>" : QS ? "<8,qs>" : "<8>";
 }
 
-template <typename K, typename... Args>
-int res_launch(const TimingScope* ts, K kernel, const char* name, int blocks, int waves, size_t smem, hipStream_t s, Args... args) {
-  // raise the dynamic-LDS limit once per kernel (nine instantiations share this function template per signature)
-  // (the table is append-only under a lock: the forward thread and autograd's device thread may both get here)
-  static struct { const void* fn; PerDeviceOnce once; } raised[32];
-  static int nraised = 0;
-  static int lock = 0;
-  PerDeviceOnce* once = nullptr;
-  while (__atomic_exchange_n(&lock, 1, __ATOMIC_ACQUIRE)) {}
-  for (int i = 0; i < nraised; ++i)
-    if (raised[i].fn == (const void*)kernel) once = &raised[i].once;
-  if (!once && nraised < 32) {
-    raised[nraised].fn = (const void*)kernel;
-    once = &raised[nraised++].once;
+template <auto Kernel, typename... Args>
+int res_launch(const TimingScope* ts, const char* family, const char* tag, int blocks, int waves, size_t smem, hipStream_t s,
+               Args... args) {
+  static const struct Name {  // "attn_fwd_res<8,multi,qs>"
+    char str[48];
+    Name(const char* f, const char* t) { snprintf(str, sizeof str, "%s%s", f, t); }
+  } name(family, tag);
+  static PerDeviceOnce once;  // the dynamic-LDS limit, raised once per kernel and device
+  if (once.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    AVF_REQUIRE(e == hipSuccess, "%s: cannot raise dynamic LDS limit: %s", name.str, hipGetErrorString(e));
+    once.mark();
   }
-  __atomic_store_n(&lock, 0, __ATOMIC_RELEASE);
-  if (!once || once->need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    AVF_REQUIRE(e == hipSuccess, "%s: cannot raise dynamic LDS limit: %s", name, hipGetErrorString(e));
-    if (once) once->mark();
-  }
-  AVF_REQUIRE(smem <= 160 * 1024, "%s: %zu bytes of LDS", name, smem);
-  launch_in_scope(ts, kernel, dim3(blocks), dim3(waves * 64), (uint32_t)smem, s, args...);
-  return check_launch(name);
+  AVF_REQUIRE(smem <= 160 * 1024, "%s: %zu bytes of LDS", name.str, smem);
+  launch_in_scope(ts, Kernel, dim3(blocks), dim3(waves * 64), (uint32_t)smem, s, args...);
+  return check_launch(name.str);
 }
 }  // namespace
 
 // log2(e)/sqrt(dh): the factor the layer path folds into the query rows of its bf16 Wqkv image
 // (AVF_ATTN_QS=0, a tuning aid, turns the folding off: factor 1 and the kernels that scale the scores themselves)
 bool attn_q_prescale_on() {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_ATTN_QS");
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_ATTN_QS", 1);
   return on != 0;
 }
 float attn_q_prescale(int dh) { return attn_q_prescale_on() ? LOG2E / sqrtf((float)dh) : 1.0f; }
@@ -1450,10 +1445,7 @@ float attn_q_prescale(int dh) { return attn_q_prescale_on() ? LOG2E / sqrtf((flo
 bool attn_fwd_emits_mx8(int N, int dh) { return use_resident(N, dh); }
 
 bool attn_masked_bf16_ok(int N, int dh, bool q_prescaled) {
-  static const int on = [] {
-    const char* e = tuning_env("AVF_ATTN_MASK_MFMA");  // A/B aid: 0 = every masked call on the fp32-arithmetic kernels
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int on = tuning_int("AVF_ATTN_MASK_MFMA", 1);  // A/B aid: 0 = every masked call on the fp32-arithmetic kernels
   return on && q_prescaled && use_resident(N, dh) && N >= 1 && N <= 512;
 }
 
@@ -1471,36 +1463,25 @@ int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, in
     shape_log("attn_fwd,attn_fwd,%d,%d,%d,%d,%d,%.0f,%.0f", B * H, B, N, H * dh, -1, 4.0 * B * H * (double)N * N * dh,
               2.0 * 4.0 * B * N * H * dh);
   if (use_resident(N, dh)) {
-    const int W = res_waves(N);
-    const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2;
-#define AVF_FWD_RES(MW, MU, Q, NAME) res_launch(&ts, attn_fwd_res_kernel<MW, MU, Q>, NAME, B * H, W, smem, s, qkv, o, lse2, N, H, \
-                                                (uint8_t*)mx_q, (uint8_t*)mx_s, (const uint8_t*)nullptr)
-    if (keep) {
-      const size_t smem_k = smem + (size_t)((N + 63) & ~63);
-#define AVF_FWD_RES_M(MW, MU, NAME) res_launch(&ts, attn_fwd_res_kernel<MW, MU, true, true>, NAME, B * H, W, smem_k, s, qkv, o, lse2, N, \
-                                              H, (uint8_t*)nullptr, (uint8_t*)nullptr, (const uint8_t*)keep)
-      if (res_multi(N)) return AVF_FWD_RES_M(8, true, "attn_fwd_res<8,multi,qs,mask>");
-      if (W <= 8) return AVF_FWD_RES_M(8, false, "attn_fwd_res<8,qs,mask>");
-      return AVF_FWD_RES_M(12, false, "attn_fwd_res<12,qs,mask>");
-#undef AVF_FWD_RES_M
-    }
-    if (q_prescaled) {
-      if (res_multi(N)) return AVF_FWD_RES(8, true, true, "attn_fwd_res<8,multi,qs>");
-      if (W <= 8) return AVF_FWD_RES(8, false, true, "attn_fwd_res<8,qs>");
-      return AVF_FWD_RES(12, false, true, "attn_fwd_res<12,qs>");
-    }
-    if (res_multi(N)) return AVF_FWD_RES(8, true, false, "attn_fwd_res<8,multi>");
-    if (W <= 8) return AVF_FWD_RES(8, false, false, "attn_fwd_res<8>");
-    return AVF_FWD_RES(12, false, false, "attn_fwd_res<12>");
-#undef AVF_FWD_RES
+    const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2 + (keep ? (size_t)((N + 63) & ~63) : 0);
+    return with_res_variant(N, [&](auto mw, auto mu, int W) {
+      auto launch = [&](auto q, auto masked, uint8_t* mq, uint8_t* ms) {
+        constexpr int MW = decltype(mw)::value;
+        constexpr bool MU = decltype(mu)::value, Q = decltype(q)::value, MK = decltype(masked)::value;
+        return res_launch<attn_fwd_res_kernel<MW, MU, Q, MK>>(&ts, "attn_fwd_res", res_tag<MW, MU, Q, MK>(), B * H, W, smem, s, qkv, o,
+                                                              lse2, N, H, mq, ms, (const uint8_t*)keep);
+      };
+      if (keep) return launch(std::true_type{}, std::true_type{}, nullptr, nullptr);  // (pre-scaled q, no fp8 image: checked above)
+      return with_bool(q_prescaled, [&](auto q) { return launch(q, std::false_type{}, (uint8_t*)mx_q, (uint8_t*)mx_s); });
+    });
   }
   const unsigned grid = (unsigned)(ceil_div(N, 128) * B * H);
   const int qs = q_prescaled ? 1 : 0;
-  if (dh == 64) launch_in_scope(&ts, attn_fwd_bf16_kernel<64>, dim3(grid), dim3(256), 0, s, qkv, o, lse2, B, N, H, qs);
-  else if (dh == 32) launch_in_scope(&ts, attn_fwd_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, o, lse2, B, N, H, qs);
-  else if (dh == 128) launch_in_scope(&ts, attn_fwd_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, o, lse2, B, N, H, qs);
-  else AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32, 64 or 128)", dh);
-  return check_launch("attn_fwd_bf16_kernel");
+  return with_stream_dim_head(dh, [&](auto d, auto nw) {
+    constexpr int DH = decltype(d)::value, NW = decltype(nw)::value;
+    launch_in_scope(&ts, attn_fwd_bf16_kernel<DH, NW>, dim3(grid), dim3(64 * NW), 0, s, qkv, o, lse2, B, N, H, qs);
+    return check_launch("attn_fwd_bf16_kernel");
+  });
 }
 
 int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep, int B, int N, int H, int dh, hipStream_t s,
@@ -1530,42 +1511,28 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
   if (keep) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, keep);  // (the merged kernel at every N <= 512)
   if (attn_bwd_merged_ok(N, dh, q_prescaled)) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, nullptr, dq_q, dq_s);
   if (use_resident(N, dh)) {  // delta comes out of the dQ kernel
-    const int W = res_waves(N);
     const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2, smem_kv = smem + (size_t)((N + 63) & ~63) * 8;
     AVF_REQUIRE(!q_prescaled || nlse, "attn_bwd_bf16: scratch for the negated statistics missing");
-#define AVF_BWD_RES(MW, MU, Q, TAG)                                                                                      \
-  do {                                                                                                                   \
-    AVF_TRY(res_launch(&ts, attn_dq_res_kernel<MW, MU, Q>, "attn_dq_res" TAG, B * H, W, smem, s, qkv, o, d_o, lse2, delta, \
-                       nlse, dqkv, N, H));                                                                               \
-    return res_launch(&ts, attn_dkv_res_kernel<MW, MU, Q>, "attn_dkv_res" TAG, B * H, W, smem_kv, s, qkv, d_o,           \
-                      Q ? (const float*)nlse : lse2, (const float*)delta, dqkv, N, H);                                   \
-  } while (0)
-    if (q_prescaled) {
-      if (res_multi(N)) AVF_BWD_RES(8, true, true, "<8,multi,qs>");
-      if (W <= 8) AVF_BWD_RES(8, false, true, "<8,qs>");
-      AVF_BWD_RES(12, false, true, "<12,qs>");
-    }
-    if (res_multi(N)) AVF_BWD_RES(8, true, false, "<8,multi>");
-    if (W <= 8) AVF_BWD_RES(8, false, false, "<8>");
-    AVF_BWD_RES(12, false, false, "<12>");
-#undef AVF_BWD_RES
+    return with_res_variant(N, [&](auto mw, auto mu, int W) {
+      return with_bool(q_prescaled, [&](auto q) {
+        constexpr int MW = decltype(mw)::value;
+        constexpr bool MU = decltype(mu)::value, Q = decltype(q)::value;
+        AVF_TRY((res_launch<attn_dq_res_kernel<MW, MU, Q>>(&ts, "attn_dq_res", res_tag<MW, MU, Q>(), B * H, W, smem, s, qkv, o, d_o,
+                                                           lse2, delta, nlse, dqkv, N, H)));
+        return res_launch<attn_dkv_res_kernel<MW, MU, Q>>(&ts, "attn_dkv_res", res_tag<MW, MU, Q>(), B * H, W, smem_kv, s, qkv, d_o,
+                                                          Q ? (const float*)nlse : lse2, (const float*)delta, dqkv, N, H);
+      });
+    });
   }
   AVF_TRY(attn_delta(AVF_BF16, o, d_o, delta, B, N, H, dh, s));
   const unsigned grid = (unsigned)(ceil_div(N, 128) * B * H);
   const int qs = q_prescaled ? 1 : 0;
-  if (dh == 64) {
-    launch_in_scope(&ts, attn_dq_bf16_kernel<64>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-    launch_in_scope(&ts, attn_dkv_bf16_kernel<64>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-  } else if (dh == 32) {
-    launch_in_scope(&ts, attn_dq_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-    launch_in_scope(&ts, attn_dkv_bf16_kernel<32>, dim3(grid), dim3(256), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-  } else if (dh == 128) {
-    launch_in_scope(&ts, attn_dq_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-    launch_in_scope(&ts, attn_dkv_bf16_kernel<128, 8>, dim3(grid), dim3(512), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
-  } else {
-    AVF_REQUIRE(false, "attention (bf16): unsupported dim_head %d (32, 64 or 128)", dh);
-  }
-  return check_launch("attn_bwd_bf16 kernels");
+  return with_stream_dim_head(dh, [&](auto d, auto nw) {
+    constexpr int DH = decltype(d)::value, NW = decltype(nw)::value;
+    launch_in_scope(&ts, attn_dq_bf16_kernel<DH, NW>, dim3(grid), dim3(64 * NW), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
+    launch_in_scope(&ts, attn_dkv_bf16_kernel<DH, NW>, dim3(grid), dim3(64 * NW), 0, s, qkv, d_o, lse2, (const float*)delta, dqkv, B, N, H, qs);
+    return check_launch("attn_bwd_bf16 kernels");
+  });
 }
 
 int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta, float* nlse,

@@ -31,7 +31,7 @@
 // (P = 0) and delta = 0.
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_dispatch.hpp"
 
 namespace avf {
 
@@ -713,6 +713,22 @@ int m4_launch(const TimingScope* ts, const bf16* qkv, const bf16* o, const bf16*
   return check_launch("attn_bwd_m4_kernel");
 }
 
+// f(int_c<KB>{}) for the key blocks per wave the kernel is built for: 1 .. AVF_M4_MAXKB, a build-time bound
+template <typename F>
+int with_key_blocks(int KB, int N, F&& f) {
+  switch (KB) {
+    case 1: return f(int_c<1>{});
+    case 2: return f(int_c<2>{});
+#if AVF_M4_MAXKB >= 3
+    case 3: return f(int_c<3>{});
+#endif
+#if AVF_M4_MAXKB >= 4
+    case 4: return f(int_c<4>{});
+#endif
+    default: AVF_REQUIRE(false, "attn_bwd_merged: N=%d out of range", N);
+  }
+}
+
 }  // namespace
 
 // merged backward: dim_head 64, pre-scaled q, N <= 512 - the default at every such N since its epilogue stores went to 16 bytes
@@ -723,14 +739,8 @@ int m4_launch(const TimingScope* ts, const bf16* qkv, const bf16* o, const bf16*
 // too: C2 (N = 324) 2.107 / 2.113 ms per step against 2.141 / 2.129 with the two kernels (same box, alternating runs).
 // AVF_ATTN_MERGED=0 turns it off, AVF_ATTN_MERGED_MIN_N moves the threshold.
 bool attn_bwd_merged_ok(int N, int dh, bool q_prescaled) {
-  static const int allow = [] {
-    const char* e = tuning_env("AVF_ATTN_MERGED");
-    return (e && *e) ? atoi(e) : 1;
-  }();
-  static const int min_n = [] {
-    const char* e = tuning_env("AVF_ATTN_MERGED_MIN_N");
-    return (e && *e) ? atoi(e) : 1;
-  }();
+  static const int allow = tuning_int("AVF_ATTN_MERGED", 1);
+  static const int min_n = tuning_int("AVF_ATTN_MERGED_MIN_N", 1);
   return allow && q_prescaled && dh == 64 && N <= 512 && N >= min_n;
 }
 
@@ -742,40 +752,17 @@ int attn_bwd_merged(const TimingScope* ts, const bf16* qkv, const bf16* o, const
                   ((uintptr_t)dqkv & 15) == 0,
               "attn_bwd_merged: misaligned pointers");
   const int KB = (((N + 31) >> 5) + 3) >> 2;
-  if (keep) {  // token mask: the masked instantiation (which treats padded keys as dropped ones)
-    switch (KB) {
-      case 1: return m4_launch<1, true, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, (const uint8_t*)keep);
-      case 2: return m4_launch<2, true, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, (const uint8_t*)keep);
-#if AVF_M4_MAXKB >= 3
-      case 3: return m4_launch<3, true, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, (const uint8_t*)keep);
-#endif
-#if AVF_M4_MAXKB >= 4
-      case 4: return m4_launch<4, true, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, (const uint8_t*)keep);
-#endif
-    }
-    AVF_REQUIRE(false, "attn_bwd_merged: N=%d out of range", N);
-  }
   const bool ragged = N != 4 * KB * 32;
-#define AVF_M4(K)                                                                                                          \
-  do {                                                                                                                     \
-    if (dq_q)                                                                                                              \
-      return ragged ? m4_launch<K, true, false, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, nullptr, (uint8_t*)dq_q, (uint8_t*)dq_s) \
-                    : m4_launch<K, false, false, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, nullptr, (uint8_t*)dq_q, (uint8_t*)dq_s); \
-    return ragged ? m4_launch<K, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s)                                            \
-                  : m4_launch<K, false>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s);                                          \
-  } while (0)
-  switch (KB) {
-    case 1: AVF_M4(1);
-    case 2: AVF_M4(2);
-#if AVF_M4_MAXKB >= 3
-    case 3: AVF_M4(3);
-#endif
-#if AVF_M4_MAXKB >= 4
-    case 4: AVF_M4(4);
-#endif
-  }
-#undef AVF_M4
-  AVF_REQUIRE(false, "attn_bwd_merged: N=%d out of range", N);
+  return with_key_blocks(KB, N, [&](auto kb) {
+    constexpr int K = decltype(kb)::value;
+    // token mask: the masked instantiation (which treats padded keys as dropped ones)
+    if (keep) return m4_launch<K, true, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, (const uint8_t*)keep);
+    return with_bool(ragged, [&](auto rg) {
+      constexpr bool R = decltype(rg)::value;
+      if (dq_q) return m4_launch<K, R, false, true>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, nullptr, (uint8_t*)dq_q, (uint8_t*)dq_s);
+      return m4_launch<K, R>(ts, qkv, o, d_o, lse2, dqkv, B, N, H, s);
+    });
+  });
 }
 
 }  // namespace avf

@@ -12,7 +12,8 @@
 // One lane owns one query (forward, dQ) or one key (dK, dV); the opposite operand is staged in
 // LDS and read as wave-wide broadcasts.  Scores are kept in the log2 domain:
 //   s2 = (q . k) * dh^-0.5 * log2(e),  p = 2^(s2 - lse2),  lse2 = m2 + log2(sum 2^(s2 - m2)).
-#include "common.hpp"
+#include "attn_dispatch.hpp"
+#include "gemm_dispatch.hpp"  // with_c_type: fp32 / bf16 storage
 
 namespace avf {
 
@@ -313,15 +314,13 @@ int attn_delta(int dtype, const void* o, const void* d_o, float* delta, int B, i
   return check_launch("attn_delta_kernel");
 }
 
-#define AVF_DH_DISPATCH(dh, MACRO)                                                           \
-  switch (dh) {                                                                               \
-    case 8: MACRO(8); break;                                                                  \
-    case 16: MACRO(16); break;                                                                \
-    case 32: MACRO(32); break;                                                                \
-    case 64: MACRO(64); break;                                                                \
-    case 128: MACRO(128); break;                                                              \
-    default: AVF_REQUIRE(false, "attention (fp32): unsupported dim_head %d (8,16,32,64,128)", dh); \
-  }
+// the instantiations of the VALU kernels, dim_head x storage type x mask: f(int_c<DH>{}, T{}, std::bool_constant<MASKED>{})
+template <typename F>
+static int with_vec_variant(int dh, int dtype, bool masked, const char* who, F&& f) {
+  return with_vec_dim_head(dh, [&](auto d) {
+    return with_c_type(dtype, who, [&](auto t) { return with_bool(masked, [&](auto mk) { return f(d, t, mk); }); });
+  });
+}
 
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s) {
   return attn_fwd_vec(AVF_F32, qkv, o, lse2, B, N, H, dh, s, nullptr, false);
@@ -340,17 +339,13 @@ int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N,
     return attn_fwd_f32_mfma((const float*)qkv, (float*)o, lse2, B, N, H, dh, s, q_prescaled);
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
-#define LT(D, T, MK) attn_fwd_f32_kernel<D, T, MK><<<dim3((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H)), 64, 0, s>>>((const T*)qkv, (T*)o, lse2, B, N, H, kp, qs)
-#define L(D)                                                  \
-  if (dtype == AVF_F32) {                                     \
-    if (kp) LT(D, float, true); else LT(D, float, false);     \
-  } else {                                                    \
-    if (kp) LT(D, bf16, true); else LT(D, bf16, false);       \
-  }
-  AVF_DH_DISPATCH(dh, L)
-#undef L
-#undef LT
-  return check_launch("attn_fwd_f32_kernel");
+  return with_vec_variant(dh, dtype, kp != nullptr, "attn_fwd_f32", [&](auto d, auto t, auto masked) {
+    constexpr int D = decltype(d)::value;
+    using T = decltype(t);
+    const dim3 grid((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H));
+    attn_fwd_f32_kernel<D, T, decltype(masked)::value><<<grid, 64, 0, s>>>((const T*)qkv, (T*)o, lse2, B, N, H, kp, qs);
+    return check_launch("attn_fwd_f32_kernel");
+  });
 }
 
 int attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, float* dqkv, float* delta,
@@ -371,21 +366,16 @@ int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, con
     return attn_bwd_f32_mfma((const float*)qkv, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, dh, s, q_prescaled);
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
-#define LT(D, T, MK)                                                                                                       \
-  const dim3 grid((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H));                                                  \
-  attn_dq_f32_kernel<D, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs);     \
-  attn_dkv_f32_kernel<D, 0, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs); \
-  attn_dkv_f32_kernel<D, 1, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs)
-#define L(D)                                                        \
-  if (dtype == AVF_F32) {                                           \
-    if (kp) { LT(D, float, true); } else { LT(D, float, false); }   \
-  } else {                                                          \
-    if (kp) { LT(D, bf16, true); } else { LT(D, bf16, false); }     \
-  }
-  AVF_DH_DISPATCH(dh, L)
-#undef L
-#undef LT
-  return check_launch("attn_bwd_f32 kernels");
+  return with_vec_variant(dh, dtype, kp != nullptr, "attn_bwd_f32", [&](auto d, auto t, auto masked) {
+    constexpr int D = decltype(d)::value;
+    constexpr bool MK = decltype(masked)::value;
+    using T = decltype(t);
+    const dim3 grid((unsigned)ceil_div(N, vec_rows<D>()), (unsigned)(B * H));
+    attn_dq_f32_kernel<D, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs);
+    attn_dkv_f32_kernel<D, 0, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs);
+    attn_dkv_f32_kernel<D, 1, T, MK><<<grid, 64, 0, s>>>((const T*)qkv, (const T*)d_o, lse2, delta, (T*)dqkv, B, N, H, kp, qs);
+    return check_launch("attn_bwd_f32 kernels");
+  });
 }
 
 }  // namespace avf

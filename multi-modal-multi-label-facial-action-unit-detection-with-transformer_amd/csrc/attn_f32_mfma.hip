@@ -18,7 +18,7 @@
 // lane fetches its four k-steps of a chunk with ONE 16-byte LDS read; both operands use the same permutation.
 // LDS images: a row-fragment copy with row stride DH + 4 floats (16-byte reads of 16 consecutive rows: conflict-free) and, where a
 // tile is also read transposed, a second copy with row stride DH + 16 (4-byte reads of 4 rows x 16 columns: conflict-free).
-#include "common.hpp"
+#include "attn_dispatch.hpp"
 
 namespace avf {
 
@@ -325,27 +325,22 @@ bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qk
 int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled) {
   dim3 grid((unsigned)ceil_div(N, 64), (unsigned)(B * H));
   const int qs = q_prescaled ? 1 : 0;
-  if (dh == 64) attn_fwd_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
-  else if (dh == 128) attn_fwd_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
-  else attn_fwd_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
-  return check_launch("attn_fwd_f32m_kernel");
+  return with_mfma_dim_head(dh, "attn_fwd_f32_mfma", [&](auto d) {
+    attn_fwd_f32m_kernel<decltype(d)::value><<<grid, 256, 0, s>>>(qkv, o, lse2, N, H, qs);
+    return check_launch("attn_fwd_f32m_kernel");
+  });
 }
 
 int attn_bwd_f32_mfma(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, int B, int N, int H,
                       int dh, hipStream_t s, bool q_prescaled) {
   dim3 grid((unsigned)ceil_div(N, 64), (unsigned)(B * H));
   const int qs = q_prescaled ? 1 : 0;
-  if (dh == 64) {
-    attn_dq_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-    attn_dkv_f32m_kernel<64><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-  } else if (dh == 128) {
-    attn_dq_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-    attn_dkv_f32m_kernel<128><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-  } else {
-    attn_dq_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-    attn_dkv_f32m_kernel<32><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
-  }
-  return check_launch("attn_bwd_f32m kernels");
+  return with_mfma_dim_head(dh, "attn_bwd_f32_mfma", [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    attn_dq_f32m_kernel<D><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
+    attn_dkv_f32m_kernel<D><<<grid, 256, 0, s>>>(qkv, d_o, lse2, delta, dqkv, N, H, qs);
+    return check_launch("attn_bwd_f32m kernels");
+  });
 }
 
 }  // namespace avf

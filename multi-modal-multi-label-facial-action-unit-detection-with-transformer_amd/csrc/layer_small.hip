@@ -708,14 +708,28 @@ int launch_small(const SmallArgs& a, int B, hipStream_t s) {
   return check_launch("layer_fwd_small_kernel");
 }
 
+// The widths the three kernels are instantiated for, 128 and 256, in every combination of D, the inner width and the MLP width
+// (eight; backward B takes the four (D, inner) pairs).  f(int_c<v / 32>{}) for a width the caller found small_width() to hold for.
+constexpr bool small_width(int v) { return v == 128 || v == 256; }
+template <typename F>
+int with_small_width(int v, F&& f) {
+  return v == 128 ? f(int_c<4>{}) : f(int_c<8>{});
+}
+template <typename F>
+int with_small_widths(int D, int I, int M, F&& f) {  // f(int_c<D / 32>{}, int_c<I / 32>{}, int_c<M / 32>{})
+  return with_small_width(D, [&](auto d) {
+    return with_small_width(I, [&](auto i) { return with_small_width(M, [&](auto m) { return f(d, i, m); }); });
+  });
+}
+
 }  // namespace
 
 // shapes the single-launch forward covers (AVF_LAYER_SMALL=0 turns it off: tuning / A-B aid)
 bool small_layer_ok(int dtype, int tokens, int dim, int heads, int dim_head, int mlp_dim) {
   static const int on = tuning_int("AVF_LAYER_SMALL", 1);
   const int inner = heads * dim_head;
-  auto ok = [](int v) { return v == 128 || v == 256; };
-  return on && dtype == AVF_BF16 && dim_head == 32 && tokens >= 1 && tokens <= 16 && ok(dim) && ok(inner) && ok(mlp_dim);
+  return on && dtype == AVF_BF16 && dim_head == 32 && tokens >= 1 && tokens <= 16 && small_width(dim) && small_width(inner) &&
+         small_width(mlp_dim);
 }
 
 int layer_fwd_small(int B, int N, int D, int H, int M, float eps, float score_scale, const avf_layer_params* p,
@@ -733,12 +747,10 @@ int layer_fwd_small(int B, int N, int D, int H, int M, float eps, float score_sc
   a.dr0 = dr0; a.dr1 = dr1; a.dr2 = dr2;
   const int I = H * 32;
   AVF_REQUIRE(((uintptr_t)x_in & 15) == 0 && ((uintptr_t)x_out & 15) == 0, "layer_fwd_small: misaligned activations");
-#define AVF_SMALL(DD, II, MM) \
-  if (D == DD * 32 && I == II * 32 && M == MM * 32) return launch_small<DD, II, MM>(a, B, s)
-  AVF_SMALL(4, 4, 4); AVF_SMALL(4, 4, 8); AVF_SMALL(4, 8, 4); AVF_SMALL(4, 8, 8);
-  AVF_SMALL(8, 4, 4); AVF_SMALL(8, 4, 8); AVF_SMALL(8, 8, 4); AVF_SMALL(8, 8, 8);
-#undef AVF_SMALL
-  AVF_REQUIRE(false, "layer_fwd_small: unsupported shape D=%d I=%d M=%d", D, I, M);
+  AVF_REQUIRE(small_width(D) && small_width(I) && small_width(M), "layer_fwd_small: unsupported shape D=%d I=%d M=%d", D, I, M);
+  return with_small_widths(D, I, M, [&](auto d, auto i, auto m) {
+    return launch_small<decltype(d)::value, decltype(i)::value, decltype(m)::value>(a, B, s);
+  });
 }
 
 // bytes of the per-clip partial rows of the two backward kernels: pb1 [B][M], pln2 [B][3D], pln1 [B][3D]
@@ -753,15 +765,11 @@ int layer_bwd_small_a(int B, int N, int D, int I, int M, const SmallBwdAHost& h,
   a.pb1 = h.pb1; a.pln2 = h.pln2; a.N = N; a.gs16 = h.gs16; a.dr0 = h.dr0; a.dr1 = h.dr1; a.dr2 = h.dr2;
   AVF_REQUIRE(N >= 1 && N <= 16 && (a.dx_out || a.dx_out_lo) && (h.gs16 || a.dx_out) && (a.dx_out_lo || a.gy_store),
               "layer_bwd_small_a: bad arguments");
-#define AVF_SMALL_A(DD, II, MM)                                                    \
-  if (D == DD * 32 && I == II * 32 && M == MM * 32) {                              \
-    layer_bwd_small_a_kernel<DD, II, MM, 16><<<B, 1024, 0, s>>>(a);                \
-    return check_launch("layer_bwd_small_a_kernel");                               \
-  }
-  AVF_SMALL_A(4, 4, 4) AVF_SMALL_A(4, 4, 8) AVF_SMALL_A(4, 8, 4) AVF_SMALL_A(4, 8, 8)
-  AVF_SMALL_A(8, 4, 4) AVF_SMALL_A(8, 4, 8) AVF_SMALL_A(8, 8, 4) AVF_SMALL_A(8, 8, 8)
-#undef AVF_SMALL_A
-  AVF_REQUIRE(false, "layer_bwd_small_a: unsupported shape D=%d I=%d M=%d", D, I, M);
+  AVF_REQUIRE(small_width(D) && small_width(I) && small_width(M), "layer_bwd_small_a: unsupported shape D=%d I=%d M=%d", D, I, M);
+  return with_small_widths(D, I, M, [&](auto d, auto i, auto m) {
+    layer_bwd_small_a_kernel<decltype(d)::value, decltype(i)::value, decltype(m)::value, 16><<<B, 1024, 0, s>>>(a);
+    return check_launch("layer_bwd_small_a_kernel");
+  });
 }
 
 template <int D32, int I32, bool ATT>
@@ -792,12 +800,11 @@ int layer_bwd_small_b(int B, int N, int D, int I, const SmallBwdBHost& h, hipStr
               "layer_bwd_small_b: bad arguments");
   AVF_REQUIRE(!h.attention || (a.qkv && a.o && a.d_o && a.lse2 && h.H >= 1 && h.H <= 16 && h.H * 32 == I),
               "layer_bwd_small_b: the fused attention backward needs the saved projection / output / lse2 and dim_head 32");
-#define AVF_SMALL_B(DD, II)                                                                   \
-  if (D == DD * 32 && I == II * 32)                                                           \
-    return h.attention ? launch_small_b<DD, II, true>(a, B, s) : launch_small_b<DD, II, false>(a, B, s);
-  AVF_SMALL_B(4, 4) AVF_SMALL_B(4, 8) AVF_SMALL_B(8, 4) AVF_SMALL_B(8, 8)
-#undef AVF_SMALL_B
-  AVF_REQUIRE(false, "layer_bwd_small_b: unsupported shape D=%d I=%d", D, I);
+  AVF_REQUIRE(small_width(D) && small_width(I), "layer_bwd_small_b: unsupported shape D=%d I=%d", D, I);
+  return with_small_width(D, [&](auto d) { return with_small_width(I, [&](auto i) {
+    return h.attention ? launch_small_b<decltype(d)::value, decltype(i)::value, true>(a, B, s)
+                       : launch_small_b<decltype(d)::value, decltype(i)::value, false>(a, B, s);
+  }); });
 }
 
 }  // namespace avf

@@ -312,6 +312,60 @@ def test_gemm_refuses_an_epilogue_without_its_operands(ops, family, case):
     assert bool((c == 7.25).all()), f"{family}: {case} was refused after C was written"
 
 
+# case -> (entry point, storage, unsupported dim_head); the fp32 kernels are built for 8 .. 128 in powers of two, the bf16 ones for 32 / 64 / 128
+_ATTN_BAD_DIM_HEAD = {
+    "fwd_bf16_48": ("avf_attn_fwd", torch.bfloat16, 48), "bwd_bf16_48": ("avf_attn_bwd", torch.bfloat16, 48),
+    "fwd_qs_48": ("avf_attn_fwd_qs", torch.bfloat16, 48), "bwd_qs_48": ("avf_attn_bwd_qs", torch.bfloat16, 48),
+    "fwd_f32_24": ("avf_attn_fwd", torch.float32, 24), "bwd_f32_24": ("avf_attn_bwd", torch.float32, 24),
+    "fwd_f32_4": ("avf_attn_fwd", torch.float32, 4), "bwd_f32_4": ("avf_attn_bwd", torch.float32, 4),
+    "fwd_masked_f32_24": ("avf_attn_fwd_masked", torch.float32, 24), "fwd_masked_qs_48": ("avf_attn_fwd_masked_qs", torch.bfloat16, 48),
+}
+
+
+@pytest.mark.parametrize("case", list(_ATTN_BAD_DIM_HEAD))
+def test_attention_refuses_an_unsupported_dim_head(ops, f32_arith, case):
+    """every attention entry point refuses a dim_head none of its kernels is built for: the call fails, the error names
+    dim_head, the outputs (o and lse2 forward, dqkv backward) keep their bytes, and the same entry point then runs dim_head 64 -
+    no sticky HIP error is left behind.  Straight through the C ABI, B = 1, 8 tokens, 1 head."""
+    import ctypes as C
+    from avformer_amd import _lib
+    lib = _lib.load()
+    entry, dt, bad_dh = _ATTN_BAD_DIM_HEAD[case]
+    B, N, H = 1, 8, 1
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    keep = torch.ones(B, N, dtype=torch.uint8, device="cuda")
+
+    def call(dh):
+        g = torch.Generator().manual_seed(dh)
+        qkv = torch.randn(B * N, 3 * H * dh, generator=g).to(dt).cuda()
+        d_o = torch.randn(B * N, H * dh, generator=g).to(dt).cuda()
+        o = torch.full((B * N, H * dh), 7.25, dtype=dt, device="cuda")
+        lse2 = torch.full((B * H * N,), 7.25, dtype=torch.float32, device="cuda")
+        dqkv = torch.full((B * N, 3 * H * dh), 7.25, dtype=dt, device="cuda")
+        ws = torch.zeros(2 * B * H * N, dtype=torch.float32, device="cuda")
+        shape = (B, N, H, dh, stream)
+        typed = () if entry.endswith("_qs") else (ops.avf_dtype(dt),)
+        if "_fwd" in entry:
+            mask = (ptr(keep),) if "masked" in entry else ()
+            rc = getattr(lib, entry)(*typed, ptr(qkv), ptr(o), ptr(lse2), *mask, *shape)
+            outs = (o, lse2)
+        else:
+            rc = getattr(lib, entry)(*typed, ptr(qkv), ptr(o), ptr(d_o), ptr(lse2), ptr(dqkv), ptr(ws), *shape)
+            outs = (dqkv,)
+        err = lib.avf_last_error().decode("utf-8", "replace")
+        torch.cuda.synchronize()
+        return rc, err, outs
+
+    rc, err, outs = call(bad_dh)
+    assert rc != 0, f"{case}: dim_head {bad_dh} was accepted"
+    assert "dim_head" in err, (case, err)
+    for t in outs:
+        assert bool((t == 7.25).all()), f"{case}: refused after an output was written"
+    rc, err, _ = call(64)
+    assert rc == 0, (case, err)
+
+
 # ---------------------------------------------------------------------------------------------- attention
 def _attn_ref(qkv, B, N, H, dh, d_o=None):
     """fp64 restatement of heads.py:222-237 on the packed projection."""
