@@ -463,6 +463,28 @@ int avf_mel_power(const float* audio, int64_t rows, int64_t samples, const float
 int avf_mel_db_norm(float* mel, const uint32_t* peak, int64_t rows, int n_mels, int64_t frames, int rows_per_clip, double top_db,
                     double mean, double std, void* stream);
 
+/* ---- video clip front-end: uint8 clips <-> normalised planes (dataloader/clip_transforms.py:31-45 NumpyToTensor, 59-93
+ * Normalize, 111-128 RandomClipFlip; dataloader/aff2compdataset.py:69-77; models/sformer.py:365-373) ----------------------------
+ * avf_clip_normalize: ONE launch.  src uint8 [B, T, H, W, C] (C in 1..4) -> dst, the last k of the C channels as planes:
+ *   layout AVF_CLIP_CTHW: dst [B, k, T, H, W]       layout AVF_CLIP_TCHW: dst [B, T, k, H, W]
+ *   dst[.. c .. h, w] = lut[(C - k + c) * 256 + src[b, t, h, w', C - k + c]],  w' = W - 1 - w where flip[b] != 0, else w
+ * lut: DEVICE fp32 [C * 256] (the caller's table of (v / 255 - mean) / std); flip: DEVICE bytes [B] or null (no clip is mirrored),
+ * read by the kernel at run time.  out_dtype AVF_F32 | AVF_BF16 (round to nearest even).  dst is aligned to its element size;
+ * src needs no alignment.
+ *
+ * avf_clip_denormalize: ONE launch, the inverse direction.  src [B, C, T, H, W] or [B, T, C, H, W] (in_dtype AVF_F32 | AVF_BF16)
+ * -> dst uint8 [B, T, H, W, C]:  trunc(min(max(((x * std[c]) + mean[c]) * 255, 0), 255)), each of the three operations rounded
+ * to fp32 on its own (no fused multiply-add), NaN -> 0.  mean / std: DEVICE fp32 [C].  A flip is not undone.
+ *
+ * Sizes are 64-bit, as is every index in the kernels.  Neither entry point allocates or synchronises; both can be captured.
+ * Every argument is checked before anything is enqueued. */
+#define AVF_CLIP_CTHW 0
+#define AVF_CLIP_TCHW 1
+int avf_clip_normalize(const uint8_t* src, int64_t B, int64_t T, int64_t H, int64_t W, int C, int k, const float* lut,
+                       const uint8_t* flip, void* dst, int out_dtype, int layout, void* stream);
+int avf_clip_denormalize(const void* src, int in_dtype, int layout, int64_t B, int64_t T, int64_t H, int64_t W, int C,
+                         const float* mean, const float* std, uint8_t* dst, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

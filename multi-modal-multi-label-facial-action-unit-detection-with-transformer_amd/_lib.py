@@ -14,6 +14,7 @@ from . import _build
 
 F32, BF16 = 0, 1
 EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
+CLIP_CTHW, CLIP_TCHW = 0, 1
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -125,6 +126,8 @@ SIGNATURES = {
     "avf_eval_scores": (_int, [_vp, _vp, _vp, _vp]),
     "avf_mel_power": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
     "avf_mel_db_norm": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_double, C.c_double, C.c_double, _vp]),
+    "avf_clip_normalize": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _int, _int, _vp]),
+    "avf_clip_denormalize": (_int, [_vp, _int, _int, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

@@ -759,6 +759,47 @@ def mel_db_norm(mel: torch.Tensor, peak: torch.Tensor, rows_per_clip: int, top_d
     return mel
 
 
+CLIP_LAYOUTS = {"cthw": _lib.CLIP_CTHW, "tchw": _lib.CLIP_TCHW}
+
+
+def clip_normalize(clip: torch.Tensor, lut: torch.Tensor, k: Optional[int] = None, flip: Optional[torch.Tensor] = None,
+                   layout: str = "cthw", out_dtype=torch.float32) -> torch.Tensor:
+    """avf_clip_normalize, one launch: clip uint8 [B, T, H, W, C] -> the last k channels as planes, [B, k, T, H, W] ("cthw") or
+    [B, T, k, H, W] ("tchw"), value lut[c, byte] with lut fp32 [C, 256].  flip: bool / uint8 [B] on the device or None; where it
+    is set the clip is mirrored along W.  The flags are read by the kernel (no host synchronisation)."""
+    _need_cuda(clip, lut, flip)
+    assert clip.dim() == 5 and clip.dtype == torch.uint8 and clip.is_contiguous()
+    B, T, H, W, Cn = clip.shape
+    k = Cn if k is None else int(k)
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (Cn, 256)
+    if flip is not None:
+        assert flip.dtype in (torch.bool, torch.uint8) and flip.is_contiguous() and tuple(flip.shape) == (B,)
+    dt, lay = torch_dtype(out_dtype), CLIP_LAYOUTS[layout]
+    shape = (B, k, T, H, W) if layout == "cthw" else (B, T, k, H, W)
+    out = torch.empty(shape, dtype=dt, device=clip.device)
+    _lib.check(_lib.load().avf_clip_normalize(_ptr(clip), B, T, H, W, Cn, k, _ptr(lut), _ptr(flip), _ptr(out), avf_dtype(dt),
+                                              lay, _stream()), "clip_normalize")
+    return out
+
+
+def clip_denormalize(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, layout: str = "cthw") -> torch.Tensor:
+    """avf_clip_denormalize, one launch: x fp32 / bf16 [B, C, T, H, W] ("cthw") or [B, T, C, H, W] ("tchw") -> uint8
+    [B, T, H, W, C] = trunc(clamp(((x * std[c]) + mean[c]) * 255, 0, 255)), NaN -> 0; mean / std fp32 [C] on the device."""
+    _need_cuda(x, mean, std)
+    assert x.dim() == 5 and x.dtype in _TORCH2AVF and x.is_contiguous()
+    lay = CLIP_LAYOUTS[layout]
+    if layout == "cthw":
+        B, Cn, T, H, W = x.shape
+    else:
+        B, T, Cn, H, W = x.shape
+    for v in (mean, std):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() == Cn
+    out = torch.empty(B, T, H, W, Cn, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().avf_clip_denormalize(_ptr(x), avf_dtype(x.dtype), lay, B, T, H, W, Cn, _ptr(mean),
+                                                _ptr(std), _ptr(out), _stream()), "clip_denormalize")
+    return out
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
