@@ -485,6 +485,20 @@ int avf_clip_normalize(const uint8_t* src, int64_t B, int64_t T, int64_t H, int6
 int avf_clip_denormalize(const void* src, int in_dtype, int layout, int64_t B, int64_t T, int64_t H, int64_t W, int C,
                          const float* mean, const float* std, uint8_t* dst, void* stream);
 
+/* ---- clip AutoAugment: the reference's ImageNetPolicy on uint8 clips (dataloader/autoaugment.py, dataloader/ops.py) -------------
+ * avf_clip_autoaugment: ONE launch, one workgroup per frame.  src, dst uint8 [B, T, H, W, C], C = 3 or 4: channels 0..2 of every
+ * frame go through the two slots of its plan, channel 3 is copied.  plan: DEVICE int32 [B * T * 2 * 8], per frame two slots
+ * [op_code, p0 .. p6] applied in order (the encoding is documented in augment.py; the host resolves the random draws and every
+ * double-precision constant into these words).  An op code outside 1..10 does nothing.  Each frame is read once and written once;
+ * everything between happens in LDS: integer arithmetic, fp32 for the blend, fp64 for the autocontrast table and the bicubic of
+ * shearX, no fused multiply-add - the bytes are those of Pillow.  dst == src is allowed (no other overlap); neither needs any
+ * alignment.  A frame has at most avf_clip_autoaugment_max_pixels() pixels (C = 3; C = 4: three quarters of it) - both frame
+ * buffers live in one workgroup's LDS.  Nothing is allocated or synchronised (capturable); every argument is checked before
+ * anything is enqueued. */
+int avf_clip_autoaugment(const uint8_t* src, uint8_t* dst, int64_t B, int64_t T, int64_t H, int64_t W, int C, const int32_t* plan,
+                         void* stream);
+int64_t avf_clip_autoaugment_max_pixels(void);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

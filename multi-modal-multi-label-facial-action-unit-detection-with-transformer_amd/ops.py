@@ -800,6 +800,26 @@ def clip_denormalize(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, lay
     return out
 
 
+def clip_autoaugment_max_pixels() -> int:
+    """the largest H * W of a frame avf_clip_autoaugment takes (two frame buffers of a workgroup's LDS; C = 4: 3/4 of it)"""
+    return int(_lib.load().avf_clip_autoaugment_max_pixels())
+
+
+def clip_autoaugment(clip: torch.Tensor, plan: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avf_clip_autoaugment, one launch: clip uint8 [B, T, H, W, C] (C = 3 or 4) -> uint8 of the same shape, every frame through
+    the two slots of plan int32 [B, T, 2, 8] on the device (augment.draw_plan / make_plan).  out: None, or a contiguous uint8
+    tensor of the clip's shape - the clip itself is allowed."""
+    _need_cuda(clip, plan, out)
+    assert clip.dim() == 5 and clip.dtype == torch.uint8 and clip.is_contiguous()
+    B, T, H, W, Cn = clip.shape
+    assert plan.dtype == torch.int32 and plan.is_contiguous() and tuple(plan.shape) == (B, T, 2, 8)
+    if out is None:
+        out = torch.empty_like(clip)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == clip.shape and out.device == clip.device
+    _lib.check(_lib.load().avf_clip_autoaugment(_ptr(clip), _ptr(out), B, T, H, W, Cn, _ptr(plan), _stream()), "clip_autoaugment")
+    return out
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
