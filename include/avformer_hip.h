@@ -189,10 +189,12 @@ int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, 
                    int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux, int64_t ldaux,
                    void* workspace, float* colsum, void* mx_q, void* mx_s, void* stream);
 
-/* The weight gradients of one layer as ONE grouped launch (autograd of nn.Linear, heads.py:191,195,212,215): up to four
+/* The weight gradients of one layer (or of up to four layers) as ONE grouped launch (autograd of nn.Linear,
+ * heads.py:191,195,212,215): up to sixteen
  * C_i[M_i,N_i] (fp32, dense) = A_i[K,M_i]^T * B_i[K,N_i] (bf16, token-major, dense: lda = M_i, ldb = N_i) that share the
  * reduction length K (the B*N token rows); K % 64 == 0, M_i % 8 == 0, N_i % 8 == 0.  Split-K partial slabs live in
- * `workspace` (avf_gemm_tn_group_workspace_bytes) and are folded by a second launch. */
+ * `workspace` (avf_gemm_tn_group_workspace_bytes) and are folded by a second launch; a group whose tiles fill the chip
+ * unsplit needs no workspace (0 bytes) and stores straight to C_i. */
 size_t avf_gemm_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N);
 int avf_gemm_tn_group(int count, int64_t K, const void* const* A, const void* const* B, float* const* C, const int64_t* M,
                       const int64_t* N, void* workspace, void* stream);
@@ -582,6 +584,39 @@ int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const voi
 int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
                   const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum,
                   float* dx_in, void* dx_in_lo, float* dx_in_colsum, const avf_layer_grads* g, void* workspace,
+                  void* stream);
+
+/* ---- deferred weight gradients: several layers' dW in one launch (bf16 path) ---------------------------------------------
+ * One layer's four weight gradients are 64 tiles of 256 x 128 at dim 512 - a quarter of the chip - so avf_layer_bwd splits their
+ * token reduction four ways and folds the partial slabs in a second launch.  A caller that runs a whole stack can instead let
+ * the gradients of several layers wait and launch them together: four such layers are exactly one workgroup per CU, with no
+ * split, no slabs and no slab fold.
+ *   avf_layer_dw_defer_ok(cfg, &tiles, &slots): 1 if the layer's mode allows it (AVF_BF16 on the grouped launch: rows % 64 == 0;
+ *     no dropout, no mx8, no key mask, not the short-sequence layer), with the layer's tile count and the workgroup slots of one
+ *     round of the kernel its group runs on.  A caller groups at most slots / tiles layers (and at most avf_layers_dw_max()).
+ *   avf_layer_bwd_dx: avf_layer_bwd without the weight-gradient launch and the layer's column folds.  dx_in and everything the
+ *     layer below needs are written as usual; of the parameter gradients only b2 (when handed over as dx_out_colsum) is final.
+ *     The operands the deferred launch reads stay in dw_block (DEVICE, avf_layer_dw_block_bytes(cfg) bytes, 256-byte aligned,
+ *     one per deferred layer) and are described in dw_desc (HOST, avf_layer_dw_desc_bytes() bytes).  Until avf_layers_dw has
+ *     run, the caller keeps alive and unchanged: dw_block, the layer's `saved` buffer, and dx_out_lo (the bf16 gradient image
+ *     the layer read - a caller that ping-pongs two stream buffers gives each deferred layer its own).
+ *   avf_layers_dw: the weight gradients and column folds of n_layers (1 .. avf_layers_dw_max()) deferred layers, the order of
+ *     cfgs / descs being the order of the launch's tile list (top layer first).  One grouped launch, then one fold launch: the
+ *     column folds alone when the group fills a round unsplit, else the slab fold with the column folds riding along
+ *     (workspace / workspace_bytes: at least avf_layers_dw_workspace_bytes, which is 0 for a group that ends up unsplit; a
+ *     workspace that is too small is an error, nothing is launched).
+ * Sums are combined in a fixed order (no atomics): the same inputs give the same bits.  An unsplit group accumulates each
+ * element in one fp32 chain where avf_layer_bwd adds four partial chains: the gradients differ at rounding level. */
+int avf_layer_dw_defer_ok(const avf_layer_cfg* cfg, int* tiles_per_layer, int* slots);
+int avf_layers_dw_max(void);
+size_t avf_layer_dw_block_bytes(const avf_layer_cfg* cfg);
+size_t avf_layer_dw_desc_bytes(void);
+int avf_layer_bwd_dx(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                     const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum,
+                     float* dx_in, void* dx_in_lo, float* dx_in_colsum, const avf_layer_grads* g, void* workspace,
+                     void* dw_block, void* dw_desc, void* stream);
+size_t avf_layers_dw_workspace_bytes(const avf_layer_cfg* cfgs, int n_layers);
+int avf_layers_dw(const avf_layer_cfg* cfgs, int n_layers, const void* const* descs, void* workspace, size_t workspace_bytes,
                   void* stream);
 
 /* test aid: the keep/(1-p) factors (0 or 1/(1-p_eff)) dropout site `site` (0 after to_out, 1 after GELU, 2 after

@@ -144,6 +144,14 @@ SIGNATURES = {
     "avf_layer_fwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp]),
     "avf_layer_bwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              C.POINTER(LayerPtrs), _vp, _vp]),
+    "avf_layer_dw_defer_ok": (_int, [C.POINTER(LayerCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "avf_layers_dw_max": (_int, []),
+    "avf_layer_dw_block_bytes": (_sz, [C.POINTER(LayerCfg)]),
+    "avf_layer_dw_desc_bytes": (_sz, []),
+    "avf_layer_bwd_dx": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp]),
+    "avf_layers_dw_workspace_bytes": (_sz, [C.POINTER(LayerCfg), _int]),
+    "avf_layers_dw": (_int, [C.POINTER(LayerCfg), _int, _vp, _vp, _sz, _vp]),
     "avf_layer_adam_step": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs),
                                    C.POINTER(LayerPtrs), _vp, _f, _f, _f, _f, _f, _vp, _vp]),
     "avf_stack_adam_step": (_int, [C.POINTER(LayerCfg), _int, C.POINTER(LayerPtrs), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs),

@@ -293,7 +293,7 @@ extern "C" int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, in
 
 static int fill_tn_group(TnGroupArgs* g, int count, int64_t K, const void* const* A, const void* const* B, float* const* C,
                          const int64_t* M, const int64_t* N) {
-  AVF_REQUIRE(count >= 1 && count <= 4 && M && N, "gemm_tn_group: 1..4 problems");
+  AVF_REQUIRE(count >= 1 && count <= kTnGroupMax && M && N, "gemm_tn_group: 1..%d problems", kTnGroupMax);
   memset(g, 0, sizeof(*g));
   g->count = count;
   g->K = K;

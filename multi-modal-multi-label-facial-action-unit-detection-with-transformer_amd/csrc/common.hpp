@@ -391,15 +391,16 @@ struct FoldJob {
   int nb, width, seg;
   float *o0, *o1, *o2;
 };
+constexpr int kFoldMax = 12;  // three jobs per layer, the four layers of the largest weight-gradient group
 struct FoldList {
-  FoldJob job[3];
+  FoldJob job[kFoldMax];
   int count;
 };
 // 16 columns (4 quads) x 64 row groups per 256-thread block, eight 16-byte loads per thread in flight; width % 4 == 0, 16-byte
 // aligned partials.  (Round 4: 32 columns x 32 row groups with four loads in flight put 48 blocks on the 1536 columns of a
 // LayerNorm fold, each walking 1024 partial rows with 16 KiB in flight - latency-bound at ~8 GB/s per CU, 12 of the 19.5 us of
 // the layer's fold launch at C3.  Half the columns per block and twice the loads in flight: four times the bytes in flight.)
-int fold_list(const FoldList& fl, hipStream_t s);  // the (up to three) jobs of a list in one launch
+int fold_list(const FoldList& fl, hipStream_t s);  // the (up to kFoldMax) jobs of a list in one launch
 constexpr int FOLD_COLS = 16, FOLD_RG = 64;
 __device__ __forceinline__ void fold_columns_vec(const FoldJob& j, int colgroup, float4 (*red)[FOLD_COLS / 4]) {
   const int cq = threadIdx.x & (FOLD_COLS / 4 - 1), grp = threadIdx.x / (FOLD_COLS / 4);
@@ -521,18 +522,22 @@ struct MxQuantJob {
 int quant_mx8_multi(const MxQuantJob* jobs, int n, hipStream_t s);
 int quant_mx8(const void* x, int dtype, int64_t ldx, int64_t R, int64_t K, void* q, int64_t ldq, void* scales, hipStream_t s);
 size_t gemm_bf16_tn_ws(int64_t M, int64_t N, int64_t K);
-// up to four C_i[M_i,N_i] = A_i[K,M_i]^T B_i[K,N_i] sharing K, one launch (weight gradients of one layer)
+// up to kTnGroupMax C_i[M_i,N_i] = A_i[K,M_i]^T B_i[K,N_i] sharing K, one launch (the weight gradients of one layer, or of up
+// to four layers whose tiles together fill one round of the chip - then without a split of K, see avf_layers_dw)
+constexpr int kTnGroupMax = 16;
 struct TnGroupArgs {
   int count;
   int64_t K;
-  const void* A[4];
-  const void* B[4];
-  float* C[4];
-  int64_t M[4], N[4], lda[4], ldb[4];
+  const void* A[kTnGroupMax];
+  const void* B[kTnGroupMax];
+  float* C[kTnGroupMax];
+  int64_t M[kTnGroupMax], N[kTnGroupMax], lda[kTnGroupMax], ldb[kTnGroupMax];
   void* workspace;
 };
 bool gemm_bf16_tn_group_ok(const TnGroupArgs& a);
 size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a);
+// the tile count of the group on the kernel it would run on, and the workgroup slots of one round of that kernel
+void gemm_bf16_tn_group_plan(const TnGroupArgs& a, int* tiles, int* slots);
 int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extra_folds = nullptr);
 // the same group for fp32 operands in the parity mode's bf16x3 arithmetic (gemm_f32.hip, round 6): one launch + one fold
 bool gemm_f32x3_tn_group_ok(const TnGroupArgs& a);

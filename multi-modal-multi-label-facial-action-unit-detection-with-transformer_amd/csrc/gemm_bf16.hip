@@ -465,9 +465,9 @@ __global__ __launch_bounds__(256) void fold_slabs_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// grouped TN kernel, LDS-DMA staged: up to 4 weight-gradient GEMMs that share the reduction axis
-// (the B*N token rows of one layer) in ONE launch, so the chip is filled even though each dW has only
-// 16..48 output tiles.  K % 64 == 0.  Staged rows are 256 B (128 bf16) with no padding (LDS-DMA images are
+// grouped TN kernel, LDS-DMA staged: up to kTnGroupMax weight-gradient GEMMs that share the reduction axis
+// (the B*N token rows of one layer, or of several layers of a stack) in ONE launch, so the chip is filled even
+// though each dW has only 16..48 output tiles.  K % 64 == 0.  Staged rows are 256 B (128 bf16) with no padding (LDS-DMA images are
 // lane-linear); transposed-read bank conflicts are removed by XOR-ing the 16-byte chunk index with
 // (row & 7) << 1 on the SOURCE address and on the read address (8 consecutive rows -> 8 distinct 32-byte
 // windows of the 256-byte bank row).
@@ -480,10 +480,12 @@ struct TnProblem {
   int lda, ldb, M, N, tiles_n, tile_start;
 };
 struct TnGroup {
-  TnProblem p[4];
+  TnProblem p[kTnGroupMax];
   int nprob, K, kchunk, S, total_tiles;
   int xcd_groups;  // 256 x 128 kernel: > 0 = XCD-aware block order (see gemm_bf16_tn_group_big_kernel), 0 = tile-major ids
 };
+// both travel by value: the group to the GEMM kernels, the group and the column folds to fold_group_kernel
+static_assert(sizeof(TnGroup) + sizeof(FoldList) + 16 <= 4096, "TnGroup + FoldList exceed the 4 KiB kernel-argument budget");
 
 __device__ __forceinline__ bf16x8_t tr_frag_swz(const lds_char* tile, int row_base, int col_base, int li, int lg) {
   const int row = row_base + 4 * lg + (li >> 2);  // row & 7 is the same for the +16 read
@@ -511,9 +513,8 @@ __global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g
   // block -> (tile, split); splits of one tile are adjacent ids
   const int tile = blockIdx.x / g.S, split = blockIdx.x - tile * g.S;
   int pi = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (i < g.nprob && tile >= g.p[i].tile_start) pi = i;
+  for (int i = 1; i < g.nprob; ++i)  // (uniform: scalar loads of the argument block)
+    if (tile >= g.p[i].tile_start) pi = i;
   const TnProblem& P = g.p[pi];
   const int lt = tile - P.tile_start;
   const int m0 = (lt / P.tiles_n) * TB, n0 = (lt % P.tiles_n) * TB;
@@ -645,7 +646,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_group_big_kernel(TnGroup g) 
   // cut into 8 / S contiguous groups: an XCD then streams ONE K-range of operand panels that no other group needs (the
   // list is ordered so that the cut falls between problems: dWqkv + dWo | dW1 + dW2), and every operand byte crosses the
   // fabric once.  The tile-major order (tile = id / S) spread the tiles of one panel over two XCD groups: 235 MB per launch
-  // at C2 against 161 MB of operands + slabs.
+  // at C2 against 161 MB of operands + slabs.  A group over several layers repeats that list per layer, so with 8 / S
+  // dividing twice the layer count a cut still falls between two problems (C2, four layers unsplit: XCD x takes half
+  // x % 2 of layer x / 2) and no operand panel is shared between two XCDs.
   int tile, split;
   if (g.xcd_groups > 0) {
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -670,9 +673,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_group_big_kernel(TnGroup g) 
     split = blockIdx.x - tile * g.S;
   }
   int pi = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (i < g.nprob && tile >= g.p[i].tile_start) pi = i;
+  for (int i = 1; i < g.nprob; ++i)  // (uniform: scalar loads of the argument block)
+    if (tile >= g.p[i].tile_start) pi = i;
   const TnProblem& P = g.p[pi];
   const int lt = tile - P.tile_start;
   const int m0 = (lt / P.tiles_n) * TBM, n0 = (lt % P.tiles_n) * TB;
@@ -848,7 +850,7 @@ int with_fold_splits(int S, F&& f) {
 }
 
 int tn_group_splits(int total_tiles, int64_t K, int slots = kWorkgroupSlots) {
-  static const int forced = tuning_int("AVF_TN_SPLITS", 0);  // tuning aid
+  const int forced = tuning_int("AVF_TN_SPLITS", 0);  // tuning aid (read per call: a test runs both arms in one process)
   if (forced > 0) return forced;
   // kWorkgroupSlots (2 per CU at 72 KiB of LDS).  Pick the split count whose total workgroup count fills whole rounds of
   // them best, charging 5 % per extra slab for the fold's traffic: 128 tiles (d = 512) -> 4 splits = exactly one round;
@@ -979,7 +981,7 @@ int gemm_bf16_tn(const GemmArgs& a, hipStream_t s) {
 }
 
 bool gemm_bf16_tn_group_ok(const TnGroupArgs& a) {
-  if (a.count < 1 || a.count > 4 || a.K <= 0 || a.K % TR != 0) return false;
+  if (a.count < 1 || a.count > kTnGroupMax || a.K <= 0 || a.K % TR != 0) return false;
   for (int i = 0; i < a.count; ++i) {
     if (a.M[i] % 8 || a.N[i] % 8 || a.lda[i] % 8 || a.ldb[i] % 8) return false;
     if (((uintptr_t)a.A[i] & 15) || ((uintptr_t)a.B[i] & 15) || ((uintptr_t)a.C[i] & 15)) return false;
@@ -1001,6 +1003,12 @@ static int tn_group_tiles(const TnGroupArgs& a, bool big) {
   int tiles = 0;
   for (int i = 0; i < a.count; ++i) tiles += (int)(ceil_div(a.M[i], big ? TBM : TB) * ceil_div(a.N[i], TB));
   return tiles;
+}
+
+void gemm_bf16_tn_group_plan(const TnGroupArgs& a, int* tiles, int* slots) {
+  const bool big = tn_group_big(a);
+  *tiles = tn_group_tiles(a, big);
+  *slots = big ? kWorkgroupSlots / 2 : kWorkgroupSlots;
 }
 
 size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a) {
@@ -1084,6 +1092,8 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
   memset(&fl, 0, sizeof(fl));
   if (extra_folds) fl = *extra_folds;
   const int nslab = g.S > 1 ? a.count : 0;
+  // an unsplit group over several layers has no slabs to fold: its column folds alone, in a grid of their own size
+  if (nslab == 0 && fl.count > 3) return fold_list(fl, s);
   if (nslab + fl.count > 0) {
     dim3 grid(256, nslab + fl.count);
     with_fold_splits(nslab ? g.S : 0, [&](auto ss) {

@@ -199,6 +199,13 @@ TnGroupArgs dw_group(const Dims& d, const void* gy, const void* g_act, const voi
   return a;
 }
 
+size_t work_colsum_bytes(const Dims& d) {
+  const int maxc = d.M > d.D ? d.M : d.D;
+  size_t csb = colsum_ws(d.R, maxc);
+  if (d.dt == AVF_BF16 && gemm_nt_colsum_ws(d.R, d.M) > csb) csb = gemm_nt_colsum_ws(d.R, d.M);
+  return csb;
+}
+
 struct Work {
   void *du, *dh, *d_o, *dqkv, *dx_mid_lo, *dx_out_lo, *ln_ws, *ln_ws1, *cs_ws, *gemm_ws;
   float *dx_mid, *delta;
@@ -223,10 +230,7 @@ size_t carve_work(const Dims& d, void* base, Work* w) {
   t.delta = (float*)c.take((size_t)d.B * d.H * d.N * 4 * 2);  // delta, then the negated lse2 rows (bf16 backward)
   t.ln_ws = c.take(layernorm_bwd_ws(d.R, d.D));
   t.ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D));  // LN1 partials (its fold may be deferred past LN2's)
-  const int maxc = d.M > d.D ? d.M : d.D;
-  size_t csb = colsum_ws(d.R, maxc);
-  if (d.dt == AVF_BF16 && gemm_nt_colsum_ws(d.R, d.M) > csb) csb = gemm_nt_colsum_ws(d.R, d.M);
-  t.cs_ws = c.take(csb);
+  t.cs_ws = c.take(work_colsum_bytes(d));
   size_t g = 0;
   if (d.dt == AVF_BF16) {
     size_t a = gemm_bf16_tn_ws(3 * d.I, d.D, d.R), b = gemm_bf16_tn_ws(d.D, d.I, d.R);
@@ -272,6 +276,37 @@ size_t carve_work(const Dims& d, void* base, Work* w) {
   t.gm_m = (float*)c.take(f32_drop ? d.R * d.D * 4 : 0);
   if (w) *w = t;
   return c.off;
+}
+
+// A layer whose weight gradients are DEFERRED (avf_layer_bwd_dx, avf_layers_dw) keeps what the grouped launch will read in a
+// block of its own instead of the shared scratch, which the layers below overwrite: the A operands du, dqkv and dx_mid_lo (the
+// B operands already live in the layer's saved activations), the bf16 image of dx_out where the layer made it itself, and the
+// partial rows of its three column folds.  bf16 path only.
+size_t carve_dw_block(const Dims& d, void* base, Work* w) {
+  Carver c(base);
+  void* du = c.take(d.R * d.M * 2);
+  void* dqkv = c.take(d.R * 3 * d.I * 2);
+  void* dx_mid_lo = c.take(d.R * d.D * 2);
+  void* dx_out_lo = c.take(d.R * d.D * 2);
+  void* ln_ws = c.take(layernorm_bwd_ws(d.R, d.D));
+  void* ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D));
+  void* cs_ws = c.take(work_colsum_bytes(d));
+  if (w) {
+    w->du = du; w->dqkv = dqkv; w->dx_mid_lo = dx_mid_lo; w->dx_out_lo = dx_out_lo;
+    w->ln_ws = ln_ws; w->ln_ws1 = ln_ws1; w->cs_ws = cs_ws;
+  }
+  return c.off;
+}
+// what avf_layer_bwd_dx leaves behind for avf_layers_dw (host memory, caller-provided, avf_layer_dw_desc_bytes() long)
+constexpr uint32_t kDwDescMagic = 0x64574431u;
+struct DwDeferred {
+  uint32_t magic;
+  TnGroupArgs grp;   // the four problems of the layer, attention half first (dw_group)
+  FoldJob folds[3];  // db1 | dgamma2, dbeta2, dbo | dgamma1, dbeta1, the db2 of the layer below
+};
+// the modes whose weight gradients can wait: the bf16 path on its grouped launch, nothing that adds images or masks
+bool dw_defer_mode_ok(const Dims& d) {
+  return d.dt == AVF_BF16 && !d.gsd && d.p == 0.f && !d.mx && !d.mxb && !d.keep && !small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M);
 }
 
 // C[R, out] = A[R, in] * W[out, in]^T  (nn.Linear forward)
@@ -520,12 +555,17 @@ extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   return 0;
 }
 
-extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
-                             const void* saved, const float* dx_out, const void* dx_out_lo,
-                             const float* dx_out_colsum, float* dx_in, void* dx_in_lo, float* dx_in_colsum,
-                             const avf_layer_grads* g, void* workspace, void* stream) {
+// dw_block / dw_desc (both or neither): the weight gradients and the column folds of the layer are NOT launched - their
+// operands stay in dw_block and dw_desc describes them for avf_layers_dw
+static int layer_bwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                          const void* saved, const float* dx_out, const void* dx_out_lo,
+                          const float* dx_out_colsum, float* dx_in, void* dx_in_lo, float* dx_in_colsum,
+                          const avf_layer_grads* g, void* workspace, void* stream, void* dw_block, DwDeferred* dw_desc) {
   Dims d;
   AVF_TRY(make_dims(cfg, &d));
+  AVF_REQUIRE(!dw_desc || (dw_block && dw_defer_mode_ok(d) && ((uintptr_t)dw_block & 255) == 0),
+              "layer_bwd_dx: this mode keeps its weight gradients in the layer (ask avf_layer_dw_defer_ok first), or the "
+              "operand block is missing / not 256-byte aligned");
   AVF_REQUIRE(p && x_in && saved && g && workspace, "layer_bwd: null pointer");
   // bf16 gradient stream: the incoming gradient may come as its bf16 image alone, and the fp32 dx_in is optional (a caller
   // asks for it only where it consumes it, e.g. below the bottom layer)
@@ -540,6 +580,7 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   const bool lo = d.dt == AVF_BF16;
   Work w;
   carve_work(d, workspace, &w);
+  if (dw_desc) carve_dw_block(d, dw_block, &w);
 
   // gradient of the layer output in the compute dtype (GEMM operand)
   // dropout: the Linears behind a dropout site see the masked, rescaled gradient (the residual stream does not)
@@ -591,6 +632,8 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   FoldList folds;
   memset(&folds, 0, sizeof(folds));
   folds.count = 3;
+  AVF_REQUIRE(!dw_desc || (grouped && !small_bwd), "layer_bwd_dx: the layer's weight gradients do not form a grouped launch "
+              "(rows %% 64, widths %% 8, 16-byte aligned operands)");
 
   // the grouped dW launch and its fold are shared with the general path
   if (small_bwd) {
@@ -762,9 +805,103 @@ extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   if (!grouped && !grouped32) AVF_TRY(linear_dw(d, w.dqkv, 3 * d.I, sv.h1, d.D, g->w_qkv, w.gemm_ws, s));
   // one launch folds the split-K slabs of the four weight gradients and the three deferred column folds
   // (db1; dgamma2/dbeta2/dbo; dgamma1/dbeta1/previous layer's db2)
+  if (dw_desc) {
+    dw_desc->magic = kDwDescMagic;
+    dw_desc->grp = grp;
+    dw_desc->grp.workspace = nullptr;
+    for (int j = 0; j < 3; ++j) dw_desc->folds[j] = folds.job[j];
+    return 0;
+  }
   if (grouped) {
     AVF_TRY(gemm_bf16_tn_group(grp, s, &folds));
   }
   if (grouped32) AVF_TRY(fold_list(folds, s));  // the two LayerNorm column folds of the layer in one launch (job 0 stays empty)
   return 0;
+}
+
+extern "C" int avf_layer_bwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                             const void* saved, const float* dx_out, const void* dx_out_lo,
+                             const float* dx_out_colsum, float* dx_in, void* dx_in_lo, float* dx_in_colsum,
+                             const avf_layer_grads* g, void* workspace, void* stream) {
+  return layer_bwd_impl(cfg, p, lowp, x_in, saved, dx_out, dx_out_lo, dx_out_colsum, dx_in, dx_in_lo, dx_in_colsum, g, workspace,
+                        stream, nullptr, nullptr);
+}
+
+// ---- deferred weight gradients: the dX chain of a layer now, the dW groups of several layers in one launch later ----------------
+extern "C" int avf_layer_dw_defer_ok(const avf_layer_cfg* cfg, int* tiles_per_layer, int* slots) {
+  Dims d;
+  if (make_dims(cfg, &d) || !dw_defer_mode_ok(d) || d.R % 64 != 0) return 0;
+  TnGroupArgs ga = dw_group(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (!gemm_bf16_tn_group_ok(ga)) return 0;
+  int t = 0, sl = 0;
+  gemm_bf16_tn_group_plan(ga, &t, &sl);
+  if (tiles_per_layer) *tiles_per_layer = t;
+  if (slots) *slots = sl;
+  return 1;
+}
+extern "C" int avf_layers_dw_max(void) { return kTnGroupMax / 4; }
+extern "C" size_t avf_layer_dw_block_bytes(const avf_layer_cfg* cfg) {
+  Dims d;
+  if (make_dims(cfg, &d) || !dw_defer_mode_ok(d)) return 0;
+  return align_up(carve_dw_block(d, nullptr, nullptr), 256);
+}
+extern "C" size_t avf_layer_dw_desc_bytes(void) { return sizeof(DwDeferred); }
+
+extern "C" int avf_layer_bwd_dx(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                                const void* saved, const float* dx_out, const void* dx_out_lo,
+                                const float* dx_out_colsum, float* dx_in, void* dx_in_lo, float* dx_in_colsum,
+                                const avf_layer_grads* g, void* workspace, void* dw_block, void* dw_desc, void* stream) {
+  AVF_REQUIRE(dw_block && dw_desc, "layer_bwd_dx: null operand block / descriptor");
+  return layer_bwd_impl(cfg, p, lowp, x_in, saved, dx_out, dx_out_lo, dx_out_colsum, dx_in, dx_in_lo, dx_in_colsum, g, workspace,
+                        stream, dw_block, (DwDeferred*)dw_desc);
+}
+
+// the group over the layers of `descs` (the order given: top layer first), each layer attention half | MLP half
+static int layers_dw_group(const avf_layer_cfg* cfgs, int n_layers, const void* const* descs, TnGroupArgs* grp, FoldList* fl) {
+  AVF_REQUIRE(cfgs && n_layers >= 1 && n_layers <= kTnGroupMax / 4, "layers_dw: 1..%d layers per group", kTnGroupMax / 4);
+  memset(grp, 0, sizeof(*grp));
+  if (fl) memset(fl, 0, sizeof(*fl));
+  for (int l = 0; l < n_layers; ++l) {
+    Dims d;
+    AVF_TRY(make_dims(&cfgs[l], &d));
+    AVF_REQUIRE(dw_defer_mode_ok(d), "layers_dw: layer %d is in a mode that keeps its weight gradients in the layer", l);
+    TnGroupArgs one;
+    if (descs) {
+      const DwDeferred* dd = (const DwDeferred*)descs[l];
+      AVF_REQUIRE(dd && dd->magic == kDwDescMagic, "layers_dw: descriptor %d was not written by avf_layer_bwd_dx", l);
+      one = dd->grp;
+      AVF_REQUIRE(one.K == d.R, "layers_dw: descriptor %d belongs to another configuration", l);
+      for (int j = 0; j < 3; ++j) fl->job[3 * l + j] = dd->folds[j];
+    } else {
+      one = dw_group(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }
+    AVF_REQUIRE(l == 0 || one.K == grp->K, "layers_dw: the layers of a group share their token rows");
+    grp->K = one.K;
+    for (int i = 0; i < 4; ++i) {
+      const int q = 4 * l + i;
+      grp->A[q] = one.A[i]; grp->B[q] = one.B[i]; grp->C[q] = one.C[i];
+      grp->M[q] = one.M[i]; grp->N[q] = one.N[i]; grp->lda[q] = one.lda[i]; grp->ldb[q] = one.ldb[i];
+    }
+  }
+  grp->count = 4 * n_layers;
+  if (fl) fl->count = 3 * n_layers;
+  return 0;
+}
+extern "C" size_t avf_layers_dw_workspace_bytes(const avf_layer_cfg* cfgs, int n_layers) {
+  TnGroupArgs grp;
+  if (layers_dw_group(cfgs, n_layers, nullptr, &grp, nullptr)) return 0;
+  return gemm_bf16_tn_group_ws(grp);
+}
+extern "C" int avf_layers_dw(const avf_layer_cfg* cfgs, int n_layers, const void* const* descs, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  AVF_REQUIRE(descs, "layers_dw: null descriptors");
+  TnGroupArgs grp;
+  FoldList fl;
+  AVF_TRY(layers_dw_group(cfgs, n_layers, descs, &grp, &fl));
+  AVF_REQUIRE(gemm_bf16_tn_group_ok(grp), "layers_dw: the group does not fit the grouped launch");
+  const size_t need = gemm_bf16_tn_group_ws(grp);
+  AVF_REQUIRE(need == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need),
+              "layers_dw: split-K workspace missing or too small (%zu bytes given, %zu needed)", workspace_bytes, need);
+  grp.workspace = workspace;
+  return gemm_bf16_tn_group(grp, (hipStream_t)stream, &fl);  // + the slab fold with the column folds, or the column folds alone
 }

@@ -57,30 +57,35 @@ int fold_job(const FoldJob& j, hipStream_t s) { return launch_fold(j.partial, j.
 
 // every job of a list in ONE launch (the parity mode's layer backward: its LayerNorm column folds were a launch each - 19 tiny
 // launches per C2 step); jobs with a null partial are skipped.  Falls back to one launch per job for unaligned / odd widths.
-__global__ __launch_bounds__(256) void fold_list_kernel(FoldList fl, int g0, int g1, int g2) {
+struct FoldStarts { int first[kFoldMax + 1]; };  // first[j] = first block of job j; first[kFoldMax] = the grid
+__global__ __launch_bounds__(256) void fold_list_kernel(FoldList fl, FoldStarts st) {
   __shared__ float4 red[FOLD_RG][FOLD_COLS / 4];
   const int b = blockIdx.x;
-  const int j = b < g0 ? 0 : (b < g0 + g1 ? 1 : 2);
-  const int local = b - (j == 0 ? 0 : (j == 1 ? g0 : g0 + g1));
-  (void)g2;
-  fold_columns_vec(fl.job[j], local, red);
+  int j = 0;
+  for (int i = 1; i < kFoldMax; ++i)  // (uniform; an empty job has first[i] == first[i + 1] and is never the last match)
+    if (b >= st.first[i] && st.first[i] < st.first[i + 1]) j = i;
+  fold_columns_vec(fl.job[j], b - st.first[j], red);
 }
 int fold_list(const FoldList& fl, hipStream_t s) {
-  int g[3] = {0, 0, 0};
+  AVF_REQUIRE(fl.count >= 0 && fl.count <= kFoldMax, "fold_list: %d jobs (at most %d)", fl.count, kFoldMax);
+  FoldStarts st;
   bool vec = true;
-  for (int j = 0; j < 3; ++j) {
+  int total = 0;
+  for (int j = 0; j < kFoldMax; ++j) {
+    st.first[j] = total;
     const FoldJob& job = fl.job[j];
     if (j >= fl.count || !job.partial) continue;
-    g[j] = (int)ceil_div(job.width, FOLD_COLS);
+    total += (int)ceil_div(job.width, FOLD_COLS);
     vec = vec && job.width % 4 == 0 && (((uintptr_t)job.partial) & 15) == 0;
   }
-  if (g[0] + g[1] + g[2] == 0) return 0;
+  st.first[kFoldMax] = total;
+  if (total == 0) return 0;
   if (!vec) {
-    for (int j = 0; j < fl.count && j < 3; ++j)
+    for (int j = 0; j < fl.count; ++j)
       if (fl.job[j].partial) AVF_TRY(fold_job(fl.job[j], s));
     return 0;
   }
-  fold_list_kernel<<<(unsigned)(g[0] + g[1] + g[2]), 256, 0, s>>>(fl, g[0], g[1], g[2]);
+  fold_list_kernel<<<(unsigned)total, 256, 0, s>>>(fl, st);
   return check_launch("fold_list_kernel");
 }
 

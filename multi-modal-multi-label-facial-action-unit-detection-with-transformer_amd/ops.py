@@ -280,8 +280,8 @@ def gemm_ws(a: torch.Tensor, w_packed: torch.Tensor, n_out: int, out_dtype=None,
 
 
 def gemm_tn_group(pairs):
-    """[(A_i [K, M_i] bf16, B_i [K, N_i] bf16), ...] (up to 4, same K) -> [C_i [M_i, N_i] fp32 = A_i^T B_i]: the grouped
-    weight-gradient launch of a layer's backward (avf_gemm_tn_group)."""
+    """[(A_i [K, M_i] bf16, B_i [K, N_i] bf16), ...] (up to 16, same K) -> [C_i [M_i, N_i] fp32 = A_i^T B_i]: the grouped
+    weight-gradient launch of a layer's backward, or of up to four layers' (avf_gemm_tn_group)."""
     lib = _lib.load()
     n = len(pairs)
     As = [a.contiguous() for a, _ in pairs]

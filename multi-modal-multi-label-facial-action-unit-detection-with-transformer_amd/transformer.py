@@ -97,6 +97,30 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def plan_dw_groups(n_layers: int, tiles_per_layer: int, slots: int, max_group: int = 4, force: int = 0) -> List[int]:
+    """How backward groups the layers' weight-gradient launches, from the top layer down: a list of group sizes that sums
+    to ``n_layers``.  One layer's four dW GEMMs are ``tiles_per_layer`` output tiles, far fewer than the ``slots`` workgroups
+    of one round of the kernel, so a layer on its own splits its token reduction and folds the partial slabs afterwards.
+    The largest ``g`` with ``g * tiles_per_layer <= slots`` (at most ``max_group`` layers fit one launch's argument block)
+    fills a round - exactly, at 64 tiles on 256 slots - with no split at all; the layers left over form one smaller group,
+    whose split count the library picks so that it stays within a round.  No group is ever larger than one round: a second
+    round would run with part of the chip idle.  ``g == 1`` (a layer that fills more than half a round by itself) is the
+    per-layer launch.  ``force`` > 0 (AVF_DW_GROUP) sets ``g``, still capped by ``max_group``."""
+    if n_layers <= 0:
+        return []
+    g = force if force > 0 else slots // max(1, tiles_per_layer)
+    g = max(1, min(g, max_group, n_layers))
+    out = [g] * (n_layers // g)
+    if n_layers % g:
+        out.append(n_layers % g)
+    return out
+
+
+class _DwGroup:
+    """buffers of one deferred weight-gradient group (Transformer._dw_buffers)"""
+    __slots__ = ("cfgs", "ws_bytes", "blocks", "descs", "desc_ptrs", "ws")
+
+
 class _StackFn(torch.autograd.Function):
     """x -> L layers.  Saved activations live in per-layer byte buffers carved by the library."""
 
@@ -218,6 +242,9 @@ class _StackFn(torch.autograd.Function):
         live = mod.flat_parameters()
         sizes = [p.numel() for p in ctx.params[:PARAMS_PER_LAYER]]
         hook = mod._grad_hook
+        # weight gradients of several layers in one launch (plan_dw_groups): not under a gradient hook - a data-parallel
+        # wrapper wants each layer's gradients as early as possible
+        groups = mod._dw_plan(lib, cfgs) if (bf16 and hook is None and L > 1) else [1] * L
         # one flat fp32 gradient bucket per layer; the tensors' .grad become views of it.  The buckets of all layers are
         # consecutive slices of ONE allocation, so a data-parallel wrapper can reduce several adjacent layers with one
         # collective (fewer, larger all-reduces: less host time per step, better xGMI efficiency)
@@ -256,22 +283,38 @@ class _StackFn(torch.autograd.Function):
                         waiter()  # accumulation needs the reduced values
                     p.grad.add_(v)
 
-        for l in reversed(range(L)):
-            gp = _lib.LayerPtrs(*[base + 4 * l * per_layer + o for o in offs])
-            pp = mod._param_struct(ctx.params, l)
-            # LN1' of this layer writes the column sums of dx_in directly into the previous layer's b2 gradient
-            # bf16 gradient stream: the fp32 buffer carries the gradient only into the top layer (when no bf16 image came
-            # with it) and out of the bottom one; in between the layers hand each other the bf16 image alone
-            dx_out_p = None if (gs16 and have_lo) else _ptr(dx)
-            dx_in_p = None if (gs16 and l > 0) else _ptr(dx)
-            _lib.check(lib.avf_layer_bwd(C.byref(cfgs[l]), C.byref(pp), _ptr(ctx.lowps[l]), _ptr(ctx.xs[l]),
-                                         _ptr(ctx.saved_bufs[l]), dx_out_p, _ptr(lo_a) if have_lo else None,
-                                         _ptr(views[l][B2]) if (l < L - 1 or top_colsum) else None, dx_in_p, _ptr(lo_b),
-                                         _ptr(views[l - 1][B2]) if l > 0 else None, C.byref(gp), _ptr(ws), stream),
-                       f"layer_bwd[{l}]")
-            lo_a, lo_b = lo_b, lo_a
-            have_lo = bf16
-            hand_over(l)
+        top = L
+        for gsize in groups:
+            # a group of one is the layer's own launch; in a larger group the layers run their dX chain only and leave their dW
+            # operands in a block each (the bf16 gradient image a layer read stays alive too: no ping-pong inside a group)
+            dw = mod._dw_buffers(lib, cfgs, top, gsize, dev) if gsize > 1 else None
+            held = []
+            for k, l in enumerate(range(top - 1, top - 1 - gsize, -1)):
+                gp = _lib.LayerPtrs(*[base + 4 * l * per_layer + o for o in offs])
+                pp = mod._param_struct(ctx.params, l)
+                # LN1' of this layer writes the column sums of dx_in directly into the previous layer's b2 gradient
+                # bf16 gradient stream: the fp32 buffer carries the gradient only into the top layer (when no bf16 image came
+                # with it) and out of the bottom one; in between the layers hand each other the bf16 image alone
+                dx_out_p = None if (gs16 and have_lo) else _ptr(dx)
+                dx_in_p = None if (gs16 and l > 0) else _ptr(dx)
+                args = (C.byref(cfgs[l]), C.byref(pp), _ptr(ctx.lowps[l]), _ptr(ctx.xs[l]),
+                        _ptr(ctx.saved_bufs[l]), dx_out_p, _ptr(lo_a) if have_lo else None,
+                        _ptr(views[l][B2]) if (l < L - 1 or top_colsum) else None, dx_in_p, _ptr(lo_b),
+                        _ptr(views[l - 1][B2]) if l > 0 else None, C.byref(gp), _ptr(ws))
+                if dw is None:
+                    _lib.check(lib.avf_layer_bwd(*args, stream), f"layer_bwd[{l}]")
+                    lo_a, lo_b = lo_b, lo_a
+                else:
+                    _lib.check(lib.avf_layer_bwd_dx(*args, _ptr(dw.blocks[k]), dw.descs[k], stream), f"layer_bwd_dx[{l}]")
+                    held.append(lo_a)
+                    lo_a, lo_b = lo_b, torch.empty(lo_bytes, dtype=torch.uint8, device=dev)
+                have_lo = bf16
+            if dw is not None:
+                _lib.check(lib.avf_layers_dw(dw.cfgs, gsize, dw.desc_ptrs, _ptr(dw.ws), dw.ws_bytes, stream), f"layers_dw[{top - gsize}:{top}]")
+            del held
+            for l in range(top - 1, top - 1 - gsize, -1):
+                hand_over(l)
+            top -= gsize
         _check_canaries()
         ctx.saved_bufs = None
         ctx.xs = None
@@ -339,7 +382,7 @@ class Transformer(nn.Module):
     # per-process caches (ctypes structs, device scratch, bf16 weight images): never copied or pickled with the module
     _CACHES = {"_ws": None, "_lowp_bufs": None, "_lowp_ptrs": None, "_lowp_versions": None, "_lowp_ready": False,
                "_seed_dev": None, "_last_seed_t": None}
-    _LAZY_CACHES = ("_pstruct_cache", "_mx_ptr_array", "_flat_cache", "_cfg_cache")  # created on first use
+    _LAZY_CACHES = ("_pstruct_cache", "_mx_ptr_array", "_flat_cache", "_cfg_cache", "_dw_plan_cache", "_dw_buf_cache")  # created on first use
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -447,6 +490,52 @@ class Transformer(nn.Module):
         if self._ws is None or self._ws.numel() - _CANARY < need or self._ws.device != dev:
             self._ws = _alloc_bytes(need, dev)
         return self._ws
+
+    def _dw_plan(self, lib, cfgs) -> List[int]:
+        """group sizes of the deferred weight-gradient launches for this configuration (plan_dw_groups), [1] * depth where
+        the mode keeps them in the layer.  AVF_DW_DEFER=0 switches deferral off (the A/B arm), AVF_DW_GROUP=n forces the
+        group size; both are read per call."""
+        env = (os.environ.get("AVF_DW_DEFER", "1"), os.environ.get("AVF_DW_GROUP", ""))
+        hit = self.__dict__.get("_dw_plan_cache")
+        if hit is not None and hit[0] is cfgs and hit[1] == env:
+            return hit[2]
+        plan = [1] * self.depth
+        tiles, slots = C.c_int(0), C.c_int(0)
+        if env[0] != "0" and lib.avf_layer_dw_defer_ok(C.byref(cfgs[0]), C.byref(tiles), C.byref(slots)):
+            force = int(env[1]) if env[1].strip() else 0
+            plan = plan_dw_groups(self.depth, tiles.value, slots.value, lib.avf_layers_dw_max(), force)
+        self.__dict__["_dw_plan_cache"] = (cfgs, env, plan)
+        return plan
+
+    def _dw_buffers(self, lib, cfgs, top: int, gsize: int, dev):
+        """what a deferred group of layers top-gsize .. top-1 needs: one operand block per layer (shared by the groups of a
+        step: a group's launch has consumed them before the next group writes), the host descriptors, the configurations
+        in launch order and the split-K workspace of the group (none when it runs unsplit)"""
+        cache = self.__dict__.get("_dw_buf_cache")
+        if cache is None or cache["cfgs"] is not cfgs or cache["dev"] != dev:
+            nmax = lib.avf_layers_dw_max()
+            desc_bytes = lib.avf_layer_dw_desc_bytes()
+            block_bytes = lib.avf_layer_dw_block_bytes(C.byref(cfgs[0]))
+            if block_bytes == 0:
+                _lib.check(1, "layer_dw_block_bytes")
+            descs = [C.create_string_buffer(desc_bytes) for _ in range(nmax)]
+            cache = {"cfgs": cfgs, "dev": dev, "blocks": [], "block_bytes": block_bytes, "descs": descs,
+                     "desc_ptrs": (C.c_void_p * nmax)(*[C.addressof(d) for d in descs]), "groups": {}, "ws": None}
+            self.__dict__["_dw_buf_cache"] = cache
+        while len(cache["blocks"]) < gsize:
+            cache["blocks"].append(_alloc_bytes(cache["block_bytes"], dev))
+        grp = cache["groups"].get((top, gsize))
+        if grp is None:
+            grp = _DwGroup()
+            grp.cfgs = (_lib.LayerCfg * gsize)(*[cfgs[l] for l in range(top - 1, top - 1 - gsize, -1)])
+            cache["groups"][(top, gsize)] = grp
+        # (asked on every call: a tuning switch may change the split count; the library checks the size it is given)
+        grp.ws_bytes = lib.avf_layers_dw_workspace_bytes(grp.cfgs, gsize)
+        if grp.ws_bytes and (cache["ws"] is None or cache["ws"].numel() - _CANARY < grp.ws_bytes):
+            cache["ws"] = _alloc_bytes(grp.ws_bytes, dev)
+        grp.blocks, grp.descs, grp.desc_ptrs = cache["blocks"], cache["descs"], cache["desc_ptrs"]
+        grp.ws = cache["ws"] if grp.ws_bytes else None
+        return grp
 
     def _lowp(self, lib, cfg, params, dev, stream):
         """bf16 weight copies (+ transposes) of the fp32 masters.  Refreshed on EVERY forward (an optimizer
