@@ -501,6 +501,32 @@ int avf_clip_autoaugment(const uint8_t* src, uint8_t* dst, int64_t B, int64_t T,
                          void* stream);
 int64_t avf_clip_autoaugment_max_pixels(void);
 
+/* ---- clips assembled on the device from a resident frame bank (dataloader/aff2compdataset.py:122-156; testset.py:84-113) --------
+ * bank uint8 [F, H, W, C] (C in 1..4, no alignment assumed), video_db_nr int32 [F], present uint8 [F] or null (every frame is
+ * present), index int64 [B]: all DEVICE pointers, read by the kernels at run time.  T: clip length, d >= 1: dilation.  Slot t of
+ * sample b is frame a = index[b] - d * (T - 1 - t) of the bank - the last slot is index[b] itself - and it is BLACK (every byte 0)
+ * where a < 0 or a >= F, where video_db_nr[a] != video_db_nr[index[b]], or where present[a] == 0 (the reference's failed decode).
+ * An index[b] outside [0, F) gives an all-black clip and reads nothing of the bank (the reference would raise).  Black is a byte
+ * value: normalised it is lut[c * 256 + 0], and a black frame goes through its AutoAugment slots like any other frame.
+ *
+ * avf_clip_gather:             ONE launch, bank -> dst uint8 [B, T, H, W, C], no alignment assumed (16-byte loads and stores where
+ *                              the source and destination ranges sit alike in their 16-byte chunks, staged through LDS where not).
+ * avf_clip_gather_normalize:   ONE launch, bank -> planes; k, lut, flip, dst, out_dtype and layout as avf_clip_normalize takes them,
+ *                              and the result is that of avf_clip_normalize on the clip of avf_clip_gather.  No uint8 clip is written.
+ * avf_clip_gather_autoaugment: ONE launch, bank -> augmented dst uint8 [B, T, H, W, C]; C, plan and the frame-size limit
+ *                              (avf_clip_autoaugment_max_pixels) as avf_clip_autoaugment takes them, and the result is that of
+ *                              avf_clip_autoaugment on the clip of avf_clip_gather.
+ * dst must not overlap the bank.  Sizes and indices are 64-bit.  Nothing is allocated or synchronised (capturable); every argument
+ * is checked before anything is enqueued. */
+int avf_clip_gather(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index, int64_t F,
+                    int64_t B, int64_t T, int64_t d, int64_t H, int64_t W, int C, uint8_t* dst, void* stream);
+int avf_clip_gather_normalize(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index,
+                              int64_t F, int64_t B, int64_t T, int64_t d, int64_t H, int64_t W, int C, int k, const float* lut,
+                              const uint8_t* flip, void* dst, int out_dtype, int layout, void* stream);
+int avf_clip_gather_autoaugment(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index,
+                                int64_t F, int64_t B, int64_t T, int64_t d, int64_t H, int64_t W, int C, const int32_t* plan,
+                                uint8_t* dst, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

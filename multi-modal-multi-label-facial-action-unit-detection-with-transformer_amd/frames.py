@@ -1,0 +1,182 @@
+"""Clips assembled from a resident frame bank: the last host stage of the video stream, on the device.
+
+The reference's data set builds the clip of a sample on the host (dataloader/aff2compdataset.py:122-156; testset.py:84-113 repeats
+the loop).  With clip length ``T`` (``n_frames``, opts.py:35, default 16) and dilation ``d`` (opts.py:36, default 3):
+
+  * the clip starts black: ``np.zeros((clip_len, H, W, C), uint8)``                                             (122-125)
+  * slot ``t`` of sample ``index`` is frame ``a = index - d * (T - 1 - t)``:
+    ``range(index - T * d + d, index - T * d + d * (T + 1), d)``, whose last entry is ``index`` itself         (45, 126-127)
+  * the slot stays black where ``a < 0``, ``a >= len(self)`` or ``video_db_nr[a] != video_db_nr[index]``        (129-132)
+  * ... and where loading the frame fails: ``try: clip[clip_i, ...] = img / except: pass``                      (142-155)
+  * otherwise it is the frame's bytes
+
+Neighbouring samples share T - 1 of their T frames, so a host-assembled batch carries every frame about T times over the host
+link.  Here the cropped frames stay on the device as one uint8 tensor - the bank - and only ``index [B]`` travels per step.
+
+Black is a byte value, not an output value: normalised, a black pixel is ``lut[c, 0]``, and a black frame goes through its
+AutoAugment slots like any other (autoaugment.py:104-112 loops over every frame).  An ``index`` outside ``[0, F)`` gives an
+all-black clip - this project's definition: the reference would raise, nothing on the device can.
+
+``backend="torch"`` (default) is ATen ops on any device: the table of source frames, ``index_select``, ``where``, then the
+existing modules.  ``backend="hip"`` is one launch of csrc/clip_bank.hip per method.  Both give the same bytes and bits.
+
+Parity: unpinned by a reference fixture (the data set class needs lmdb and cv2, which are not importable here); checked bytewise
+against an independent numpy restatement of the cited lines (tests/frames_util.py).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import ops
+from .augment import ClipAutoAugment, _check_rotate_size
+from .clip import MAX_CHANNELS, ClipFrontEnd
+
+BACKENDS = ("torch", "hip")
+
+
+class FrameBank:
+    """The frames of a data set split on one device: ``frames_u8`` uint8 [F, H, W, C] (C in 1..4), ``video_db_nr`` int32 [F] (the
+    video every frame belongs to; equal numbers need not be neighbours) and ``present`` bool / uint8 [F] or None (0: the frame
+    could not be decoded and is black).  All contiguous, all on the device of ``frames_u8``."""
+
+    def __init__(self, frames_u8: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor] = None):
+        if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+            raise ValueError("frames_u8 must be a uint8 tensor [F, H, W, C]")
+        F, H, W, C = frames_u8.shape
+        if F < 1 or H < 1 or W < 1:
+            raise ValueError(f"the bank needs at least one frame of at least one pixel, got {tuple(frames_u8.shape)}")
+        if not 1 <= C <= MAX_CHANNELS:
+            raise ValueError(f"a frame has 1..{MAX_CHANNELS} channels, got {C}")
+        if not torch.is_tensor(video_db_nr) or video_db_nr.dtype != torch.int32 or tuple(video_db_nr.shape) != (F,):
+            raise ValueError(f"video_db_nr must be an int32 tensor [{F}]")
+        if present is not None and (not torch.is_tensor(present) or present.dtype not in (torch.bool, torch.uint8)
+                                    or tuple(present.shape) != (F,)):
+            raise ValueError(f"present must be None or a bool / uint8 tensor [{F}]")
+        for name, t in (("video_db_nr", video_db_nr), ("present", present)):
+            if t is not None and t.device != frames_u8.device:
+                raise ValueError(f"{name} is on {t.device}, the frames on {frames_u8.device}")
+        for name, t in (("frames_u8", frames_u8), ("video_db_nr", video_db_nr), ("present", present)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        self.frames, self.video_db_nr, self.present = frames_u8, video_db_nr, present
+
+    def __len__(self) -> int:
+        return self.frames.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.frames.device
+
+    @property
+    def frame_shape(self):
+        return tuple(self.frames.shape[1:])
+
+    def to(self, device) -> "FrameBank":
+        return FrameBank(self.frames.to(device), self.video_db_nr.to(device), None if self.present is None else self.present.to(device))
+
+
+class ClipAssembler(nn.Module):
+    """The clips of ``index`` int64 [B] out of a ``FrameBank``, ``clip_len`` frames each, ``dilation`` frames apart, ending at the
+    labelled frame ``index[b]`` (the module docstring states the rule).
+
+    ``source_table(bank, index)`` -> int64 [B, T]: the bank frame of every slot, -1 for a black one.  Plain torch, any device.
+    ``forward(bank, index)`` -> uint8 [B, T, H, W, C], what ``ClipAutoAugment`` and ``ClipFrontEnd`` take.
+    ``normalized(bank, index, front_end, flip=None)`` -> ``front_end(forward(bank, index), flip)``: the planes in the front end's
+    layout, dtype and channel slice.
+    ``augmented(bank, index, plan, augment)`` -> ``augment(forward(bank, index), plan)``: the augmented uint8 clip.
+
+    ``backend="torch"`` (default): ATen ops on any device, then the module that was passed in.  ``backend="hip"``: one launch of
+    csrc/clip_bank.hip per method - no uint8 clip is written by ``normalized``, no plain one by ``augmented`` -, the bank must be
+    on the GPU (no CPU fallback), under ``no_grad``; ``index`` and ``flip`` are read on the device.  Both give the same bytes."""
+
+    def __init__(self, clip_len: int = 16, dilation: int = 3, backend: str = "torch"):
+        super().__init__()
+        if backend not in BACKENDS:
+            raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
+        for name, v in (("clip_len", clip_len), ("dilation", dilation)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer of at least 1, got {v!r}")
+        self.clip_len, self.dilation, self.backend = clip_len, dilation, backend
+
+    def _check(self, bank: FrameBank, index: torch.Tensor, table_only: bool = False) -> None:
+        if not isinstance(bank, FrameBank):
+            raise ValueError(f"bank must be a FrameBank, got {type(bank).__name__}")
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+            raise ValueError("index must be an int64 tensor [B] with B >= 1")
+        if index.device != bank.device:
+            raise ValueError(f"index is on {index.device}, the bank on {bank.device}")
+        if self.backend == "hip" and not table_only and not bank.frames.is_cuda:
+            raise RuntimeError("ClipAssembler (HIP) needs its bank on the MI355X; there is no CPU fallback - "
+                               "use backend='torch' on the host")
+
+    def source_table(self, bank: FrameBank, index: torch.Tensor) -> torch.Tensor:
+        self._check(bank, index, table_only=True)
+        F, T, d = len(bank), self.clip_len, self.dilation
+        label_ok = (index >= 0) & (index < F)
+        a = index[:, None] - d * (T - 1 - torch.arange(T, device=index.device))[None, :]          # aff2compdataset.py:126-127
+        inside = (a >= 0) & (a < F) & label_ok[:, None]
+        a_safe, label_safe = torch.where(inside, a, torch.zeros_like(a)), torch.where(label_ok, index, torch.zeros_like(index))
+        ok = inside & (bank.video_db_nr[a_safe] == bank.video_db_nr[label_safe][:, None])          # :129
+        if bank.present is not None:
+            ok = ok & (bank.present[a_safe] != 0)                                                  # :142-155
+        return torch.where(ok, a, torch.full_like(a, -1))
+
+    def _gather(self, bank: FrameBank, index: torch.Tensor) -> torch.Tensor:
+        table = self.source_table(bank, index)
+        B, T = table.shape
+        black = (table < 0).view(B, T, 1, 1, 1)
+        clip = bank.frames.index_select(0, table.clamp(min=0).view(-1)).view(B, T, *bank.frame_shape)
+        return torch.where(black, torch.zeros((), dtype=torch.uint8, device=clip.device), clip)
+
+    def forward(self, bank: FrameBank, index: torch.Tensor) -> torch.Tensor:
+        self._check(bank, index)
+        if self.backend == "hip":
+            with torch.no_grad():
+                return ops.clip_gather(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len, self.dilation)
+        return self._gather(bank, index)
+
+    def normalized(self, bank: FrameBank, index: torch.Tensor, front_end: ClipFrontEnd,
+                   flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check(bank, index)
+        if not isinstance(front_end, ClipFrontEnd):
+            raise ValueError(f"front_end must be a ClipFrontEnd, got {type(front_end).__name__}")
+        if self.backend != "hip":
+            return front_end(self._gather(bank, index), flip)
+        C = bank.frame_shape[-1]
+        if C != front_end.in_channels:
+            raise ValueError(f"the bank has {C} channels, mean / std have {front_end.in_channels}")
+        flip = front_end._flags(flip, index.numel(), bank.device)
+        if front_end.lut.device != bank.device:
+            raise ValueError(f"the front end is on {front_end.lut.device}, the bank on {bank.device}")
+        with torch.no_grad():
+            return ops.clip_gather_normalize(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len,
+                                             self.dilation, front_end.lut, front_end.channels, flip, front_end.layout,
+                                             front_end.out_dtype)
+
+    def augmented(self, bank: FrameBank, index: torch.Tensor, plan: torch.Tensor, augment: ClipAutoAugment) -> torch.Tensor:
+        self._check(bank, index)
+        if not isinstance(augment, ClipAutoAugment):
+            raise ValueError(f"augment must be a ClipAutoAugment, got {type(augment).__name__}")
+        if self.backend != "hip":
+            return augment(self._gather(bank, index), plan)
+        if augment.backend != "hip":
+            raise ValueError("ClipAssembler (HIP) runs the policy in its own launch: augment must be ClipAutoAugment(backend='hip')")
+        B, T = index.numel(), self.clip_len
+        H, W, C = bank.frame_shape
+        if C not in (3, 4):
+            raise ValueError(f"the bank has {C} channels; the policy transforms RGB (C = 3) or RGB + mask (C = 4)")
+        if not torch.is_tensor(plan) or plan.dtype != torch.int32:
+            raise ValueError("plan must be an int32 tensor (draw_plan / make_plan)")
+        if tuple(plan.shape) != (B, T, 2, 8):
+            raise ValueError(f"plan must be [{B}, {T}, 2, 8] for these clips, got {tuple(plan.shape)}")
+        if not plan.is_cuda:
+            _check_rotate_size(plan, H, W)
+            plan = plan.to(bank.device, non_blocking=True)
+        elif plan.device != bank.device:
+            raise ValueError(f"plan is on {plan.device}, the bank on {bank.device}")
+        with torch.no_grad():
+            return ops.clip_gather_autoaugment(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len,
+                                               self.dilation, plan.contiguous())

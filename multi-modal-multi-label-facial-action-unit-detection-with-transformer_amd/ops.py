@@ -820,6 +820,70 @@ def clip_autoaugment(clip: torch.Tensor, plan: torch.Tensor, out: Optional[torch
     return out
 
 
+def _bank_args(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor):
+    """the tensors that the avf_clip_gather* entry points share: bank uint8 [F, H, W, C], video_db_nr int32 [F], present uint8 /
+    bool [F] or None, index int64 [B], contiguous and on one device"""
+    _need_cuda(bank, video_db_nr, present, index)
+    assert bank.dim() == 4 and bank.dtype == torch.uint8 and bank.is_contiguous()
+    F = bank.shape[0]
+    assert video_db_nr.dtype == torch.int32 and video_db_nr.is_contiguous() and tuple(video_db_nr.shape) == (F,)
+    if present is not None:
+        assert present.dtype in (torch.bool, torch.uint8) and present.is_contiguous() and tuple(present.shape) == (F,)
+    assert index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1 and index.numel() >= 1
+    for t in (video_db_nr, present, index):
+        assert t is None or t.device == bank.device
+    return F, index.numel()
+
+
+def clip_gather(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor, T: int,
+                d: int) -> torch.Tensor:
+    """avf_clip_gather, one launch: bank uint8 [F, H, W, C] -> the clips of index int64 [B], uint8 [B, T, H, W, C].  Slot t of
+    sample b is frame index[b] - d * (T - 1 - t), black outside the bank, in another video (video_db_nr int32 [F]) or where
+    present (uint8 / bool [F] or None) is 0.  Everything is read on the device (no host synchronisation)."""
+    F, B = _bank_args(bank, video_db_nr, present, index)
+    _, H, W, Cn = bank.shape
+    out = torch.empty(B, int(T), H, W, Cn, dtype=torch.uint8, device=bank.device)
+    _lib.check(_lib.load().avf_clip_gather(_ptr(bank), _ptr(video_db_nr), _ptr(present), _ptr(index), F, B, int(T), int(d), H, W, Cn,
+                                           _ptr(out), _stream()), "clip_gather")
+    return out
+
+
+def clip_gather_normalize(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor,
+                          T: int, d: int, lut: torch.Tensor, k: Optional[int] = None, flip: Optional[torch.Tensor] = None,
+                          layout: str = "cthw", out_dtype=torch.float32) -> torch.Tensor:
+    """avf_clip_gather_normalize, one launch: clip_normalize(clip_gather(...), lut, k, flip, layout, out_dtype) without the
+    uint8 clip in between."""
+    F, B = _bank_args(bank, video_db_nr, present, index)
+    _need_cuda(lut, flip)
+    _, H, W, Cn = bank.shape
+    T, k = int(T), Cn if k is None else int(k)
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (Cn, 256)
+    if flip is not None:
+        assert flip.dtype in (torch.bool, torch.uint8) and flip.is_contiguous() and tuple(flip.shape) == (B,)
+    dt, lay = torch_dtype(out_dtype), CLIP_LAYOUTS[layout]
+    shape = (B, k, T, H, W) if layout == "cthw" else (B, T, k, H, W)
+    out = torch.empty(shape, dtype=dt, device=bank.device)
+    _lib.check(_lib.load().avf_clip_gather_normalize(_ptr(bank), _ptr(video_db_nr), _ptr(present), _ptr(index), F, B, T, int(d), H, W,
+                                                     Cn, k, _ptr(lut), _ptr(flip), _ptr(out), avf_dtype(dt), lay, _stream()),
+               "clip_gather_normalize")
+    return out
+
+
+def clip_gather_autoaugment(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor,
+                            T: int, d: int, plan: torch.Tensor) -> torch.Tensor:
+    """avf_clip_gather_autoaugment, one launch: clip_autoaugment(clip_gather(...), plan) without the plain clip in between;
+    plan int32 [B, T, 2, 8] on the device."""
+    F, B = _bank_args(bank, video_db_nr, present, index)
+    _need_cuda(plan)
+    _, H, W, Cn = bank.shape
+    T = int(T)
+    assert plan.dtype == torch.int32 and plan.is_contiguous() and tuple(plan.shape) == (B, T, 2, 8)
+    out = torch.empty(B, T, H, W, Cn, dtype=torch.uint8, device=bank.device)
+    _lib.check(_lib.load().avf_clip_gather_autoaugment(_ptr(bank), _ptr(video_db_nr), _ptr(present), _ptr(index), F, B, T, int(d), H,
+                                                       W, Cn, _ptr(plan), _ptr(out), _stream()), "clip_gather_autoaugment")
+    return out
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
