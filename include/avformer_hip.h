@@ -185,6 +185,26 @@ size_t avf_gemm_nt_ws_workspace_bytes(int64_t M, int64_t N);
  * aligned operands and no dropout); avf_gemm_nt_ws itself takes every shape the kernel can run */
 int avf_gemm_nt_ws_dispatch(int64_t M, int64_t N, int64_t K, int epilogue, int c_dtype);
 int avf_pack_weight_ws(const void* w_bf16, int64_t ldw, int64_t rows, int64_t cols, void* out, void* stream);
+
+/* Test plumbing for the tiled bf16 NT GEMM: C[M,N] = epilogue(A[M,K] B[N,K]^T) as avf_gemm(AVF_BF16, 0, 1, ...) runs it, plus
+ * the two things only a layer call could ask of that kernel family so far:
+ *   colsum   (nullable) fp32 [N]: column sums over the rows of the values behind the stored C (fp32, before their rounding to
+ *            c_dtype); needs workspace >= avf_gemm_nt_ws_workspace_bytes(M, N).
+ *   dropout  (seed_lo, seed_hi, layer_index, site, p) name a dropout site exactly as avf_dropout_factors does, element index
+ *            m * N + n; p == 0 is no dropout.  With f = those factors: BIAS_RES C = (acc + bias) * f + residual, BIAS_GELU
+ *            aux = acc + bias (unmasked), C = gelu(aux) * f, DGELU C = acc * f * gelu'(aux).  Not on AVF_EPI_NONE.
+ * residual and aux are stored in C's type.  Never the weight-stationary kernel, never an MX-FP8 image.
+ * avf_gemm_nt_plan: which kernel that call runs, decided by the function the launcher itself acts on.  Pointers are replaced
+ * by their presence (every operand 16-byte aligned).  *kind: 0 = the register-staged kernel (K % 64 != 0; *tile = -1), 1 = the
+ * tiled LDS-DMA kernel; *tile: the tile configuration's id; *lean: the LEAN code of the instantiation (0 = general epilogue,
+ * 1 = lean, 2 = lean with column sums, + 4 = with the dropout site); *wpf: 1 when the launch does the weight warm-up. */
+int avf_gemm_nt_ex(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                   int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux, int64_t ldaux,
+                   void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site, float p,
+                   void* stream);
+int avf_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int c_dtype, int epilogue,
+                     int has_bias, int64_t ldres, int64_t ldaux, int want_colsum, float p, int* kind, int* tile, int* lean,
+                     int* wpf);
 int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B_packed, void* C, int64_t ldc,
                    int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux, int64_t ldaux,
                    void* workspace, float* colsum, void* mx_q, void* mx_s, void* stream);

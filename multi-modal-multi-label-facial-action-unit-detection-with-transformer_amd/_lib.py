@@ -82,6 +82,10 @@ SIGNATURES = {
     "avf_gemm_nt_ws_workspace_bytes": (_sz, [_i64, _i64]),
     "avf_gemm_nt_ws_dispatch": (_int, [_i64, _i64, _i64, _int, _int]),
     "avf_pack_weight_ws": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "avf_gemm_nt_ex": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                              C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
+    "avf_gemm_nt_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _i64, _i64, _int, _f, C.POINTER(C.c_int),
+                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_gemm_nt_ws": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                               _vp]),
     "avf_gemm_tn_group_workspace_bytes": (_sz, [_int, _i64, _vp, _vp]),

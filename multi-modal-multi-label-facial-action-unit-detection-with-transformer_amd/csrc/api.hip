@@ -270,6 +270,47 @@ extern "C" int avf_gemm_nt_ws_dispatch(int64_t M, int64_t N, int64_t K, int epil
   a.Bp = aligned; a.ws_force = 0; a.mx_q = nullptr; a.mx_s = nullptr;
   return gemm_bf16_nt_ws_preferred(a) ? 1 : 0;
 }
+// ---- the tiled / register-staged bf16 NT GEMM with everything a layer can ask of it (test plumbing) ----
+static int fill_nt_ex(GemmArgs* a, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                      int64_t ldc, int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux,
+                      int64_t ldaux, void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site,
+                      float p, const char* who) {
+  AVF_REQUIRE(A && B && C, "%s: null pointer", who);
+  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "%s: bad dropout site %d / p %g", who, site, (double)p);
+  a->dtype = AVF_BF16; a->transA = 0; a->transB = 1;
+  a->M = M; a->N = N; a->K = K;
+  a->A = A; a->lda = lda; a->B = B; a->ldb = ldb; a->C = C; a->ldc = ldc;
+  a->c_dtype = c_dtype; a->epilogue = epilogue; a->bias = bias; a->residual = residual; a->ldres = ldres;
+  a->aux = aux; a->ldaux = ldaux; a->workspace = workspace; a->colsum = colsum;
+  a->drop = p > 0.f ? make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site) : kNoDrop;
+  a->defer_fold = nullptr;
+  a->Bp = nullptr; a->ws_force = 0; a->mx_q = nullptr; a->mx_s = nullptr;
+  return 0;
+}
+extern "C" int avf_gemm_nt_ex(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                              int64_t ldc, int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres,
+                              void* aux, int64_t ldaux, void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi,
+                              int layer_index, int site, float p, void* stream) {
+  GemmArgs a;
+  AVF_TRY(fill_nt_ex(&a, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, epilogue, bias, residual, ldres, aux, ldaux, workspace, colsum,
+                     seed_lo, seed_hi, layer_index, site, p, "gemm_nt_ex"));
+  return gemm_bf16_nt(a, (hipStream_t)stream);
+}
+extern "C" int avf_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int c_dtype, int epilogue,
+                                int has_bias, int64_t ldres, int64_t ldaux, int want_colsum, float p, int* kind, int* tile,
+                                int* lean, int* wpf) {
+  AVF_REQUIRE(kind && tile && lean && wpf, "gemm_nt_plan: null pointer");
+  void* aligned = (void*)(uintptr_t)256;  // never dereferenced: the predicates look at null-ness and alignment only
+  GemmArgs a;
+  AVF_TRY(fill_nt_ex(&a, M, N, K, aligned, lda, aligned, ldb, aligned, ldc, c_dtype, epilogue, has_bias ? (const float*)aligned : nullptr,
+                     epilogue == AVF_EPI_BIAS_RES ? aligned : nullptr, ldres,
+                     (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) ? aligned : nullptr, ldaux,
+                     want_colsum ? aligned : nullptr, want_colsum ? (float*)aligned : nullptr, 1u, 0u, 0, 0, p, "gemm_nt_plan"));
+  NtPlan pl;
+  AVF_TRY(gemm_bf16_nt_plan(a, &pl));
+  *kind = pl.kind; *tile = pl.tile; *lean = pl.lean; *wpf = pl.wpf;
+  return 0;
+}
 extern "C" int avf_pack_weight_ws(const void* w_bf16, int64_t ldw, int64_t rows, int64_t cols, void* out, void* stream) {
   return pack_ws(w_bf16, ldw, rows, cols, out, (hipStream_t)stream);
 }

@@ -508,6 +508,16 @@ size_t gemm_f32_ws(int64_t M, int64_t N, int64_t K);  // split-K slabs of skinny
 void set_f32_arith(int mode);
 int get_f32_arith();
 int gemm_bf16_nt(const GemmArgs& a, hipStream_t s);
+// Which kernel gemm_bf16_nt runs for a call that does not go to the weight-stationary kernel: the launcher acts on exactly
+// this (nt_plan_bf16 in gemm_bf16.hip), gemm_bf16_nt_plan answers a test's or a profile tool's question from the same function.
+struct NtPlan {
+  int kind;   // 0 = gemm_bf16_nt_kernel (register-staged, K % 64 != 0), 1 = gemm_bf16_nt_glds_kernel
+  int tile;   // kind 1: id of the kNtTiles entry that runs (-1 for kind 0)
+  int index;  // kind 1: its index in kNtTiles
+  int lean;   // kind 1: LEAN code of the instantiation (0 = the general epilogue)
+  int wpf;    // kind 1: 1 when the launch does the weight warm-up
+};
+int gemm_bf16_nt_plan(const GemmArgs& a, NtPlan* out);  // pointers are looked at for null-ness and alignment only
 int gemm_bf16_tn(const GemmArgs& a, hipStream_t s);
 // MX-FP8 NT GEMM (gemm_mx8.hip): A, B are e4m3 byte images (lda, ldb in bytes), scales [rows][K/32] E8M0 bytes
 // mx_q / mx_s (optional, BIAS_GELU only): also write the MX-FP8 image of C ([M,N] e4m3 + [M,N/32] E8M0)

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(NtParam
 }
 
 template <int EPI, typename CT, int WM, int WN, int MI, int NI, int NS, int LEAN = 0>
-int launch_nt_glds(const NtParams& p, hipStream_t s, int* part_rows, TimingScope* ts) {
+int launch_nt_glds(const NtParams& p, int wpf, hipStream_t s, int* part_rows, TimingScope* ts) {
   constexpr int BMT = 16 * MI * WM, BNT = 16 * NI * WN;
   constexpr int SMEM = NS * (BMT + BNT) * 128;
   static_assert(NS >= 2 && NS <= 8 && SMEM <= 160 * 1024, "stage count / LDS budget");
@@ -285,17 +285,6 @@ int launch_nt_glds(const NtParams& p, hipStream_t s, int* part_rows, TimingScope
     shape_log("gemm_bf16_nt,gemm_bf16_nt_glds_kernel<%d, %s, %d, %d, %d, %d, %d, %d>,%d,%d,%d,%d,%d,%.0f,%.0f", EPI,
               sizeof(CT) == 4 ? "float" : "bf16", WM, WN, MI, NI, NS, LEAN, nwg, p.M, p.N, p.K,
               EPI, 2.0 * p.M * p.N * p.K, nt_algorithmic_bytes(p.M, p.N, p.K, 2.0, sizeof(CT), EPI, false));
-  // Weight warm-up (see the kernel): on for launches that leave workgroup slots of the chip empty (C2: 432 workgroups on 512
-  // slots).  It turns stall time into MFMA-dense time, and the replayed step runs against the package power limit (amd-smi: PPT
-  // violation active during replay, shader clock 2.15 - 2.37 GHz of 2.4): on the full launches of C3 the tiled shapes ran 6 -
-  // 12 % shorter and the firmware lowered the clock of the WHOLE step by 6 % (2305 -> 2155 MHz) - C3 +3.0 %, C4 +0.5 %,
-  // C5 +0.3 % in wall time, C2 -1.9 ... -3.8 % (profiles/r05_weight_warmup.txt).
-  static const int wpf_env = tuning_int("AVF_NT_WPF", 1);  // A/B aid: 0 = never, 2 = every launch
-  // the 8-wave tiles only: on the small-M tile (four workgroups of 8 K-steps per CU, the reference's 17-token layers) the warm-up
-  // loads queue in front of a short K loop's own - TFormer 133 -> 140 us per layer
-  constexpr int kSlots = (WM * WN == 8) ? kWorkgroupSlots : 0;
-  const int wpf = (wpf_env && (wpf_env == 2 || nwg < kSlots) && p.ldb == p.K && p.K >= TK) ? 1 : 0;  // (K >= TK: the K loop's
-                                                                                                       //  first wait retires the loads)
   launch_in_scope(ts, gemm_bf16_nt_glds_kernel<EPI, CT, WM, WN, MI, NI, NS, LEAN>, dim3(nwg), dim3(WM * WN * 64), SMEM, s, p,
                   tiles_n, nwg, wpf);
   return 0;
@@ -307,24 +296,53 @@ int launch_nt_glds(const NtParams& p, hipStream_t s, int* part_rows, TimingScope
 constexpr bool nt_lean_exists(int epi, int lean) {
   return lean == 0 || (((lean & 3) != 2 || epi == AVF_EPI_DGELU) && (!(lean & 4) || epi != AVF_EPI_NONE));
 }
+int nt_wpf_env() {
+  static const int on = tuning_int("AVF_NT_WPF", 1);  // A/B aid: 0 = never, 2 = every launch
+  return on;
+}
+// The one place that decides which NT kernel a call runs and how: register-staged or tiled, the tile, the LEAN code and the
+// weight warm-up.  gemm_bf16_nt launches what this returns; gemm_bf16_nt_plan reports it.
 template <int EPI, typename CT>
-int launch_nt_glds_any(const NtParams& p, hipStream_t s, int* part_rows, TimingScope* ts) {
+NtPlan nt_plan_bf16(const NtParams& p) {
+  NtPlan pl = {0, -1, -1, 0, 0};
+  if (p.K % TK != 0) return pl;  // global->register->LDS staging copes with a ragged last K-step, the LDS-DMA does not
+  pl.kind = 1;
   const int tile = pick_nt_tile_bf16(p.M, p.N, p.K), ti = nt_tile_index(tile);
+  const NtTile& t = kNtTiles[ti];
+  pl.tile = t.id;
+  pl.index = ti;
   // The instantiations are (tile, LEAN): every tile with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every epilogue),
   // 5 (every fused epilogue) and 2, 6 (DGELU).  The lean epilogue runs when nothing asks for the general one's options (and
   // never on an id that only runs as tile 2 because the table does not hold it).
   int lean = (p.cs_partial ? 2 : 1) + (p.drop.thresh16 ? 4 : 0);
-  if (kNtTiles[ti].id != tile || !kNtTiles[ti].lean() || !nt_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(p, kNtTiles[ti].bn(), false, /*drop_ok=*/true))
+  if (t.id != tile || !t.lean() || !nt_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(p, t.bn(), false, /*drop_ok=*/true))
     lean = 0;
-  return with_nt_tile(ti, [&](auto ic) {
+  pl.lean = lean;
+  // Weight warm-up (see the kernel): on for launches that leave workgroup slots of the chip empty (C2: 432 workgroups on 512
+  // slots).  It turns stall time into MFMA-dense time, and the replayed step runs against the package power limit (amd-smi: PPT
+  // violation active during replay, shader clock 2.15 - 2.37 GHz of 2.4): on the full launches of C3 the tiled shapes ran 6 -
+  // 12 % shorter and the firmware lowered the clock of the WHOLE step by 6 % (2305 -> 2155 MHz) - C3 +3.0 %, C4 +0.5 %,
+  // C5 +0.3 % in wall time, C2 -1.9 ... -3.8 % (profiles/r05_weight_warmup.txt).
+  const int wpf_env = nt_wpf_env();
+  // the 8-wave tiles only: on the small-M tile (four workgroups of 8 K-steps per CU, the reference's 17-token layers) the warm-up
+  // loads queue in front of a short K loop's own - TFormer 133 -> 140 us per layer
+  const int kSlots = (t.WM * t.WN == 8) ? kWorkgroupSlots : 0;
+  const int nwg = (int)(ceil_div(p.M, t.bm()) * ceil_div(p.N, t.bn()));
+  pl.wpf = (wpf_env && (wpf_env == 2 || nwg < kSlots) && p.ldb == p.K && p.K >= TK) ? 1 : 0;  // (K >= TK: the K loop's
+                                                                                                       //  first wait retires the loads)
+  return pl;
+}
+template <int EPI, typename CT>
+int launch_nt_glds_any(const NtParams& p, const NtPlan& pl, hipStream_t s, int* part_rows, TimingScope* ts) {
+  return with_nt_tile(pl.index, [&](auto ic) {
     const auto launch = [&](auto lc) {
       constexpr NtTile t = kNtTiles[decltype(ic)::value];
       constexpr int LEAN = decltype(lc)::value;
       if constexpr (nt_lean_exists(EPI, LEAN) && (LEAN == 0 || t.lean()))
-        return launch_nt_glds<EPI, CT, t.WM, t.WN, t.MI, t.NI, t.NS, LEAN>(p, s, part_rows, ts);
+        return launch_nt_glds<EPI, CT, t.WM, t.WN, t.MI, t.NI, t.NS, LEAN>(p, pl.wpf, s, part_rows, ts);
       else AVF_REQUIRE(false, "gemm_bf16_nt: no lean instantiation %d of tile %d (internal error)", LEAN, t.id);
     };
-    switch (lean) {
+    switch (pl.lean) {
       case 1: return launch(int_c<1>{});
       case 2: return launch(int_c<2>{});
       case 5: return launch(int_c<5>{});
@@ -917,7 +935,7 @@ int gemm_bf16_nt(const GemmArgs& a, hipStream_t s) {
     return finish_colsum(a, (float*)a.workspace, ws_rows, s);
   }
   const NtParams p = nt_params_from(a);  // (mxq is null here: an image of C went to the persistent kernel above)
-  const bool dma = (a.K % TK == 0);
+  const bool dma = (a.K % TK == 0);  // (nt_plan_bf16's first decision; here for the workspace check below)
   int part_rows = (int)grid.y * 2;  // register-staged kernel: 2 wave rows per 128-row tile
   if (a.colsum) {
     AVF_REQUIRE(a.workspace, "gemm_bf16_nt: column-sum workspace missing");
@@ -932,13 +950,28 @@ int gemm_bf16_nt(const GemmArgs& a, hipStream_t s) {
     return with_c_type(a.c_dtype, "gemm_bf16_nt", [&](auto ct) {
       constexpr int E = decltype(epi)::value;
       using CT = decltype(ct);
-      if (dma) return launch_nt_glds_any<E, CT>(p, s, &part_rows, &ts);
+      const NtPlan pl = nt_plan_bf16<E, CT>(p);
+      if (pl.kind) return launch_nt_glds_any<E, CT>(p, pl, s, &part_rows, &ts);
       launch_in_scope(&ts, gemm_bf16_nt_kernel<E, CT>, grid, dim3(256), 0, s, p);
       return 0;
     });
   }));
   AVF_TRY(check_launch("gemm_bf16_nt_kernel"));
   return finish_colsum(a, p.cs_partial, part_rows, s);
+}
+
+int gemm_bf16_nt_plan(const GemmArgs& a, NtPlan* out) {
+  AVF_REQUIRE(out && a.M > 0 && a.N > 0 && a.K > 0 && a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31),
+              "gemm_bf16_nt_plan: bad arguments");
+  AVF_REQUIRE(!((a.ws_force || a.mx_q) ? gemm_bf16_nt_ws_ok(a) : gemm_bf16_nt_ws_preferred(a)),
+              "gemm_bf16_nt_plan: this call runs on the weight-stationary kernel");
+  const NtParams p = nt_params_from(a);
+  return with_epilogue(a.epilogue, "gemm_bf16_nt_plan", [&](auto epi) {
+    return with_c_type(a.c_dtype, "gemm_bf16_nt_plan", [&](auto ct) {
+      *out = nt_plan_bf16<decltype(epi)::value, decltype(ct)>(p);
+      return 0;
+    });
+  });
 }
 
 int gemm_bf16_tn(const GemmArgs& a, hipStream_t s) {

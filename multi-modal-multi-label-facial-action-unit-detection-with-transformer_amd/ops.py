@@ -209,6 +209,78 @@ def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool 
     return c
 
 
+def _row_view(name: str, t: torch.Tensor, rows: int, cols: int, dtype) -> torch.Tensor:
+    """a [rows, cols] operand of gemm_nt_ex, used in place: its row stride is its leading dimension"""
+    if not (t.dim() == 2 and tuple(t.shape) == (rows, cols) and t.stride(1) == 1 and t.stride(0) >= cols and t.dtype == dtype):
+        raise ValueError(f"gemm_nt_ex: {name} must be a [{rows}, {cols}] {dtype} tensor or row-strided view of one "
+                         f"(got {tuple(t.shape)}, strides {t.stride()}, {t.dtype})")
+    return t
+
+
+def gemm_nt_plan(M: int, N: int, K: int, out_dtype=torch.bfloat16, epilogue: int = EPI_NONE, bias: bool = True,
+                 want_colsum: bool = False, p: float = 0.0, lda: Optional[int] = None, ldb: Optional[int] = None,
+                 ldc: Optional[int] = None, ldres: Optional[int] = None, ldaux: Optional[int] = None) -> dict:
+    """Which kernel ``gemm_nt_ex`` runs for these arguments (avf_gemm_nt_plan; 16-byte aligned operands assumed):
+    dict(kind = 0 register-staged | 1 tiled, tile = the tile id or -1, lean = the LEAN code, wpf = weight warm-up on).
+    Leading dimensions default to the dense ones."""
+    out = [C.c_int(-1) for _ in range(4)]
+    _lib.check(_lib.load().avf_gemm_nt_plan(int(M), int(N), int(K), int(K if lda is None else lda), int(K if ldb is None else ldb),
+                                            int(N if ldc is None else ldc), avf_dtype(torch_dtype(out_dtype)), int(epilogue),
+                                            int(bool(bias)), int(N if ldres is None else ldres), int(N if ldaux is None else ldaux),
+                                            int(bool(want_colsum)), float(p), *[C.byref(o) for o in out]), "gemm_nt_plan")
+    kind, tile, lean, wpf = (o.value for o in out)
+    return dict(kind=kind, tile=tile, lean=lean, wpf=bool(wpf))
+
+
+def gemm_nt_ex(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, out_dtype=None, epilogue: int = EPI_NONE,
+               bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,
+               want_colsum: bool = False, drop=None):
+    """C = epilogue(A W^T) on the tiled / register-staged bf16 NT kernels (avf_gemm_nt_ex), with the column sums and the
+    dropout site a layer call can ask of them.  a [M, K], w [N, K] bf16; out / residual / aux [M, N] in C's type; all five may
+    be row-strided views (leading dimension = row stride).  EPI_BIAS_GELU writes aux (made here when not given), EPI_DGELU
+    reads it.  drop: (seed, layer, site, p) as ops.dropout_factors takes them, or None.
+    Returns (C, aux or None, column sums or None, plan) with plan = gemm_nt_plan of exactly this call."""
+    _need_cuda(a, w, out, bias, residual, aux)
+    lib = _lib.load()
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1]:
+        raise ValueError(f"gemm_nt_ex: a is [M, K] and w is [N, K] (got {tuple(a.shape)}, {tuple(w.shape)})")
+    M, K = a.shape
+    N = w.shape[0]
+    a = _row_view("a", a, M, K, torch.bfloat16)
+    w = _row_view("w", w, N, K, torch.bfloat16)
+    cdt = out.dtype if out is not None else (torch_dtype(out_dtype) if out_dtype is not None else torch.bfloat16)
+    if cdt not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"gemm_nt_ex: C is bf16 or fp32, not {cdt}")
+    c = _row_view("out", out, M, N, cdt) if out is not None else torch.empty((M, N), dtype=cdt, device=a.device)
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,) or not bias.is_contiguous()):
+        raise TypeError("gemm_nt_ex: bias is a contiguous fp32 [N]")
+    if (residual is not None) != (epilogue == EPI_BIAS_RES):
+        raise ValueError("gemm_nt_ex: a residual goes with EPI_BIAS_RES, and only with it")
+    if epilogue == EPI_DGELU and aux is None:
+        raise ValueError("gemm_nt_ex: EPI_DGELU reads aux, the saved pre-activation")
+    if epilogue in (EPI_NONE, EPI_BIAS_RES) and aux is not None:
+        raise ValueError("gemm_nt_ex: aux goes with EPI_BIAS_GELU / EPI_DGELU only")
+    if epilogue == EPI_BIAS_GELU and aux is None:
+        aux = torch.empty((M, N), dtype=cdt, device=a.device)
+    if residual is not None:
+        residual = _row_view("residual", residual, M, N, cdt)
+    if aux is not None:
+        aux = _row_view("aux", aux, M, N, cdt)
+    seed, layer, site, p = drop if drop is not None else (0, 0, 0, 0.0)
+    cs = torch.empty(N, dtype=torch.float32, device=a.device) if want_colsum else None
+    ws = _bytes(lib.avf_gemm_nt_ws_workspace_bytes(M, N), a.device) if want_colsum else None
+    ldres = residual.stride(0) if residual is not None else N
+    ldaux = aux.stride(0) if aux is not None else N
+    plan = gemm_nt_plan(M, N, K, cdt, epilogue, bias is not None, want_colsum, p, a.stride(0), w.stride(0), c.stride(0), ldres, ldaux)
+    for name, t in (("a", a), ("w", w), ("out", c), ("bias", bias), ("residual", residual), ("aux", aux)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"gemm_nt_ex: {name} must be 16-byte aligned")
+    _lib.check(lib.avf_gemm_nt_ex(M, N, K, _ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(c), c.stride(0), avf_dtype(cdt),
+                                  int(epilogue), _ptr(bias), _ptr(residual), ldres, _ptr(aux), ldaux, _ptr(ws), _ptr(cs),
+                                  seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, layer, site, float(p), _stream()), "gemm_nt_ex")
+    return c, aux, cs, plan
+
+
 def pack_ws(w: torch.Tensor) -> torch.Tensor:
     """Fragment-major image of a bf16 weight [rows % 256 == 0, 512] for gemm_ws (avf_pack_weight_ws)."""
     _need_cuda(w)

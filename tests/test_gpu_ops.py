@@ -189,6 +189,9 @@ def test_gemm_f32_bf16x3_kernel_implements_the_emulated_arithmetic(ops, ta, tb):
 @pytest.mark.parametrize("dtype,M,N,K", [(torch.float32, 200, 136, 96), (torch.bfloat16, 200, 136, 96),
                                          (torch.bfloat16, 301, 260, 1088), (torch.bfloat16, 8200, 520, 64)])
 def test_gemm_epilogues(ops, f32_arith, dtype, M, N, K):
+    """the four epilogues through avf_gemm, norm-wise.  The bf16 shapes reach three variants of the NT family (avf_gemm_nt_plan):
+    200x136x96 the register-staged kernel, 301x260x1088 tile 6, 8200x520x64 tile 5 with the general epilogue.  The element-wise
+    matrix over every kernel, tile, LEAN code, epilogue, C type and dropout site lives in tests/test_gpu_gemm_nt.py."""
     if dtype != torch.float32 and f32_arith == "f32":
         pytest.skip("the arithmetic switch only concerns fp32 operands")
     g = torch.Generator().manual_seed(11)
@@ -236,6 +239,9 @@ def test_gemm_bf16_operands_fp32_outputs_keep_aux_in_fp32(ops, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(8, 8, 8), (64, 128, 64), (200, 136, 96), (384, 1536, 512), (1000, 48, 40),
                                    (1000, 512, 1024), (301, 132, 1088), (8200, 1024, 128)])  # 96x128 / 128x128x8w tiles
 def test_gemm_bf16_nt(ops, M, N, K):
+    """EPI_NONE only.  By avf_gemm_nt_plan the shapes reach: K = 8, 96, 40 the register-staged kernel; 64x128x64, 384x1536x512,
+    1000x512x1024 and 301x132x1088 tile 6; 8200x1024x128 tile 2 with the lean epilogue.  Every other variant, element by element
+    against fp64: tests/test_gpu_gemm_nt.py."""
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g).to(torch.bfloat16)
     b = torch.randn(N, K, generator=g).to(torch.bfloat16)
