@@ -485,6 +485,34 @@ int avf_mel_power(const float* audio, int64_t rows, int64_t samples, const float
 int avf_mel_db_norm(float* mel, const uint32_t* peak, int64_t rows, int n_mels, int64_t frames, int rows_per_clip, double top_db,
                     double mean, double std, void* stream);
 
+/* ---- audio windows from a resident waveform bank (dataloader/aff2compdataset.py:214-247; testset.py:164-198) --------------
+ * wave: the wavs of a data set split, one after the other, `total` elements of fp32 (wave_dtype 0) or int16 (wave_dtype 1; a
+ * sample x is worth x * 2^-15).  wav_start / wav_len int64 [V]: where wav v lies in wave; wav_of int32 [F]: the wav of every
+ * sample; end_sample int64 [F]: int((time_stamp / 1000) * sample_rate) of every sample; index int64 [B].  All DEVICE arrays, read
+ * by the kernels (no host synchronisation).  With N = sample_len_secs * sample_rate, w = int(window_size * sample_rate), shift =
+ * audio_shift_secs * sample_rate, and for sample i = index[b] with E = end_sample[i], whose wav has L samples:
+ *   num = min(N, max(E, w));  off = max(E - N + shift, 0);  got = max(0, min(num, L - off))
+ *   got > n_fft / 2:   the window is wav[off : off + got]
+ *   got <= n_fft / 2:  the window is silent.  So is an index outside [0, F), an absent wav (L == 0) and any table entry that
+ *                      points outside its array; nothing outside [wave, wave + total) is read.
+ *
+ * avf_mel_power_bank: one memset of peak and ONE launch -> mel fp32 [B, n_mels, full_frames], peak uint32 [B].  Row b is what
+ * avf_mel_power gives, bit for bit, on the window's own samples (w = win_length): 1 + got / hop frames, reflect padding at the
+ * window's own ends, right-aligned behind zero columns; a silent row is all zero columns.  full_frames >= 1 + N / hop.  window,
+ * win_length, n_fft, hop, fb, bin_lo, bin_hi, n_mels as avf_mel_power takes them; avf_mel_db_norm then runs on the result with
+ * rows_per_clip = 1.
+ * avf_wave_gather: ONE launch -> dst fp32 [B, N]: the window's samples right-aligned in N zeros, a silent row all zeros.  dst is
+ * 4-byte aligned; 16-byte stores wherever the destination allows them.
+ * Neither entry point allocates or synchronises; both can be captured.  dst / mel must not overlap the bank. */
+int avf_mel_power_bank(const void* wave, int wave_dtype, int64_t total, const int64_t* wav_start, const int64_t* wav_len, int64_t V,
+                       const int32_t* wav_of, const int64_t* end_sample, int64_t F, const int64_t* index, int64_t B, int64_t N,
+                       int64_t shift, const float* window, int win_length, int n_fft, int hop, const float* fb,
+                       const int32_t* bin_lo, const int32_t* bin_hi, int n_mels, int full_frames, float* mel, uint32_t* peak,
+                       void* stream);
+int avf_wave_gather(const void* wave, int wave_dtype, int64_t total, const int64_t* wav_start, const int64_t* wav_len, int64_t V,
+                    const int32_t* wav_of, const int64_t* end_sample, int64_t F, const int64_t* index, int64_t B, int64_t N,
+                    int64_t w, int64_t shift, float* dst, void* stream);
+
 /* ---- video clip front-end: uint8 clips <-> normalised planes (dataloader/clip_transforms.py:31-45 NumpyToTensor, 59-93
  * Normalize, 111-128 RandomClipFlip; dataloader/aff2compdataset.py:69-77; models/sformer.py:365-373) ----------------------------
  * avf_clip_normalize: ONE launch.  src uint8 [B, T, H, W, C] (C in 1..4) -> dst, the last k of the C channels as planes:

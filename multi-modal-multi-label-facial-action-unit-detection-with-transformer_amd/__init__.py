@@ -5,7 +5,7 @@ The compute lives in ``lib/libavformer_hip.so`` (hand-written HIP for gfx950, C 
 ``include/avformer_hip.h``); this package is the host-side mirror of the reference's
 ``Transformer`` / head / loss / model-registry surface.
 """
-from . import _build, _lib, audio, augment, checkpoint, clip, dp, frames, graphs, metrics, ops, optim  # noqa: F401
+from . import _build, _lib, audio, audio_bank, augment, checkpoint, clip, dp, frames, graphs, metrics, ops, optim  # noqa: F401
 from ._lib import get_f32_arithmetic, set_f32_arithmetic  # noqa: F401
 from .heads import AU_former, ResFormerTokens, TFormer, VA_former, former_AU_head, tformer_AU_head  # noqa: F401
 from .loss import AULoss, CCCLoss, CrossEntropyEX, DiceAULoss, FocalLoss_Ori, MultiTaskLoss  # noqa: F401

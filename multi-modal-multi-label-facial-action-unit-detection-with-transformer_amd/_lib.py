@@ -15,6 +15,7 @@ from . import _build
 F32, BF16 = 0, 1
 EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
 CLIP_CTHW, CLIP_TCHW = 0, 1
+WAVE_F32, WAVE_I16 = 0, 1
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -130,6 +131,9 @@ SIGNATURES = {
     "avf_eval_scores": (_int, [_vp, _vp, _vp, _vp]),
     "avf_mel_power": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
     "avf_mel_db_norm": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_double, C.c_double, C.c_double, _vp]),
+    "avf_mel_power_bank": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _vp,
+                                  _vp, _int, _int, _vp, _vp, _vp]),
+    "avf_wave_gather": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "avf_clip_normalize": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _int, _int, _vp]),
     "avf_clip_denormalize": (_int, [_vp, _int, _int, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "avf_clip_autoaugment": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp]),

@@ -79,6 +79,7 @@ class MelFrontEnd(nn.Module):
         self.hop_length = int(window_stride * sample_rate)
         self.n_mels = n_mels
         self.full_frames = int(sample_len_secs / window_stride + 1)
+        self.sample_len_frames = sample_len_secs * sample_rate   # aff2compdataset.py:55 (read by audio_bank.AudioAssembler)
         self.top_db, self.mean, self.std = top_db, mean, std
         self.register_buffer("window", torch.hann_window(self.win_length), persistent=False)
         self.register_buffer("fb", melscale_fbanks_htk(self.n_fft // 2 + 1, n_mels, sample_rate), persistent=False)
@@ -126,7 +127,10 @@ class MelFrontEnd(nn.Module):
     def forward(self, audio: torch.Tensor) -> torch.Tensor:
         if self.backend == "hip":
             return self._hip(audio, self.full_frames, True)
-        mel = self.mel_power(audio)
+        return self.db_norm(self.mel_power(audio))
+
+    def db_norm(self, mel: torch.Tensor) -> torch.Tensor:
+        """mel power [.., n_mels, frames] -> left-padded to full_frames, dB, per-clip top_db clamp, normalised (ATen ops)"""
         if mel.shape[-1] < self.full_frames:  # short clip: zero frames in front (aff2compdataset.py:235-239)
             pad = mel.new_zeros(*mel.shape[:-1], self.full_frames)
             pad[..., -mel.shape[-1]:] = mel

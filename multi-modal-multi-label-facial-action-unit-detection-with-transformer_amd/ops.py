@@ -831,7 +831,65 @@ def mel_db_norm(mel: torch.Tensor, peak: torch.Tensor, rows_per_clip: int, top_d
     return mel
 
 
-CLIP_LAYOUTS = {"cthw": _lib.CLIP_CTHW, "tchw": _lib.CLIP_TCHW}
+_WAVE_DTYPES = {torch.float32: _lib.WAVE_F32, torch.int16: _lib.WAVE_I16}
+
+
+def _wave_bank_args(wave: torch.Tensor, wav_start: torch.Tensor, wav_len: torch.Tensor, wav_of: torch.Tensor,
+                    end_sample: torch.Tensor, index: torch.Tensor):
+    """the tensors that avf_mel_power_bank and avf_wave_gather share: wave fp32 / int16 [total], wav_start / wav_len int64 [V],
+    wav_of int32 [F], end_sample int64 [F], index int64 [B], contiguous and on one device"""
+    _need_cuda(wave, wav_start, wav_len, wav_of, end_sample, index)
+    assert wave.dim() == 1 and wave.dtype in _WAVE_DTYPES and wave.is_contiguous() and wave.numel() >= 1
+    V, F = wav_start.numel(), wav_of.numel()
+    assert wav_start.dtype == torch.int64 and wav_len.dtype == torch.int64 and wav_start.dim() == 1 and tuple(wav_len.shape) == (V,)
+    assert wav_of.dtype == torch.int32 and wav_of.dim() == 1 and end_sample.dtype == torch.int64 and tuple(end_sample.shape) == (F,)
+    assert index.dtype == torch.int64 and index.dim() == 1 and index.numel() >= 1
+    for t in (wav_start, wav_len, wav_of, end_sample, index):
+        assert t.is_contiguous() and t.device == wave.device
+    return _WAVE_DTYPES[wave.dtype], V, F, index.numel()
+
+
+def mel_power_bank(wave: torch.Tensor, wav_start: torch.Tensor, wav_len: torch.Tensor, wav_of: torch.Tensor,
+                   end_sample: torch.Tensor, index: torch.Tensor, N: int, shift: int, window: torch.Tensor, fb: torch.Tensor,
+                   bin_lo: torch.Tensor, bin_hi: torch.Tensor, n_fft: int, hop: int, full_frames: int,
+                   out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """avf_mel_power_bank, one memset + one launch: the windows of index int64 [B] out of a waveform bank -> (mel power fp32
+    [B, n_mels, full_frames], peak int32 [B]), each row what mel_power gives on the window's own samples; a silent window is all
+    zero columns.  Everything is read on the device (no host synchronisation).  out: None, or a contiguous fp32 tensor
+    [B, n_mels, full_frames] to write into."""
+    dt, V, F, B = _wave_bank_args(wave, wav_start, wav_len, wav_of, end_sample, index)
+    _need_cuda(window, fb, bin_lo, bin_hi)
+    assert window.dtype == torch.float32 and window.is_contiguous() and fb.dtype == torch.float32 and fb.is_contiguous()
+    assert bin_lo.dtype == torch.int32 and bin_hi.dtype == torch.int32 and bin_lo.is_contiguous() and bin_hi.is_contiguous()
+    n_mels = fb.shape[1]
+    assert fb.shape[0] == n_fft // 2 + 1 and bin_lo.numel() == n_mels and bin_hi.numel() == n_mels
+    mel = torch.empty(B, n_mels, int(full_frames), dtype=torch.float32, device=wave.device) if out is None else out
+    assert mel.dtype == torch.float32 and mel.is_contiguous() and tuple(mel.shape) == (B, n_mels, int(full_frames))
+    assert mel.device == wave.device
+    peak = torch.empty(B, dtype=torch.int32, device=wave.device)
+    _lib.check(_lib.load().avf_mel_power_bank(_ptr(wave), dt, wave.numel(), _ptr(wav_start), _ptr(wav_len), V, _ptr(wav_of),
+                                              _ptr(end_sample), F, _ptr(index), B, int(N), int(shift), _ptr(window), window.numel(),
+                                              int(n_fft), int(hop), _ptr(fb), _ptr(bin_lo), _ptr(bin_hi), n_mels, int(full_frames),
+                                              _ptr(mel), _ptr(peak), _stream()), "mel_power_bank")
+    return mel, peak
+
+
+def wave_gather(wave: torch.Tensor, wav_start: torch.Tensor, wav_len: torch.Tensor, wav_of: torch.Tensor, end_sample: torch.Tensor,
+                index: torch.Tensor, N: int, w: int, shift: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avf_wave_gather, one launch: the windows of index int64 [B] out of a waveform bank -> fp32 [B, N], every window right-aligned
+    in N zeros (int16 samples times 2^-15), a silent window all zeros.  out: None, or a contiguous fp32 tensor [B, N] to write
+    into (4-byte alignment is enough)."""
+    dt, V, F, B = _wave_bank_args(wave, wav_start, wav_len, wav_of, end_sample, index)
+    if out is None:
+        out = torch.empty(B, int(N), dtype=torch.float32, device=wave.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, int(N)) and out.device == wave.device
+    _lib.check(_lib.load().avf_wave_gather(_ptr(wave), dt, wave.numel(), _ptr(wav_start), _ptr(wav_len), V, _ptr(wav_of),
+                                           _ptr(end_sample), F, _ptr(index), B, int(N), int(w), int(shift), _ptr(out), _stream()),
+               "wave_gather")
+    return out
+
+
+CLIP_LAYOUTS ={"cthw": _lib.CLIP_CTHW, "tchw": _lib.CLIP_TCHW}
 
 
 def clip_normalize(clip: torch.Tensor, lut: torch.Tensor, k: Optional[int] = None, flip: Optional[torch.Tensor] = None,
