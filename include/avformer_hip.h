@@ -544,10 +544,19 @@ int avf_clip_denormalize(const void* src, int in_dtype, int layout, int64_t B, i
  * shearX, no fused multiply-add - the bytes are those of Pillow.  dst == src is allowed (no other overlap); neither needs any
  * alignment.  A frame has at most avf_clip_autoaugment_max_pixels() pixels (C = 3; C = 4: three quarters of it) - both frame
  * buffers live in one workgroup's LDS.  Nothing is allocated or synchronised (capturable); every argument is checked before
- * anything is enqueued. */
+ * anything is enqueued.
+ *
+ * avf_clip_autoaugment_normalize: ONE launch, the reference's whole training transform aug_clip_transform = [ImageNetPolicy(),
+ * RandomClipFlip(), NumpyToTensor(), Normalize(...)] (dataloader/aff2compdataset.py:72-74, applied at 163-164): the result is
+ * that of avf_clip_normalize on the clip of avf_clip_autoaugment, and no uint8 clip is written.  src, B .. C and plan as
+ * avf_clip_autoaugment takes them (the same frame-size limit), k, lut, flip, dst, out_dtype and layout as avf_clip_normalize
+ * takes them; dst must not overlap src.  Capturable; every argument is checked before anything is enqueued. */
 int avf_clip_autoaugment(const uint8_t* src, uint8_t* dst, int64_t B, int64_t T, int64_t H, int64_t W, int C, const int32_t* plan,
                          void* stream);
 int64_t avf_clip_autoaugment_max_pixels(void);
+int avf_clip_autoaugment_normalize(const uint8_t* src, int64_t B, int64_t T, int64_t H, int64_t W, int C, const int32_t* plan,
+                                   int k, const float* lut, const uint8_t* flip, void* dst, int out_dtype, int layout,
+                                   void* stream);
 
 /* ---- clips assembled on the device from a resident frame bank (dataloader/aff2compdataset.py:122-156; testset.py:84-113) --------
  * bank uint8 [F, H, W, C] (C in 1..4, no alignment assumed), video_db_nr int32 [F], present uint8 [F] or null (every frame is
@@ -564,6 +573,12 @@ int64_t avf_clip_autoaugment_max_pixels(void);
  * avf_clip_gather_autoaugment: ONE launch, bank -> augmented dst uint8 [B, T, H, W, C]; C, plan and the frame-size limit
  *                              (avf_clip_autoaugment_max_pixels) as avf_clip_autoaugment takes them, and the result is that of
  *                              avf_clip_autoaugment on the clip of avf_clip_gather.
+ * avf_clip_gather_autoaugment_normalize:
+ *                              ONE launch, bank -> augmented, mirrored, normalised planes: the reference's training transform
+ *                              (dataloader/aff2compdataset.py:72-74, 163-164) from the bank.  plan as avf_clip_gather_autoaugment,
+ *                              k .. layout as avf_clip_gather_normalize take them, and the result is that of avf_clip_normalize on
+ *                              the clip of avf_clip_gather_autoaugment: a black slot goes through its plan slots and is then
+ *                              normalised.  No uint8 clip is written.
  * dst must not overlap the bank.  Sizes and indices are 64-bit.  Nothing is allocated or synchronised (capturable); every argument
  * is checked before anything is enqueued. */
 int avf_clip_gather(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index, int64_t F,
@@ -574,6 +589,10 @@ int avf_clip_gather_normalize(const uint8_t* bank, const int32_t* video_db_nr, c
 int avf_clip_gather_autoaugment(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index,
                                 int64_t F, int64_t B, int64_t T, int64_t d, int64_t H, int64_t W, int C, const int32_t* plan,
                                 uint8_t* dst, void* stream);
+int avf_clip_gather_autoaugment_normalize(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present,
+                                          const int64_t* index, int64_t F, int64_t B, int64_t T, int64_t d, int64_t H, int64_t W,
+                                          int C, const int32_t* plan, int k, const float* lut, const uint8_t* flip, void* dst,
+                                          int out_dtype, int layout, void* stream);
 
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */

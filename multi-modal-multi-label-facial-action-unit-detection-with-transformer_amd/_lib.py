@@ -138,10 +138,13 @@ SIGNATURES = {
     "avf_clip_denormalize": (_int, [_vp, _int, _int, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "avf_clip_autoaugment": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
     "avf_clip_autoaugment_max_pixels": (_i64, []),
+    "avf_clip_autoaugment_normalize": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp, _int, _int, _vp]),
     "avf_clip_gather": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
     "avf_clip_gather_normalize": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _int, _int,
                                          _vp]),
     "avf_clip_gather_autoaugment": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "avf_clip_gather_autoaugment_normalize": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp,
+                                                     _vp, _int, _int, _vp]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

@@ -38,6 +38,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .clip import ClipFrontEnd
 
 BACKENDS = ("numpy", "hip")
 OPS = ("posterize", "solarize", "invert", "autocontrast", "equalize", "color", "contrast", "sharpness", "rotate", "shearX")
@@ -307,11 +308,15 @@ class ClipAutoAugment(nn.Module):
     """``forward(clip_u8 [B, T, H, W, C] or [T, H, W, C], plan int32 [B, T, 2, 8] or [T, 2, 8])`` -> uint8 of the clip's shape:
     each frame through the two slots of its plan (``draw_plan`` / ``make_plan``).  C is 3 or 4; channels 0..2 are transformed,
     channel 3 passes through (``clip[t, :, :, 0:3]``, autoaugment.py:106-111).  The output feeds ``ClipFrontEnd`` unchanged.
+    ``normalized(clip_u8, plan, front_end, flip=None)`` -> ``front_end(forward(clip_u8, plan), flip)``: the reference's training
+    transform (policy, mirror, NumpyToTensor, Normalize; aff2compdataset.py:72-74) in the front end's layout, dtype and channel
+    slice.
 
     ``backend="numpy"`` (default): the numpy restatement, clip and plan on the CPU.  ``backend="hip"``: one launch of
     csrc/augment.hip; the clip must be on the GPU (no CPU fallback), under ``no_grad``; the plan is on the clip's device, or on
     the CPU - then it is checked against the frame size and uploaded.  ``inplace=True`` (hip) writes into the clip.  Frames
-    above ``ops.clip_autoaugment_max_pixels()`` pixels are an error."""
+    above ``ops.clip_autoaugment_max_pixels()`` pixels are an error.  ``normalized`` is one launch too (no augmented uint8 clip
+    is written; ``inplace`` does not apply to it) and takes the front end's table, whatever the front end's own backend."""
 
     def __init__(self, backend: str = "numpy", inplace: bool = False):
         super().__init__()
@@ -319,7 +324,9 @@ class ClipAutoAugment(nn.Module):
             raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
         self.backend, self.inplace = backend, bool(inplace)
 
-    def forward(self, clip_u8: torch.Tensor, plan: torch.Tensor) -> torch.Tensor:
+    def _checked(self, clip_u8: torch.Tensor, plan: torch.Tensor):
+        """the argument checks of ``forward`` and ``normalized``: the batched clip, its plan (hip: on the clip's device) and whether
+        the batch axis was added"""
         if clip_u8.dtype != torch.uint8:
             raise ValueError(f"the clip must be uint8, got {clip_u8.dtype}")
         if clip_u8.dim() not in (4, 5):
@@ -344,6 +351,12 @@ class ClipAutoAugment(nn.Module):
                 plan = plan.to(clip.device, non_blocking=True)
             elif plan.device != clip.device:
                 raise ValueError(f"plan is on {plan.device}, the clip on {clip.device}")
+        return clip, plan, squeeze
+
+    def forward(self, clip_u8: torch.Tensor, plan: torch.Tensor) -> torch.Tensor:
+        clip, plan, squeeze = self._checked(clip_u8, plan)
+        B, T, H, W, C = clip.shape
+        if self.backend == "hip":
             with torch.no_grad():
                 src = clip.contiguous()
                 if self.inplace and src.data_ptr() != clip.data_ptr():
@@ -361,4 +374,22 @@ class ClipAutoAugment(nn.Module):
                         img = apply_slot(img, pl[b, t, s])
                     x[b, t, :, :, 0:3] = img
             out = torch.from_numpy(x)
+        return out[0] if squeeze else out
+
+    def normalized(self, clip_u8: torch.Tensor, plan: torch.Tensor, front_end: ClipFrontEnd,
+                   flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not isinstance(front_end, ClipFrontEnd):
+            raise ValueError(f"front_end must be a ClipFrontEnd, got {type(front_end).__name__}")
+        clip, plan, squeeze = self._checked(clip_u8, plan)
+        C = clip.shape[-1]
+        if C != front_end.in_channels:
+            raise ValueError(f"front_end: the clip has {C} channels, mean / std have {front_end.in_channels}")
+        flip = front_end._flags(flip, clip.shape[0], clip.device)
+        if self.backend != "hip":
+            return front_end(self(clip_u8, plan), flip)
+        if front_end.lut.device != clip.device:
+            raise ValueError(f"front_end is on {front_end.lut.device}, the clip on {clip.device}")
+        with torch.no_grad():
+            out = ops.clip_autoaugment_normalize(clip.contiguous(), plan.contiguous(), front_end.lut, front_end.channels, flip,
+                                                 front_end.layout, front_end.out_dtype)
         return out[0] if squeeze else out

@@ -21,6 +21,16 @@
 //      byte).  dst == src is allowed: a workgroup reads all it uses of its frame before it writes.
 // A frame whose two op codes are 0 (or outside 1..10) is copied; with dst == src its workgroup returns at once.
 //
+// avf_clip_autoaugment_normalize, one launch: the same kernel with another step 3 (the kernel is a template over its sink,
+// augment_kernels.hpp) - ImageNetPolicy, RandomClipFlip, NumpyToTensor and Normalize, the reference's aug_clip_transform
+// (dataloader/aff2compdataset.py:72-74, 163-164), without a uint8 clip in between.  Step 1 keeps the SOURCE's offset (there is
+// no byte destination), so it always loads aligned 16-byte chunks.  Step 3 is the store phase of clip.hip's normalise kernel on
+// the LDS frame: per kept channel each lane stores 16 bytes (4 fp32 / 8 bf16 pixels) of one plane, value lut[channel][byte],
+// scalar stores in front of the first aligned vector and behind the last; a mirrored clip (flip[b], read on the device)
+// reverses the read index within each row.  The k * 256 table entries sit in the frame buffer that does not hold the result,
+// so the launch asks for no more LDS than avf_clip_autoaugment does (79200 B at 112 x 112 x 3, two workgroups per CU); a
+// frame of fewer than k * 1024 bytes reads the table from global memory.
+//
 // Arithmetic: integers wherever Pillow's are integers; fp32 for Image.blend, fp64 for the autocontrast table and the bicubic
 // of shearX, each operation rounded on its own (#pragma clang fp contract(off) in every function with floating-point
 // arithmetic - see clip.hip - and -ffp-contract=off for the file); float / double -> byte conversions truncate.
@@ -45,7 +55,25 @@ extern "C" int avf_clip_autoaugment(const uint8_t* src, uint8_t* dst, int64_t B,
   const int64_t bytes = B * T * H * W * C;                          // < 2^31 * 2^17
   AVF_REQUIRE(dst == src || dst + bytes <= src || src + bytes <= dst, "clip_autoaugment: dst overlaps src without being src");
   const ClipTensorSource from{src, bytes};
-  hipStream_t s = (hipStream_t)stream;
-  return C == 3 ? aug_launch<3>("clip_autoaugment", from, dst, B, T, (int)H, (int)W, plan, s)
-                : aug_launch<4>("clip_autoaugment", from, dst, B, T, (int)H, (int)W, plan, s);
+  return aug_bytes_launch("clip_autoaugment", from, dst, B, T, H, W, C, plan, (hipStream_t)stream);
+}
+
+extern "C" int avf_clip_autoaugment_normalize(const uint8_t* src, int64_t B, int64_t T, int64_t H, int64_t W, int C,
+                                              const int32_t* plan, int k, const float* lut, const uint8_t* flip, void* dst,
+                                              int out_dtype, int layout, void* stream) {
+  using namespace avf;
+  const char* who = "clip_autoaugment_normalize";
+  AVF_REQUIRE(src, "%s: src is null", who);
+  AVF_REQUIRE(plan, "%s: plan is null", who);
+  AVF_REQUIRE(((uintptr_t)plan & 3u) == 0, "%s: plan is not aligned to its element", who);
+  AVF_REQUIRE(lut, "%s: lut is null", who);
+  AVF_REQUIRE(dst, "%s: dst is null", who);
+  AVF_TRY(aug_shape_ok(who, B, T, H, W, C));
+  AVF_TRY(aug_planes_ok(who, C, k, lut, dst, out_dtype, layout));
+  const int64_t bytes = B * T * H * W * C;
+  const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+  AVF_REQUIRE(d0 + (uintptr_t)aug_planes_bytes(B, T, H, W, k, out_dtype) <= s0 || s0 + (uintptr_t)bytes <= d0, "%s: dst overlaps src",
+              who);
+  const ClipTensorSource from{src, bytes};
+  return aug_planes_launch(who, from, B, T, H, W, C, plan, k, lut, flip, dst, out_dtype, layout, (hipStream_t)stream);
 }

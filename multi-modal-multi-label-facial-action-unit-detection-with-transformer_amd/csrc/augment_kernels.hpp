@@ -1,8 +1,9 @@
 // augment_kernels.hpp - the device code that augment.hip (an assembled clip) and clip_bank.hip (a resident frame bank) share:
-// the AutoAugment kernel as a template over the frame source (clip_source.hpp).  augment.hip describes the kernel.  A file that
-// includes this one is compiled with -ffp-contract=off.
+// the AutoAugment kernel as a template over the frame source (clip_source.hpp) and over the sink, where the finished frame goes
+// (AugBytesSink / AugPlanesSink below).  augment.hip describes the kernel.  A file that includes this one is compiled with
+// -ffp-contract=off.
 #pragma once
-#include "clip_source.hpp"
+#include "clip_kernels.hpp"
 
 namespace avf {
 namespace {
@@ -119,8 +120,131 @@ __device__ __forceinline__ void shear_pixel(const uint8_t* __restrict__ in, uint
   }
 }
 
-template <int C, typename Source>
-__global__ __launch_bounds__(AUG_THREADS) void clip_autoaugment_kernel(const Source src, uint8_t* dst, int64_t T,
+
+// Where the finished frame goes.  A sink is passed by value and tells the kernel three things: is(p) - whether it writes to p
+// (a frame without operations is then already in place); shift() - where the frame's first byte sits inside its 16-byte chunk of
+// LDS; store() - the last phase, from the LDS frame `res` (pixel byte j at res[shift + j]) to global memory.  `idle` is the
+// frame buffer that does not hold the result: fb bytes, 16-byte aligned, free for the store phase.
+//
+//   AugBytesSink        the interleaved uint8 frame to dst + frame * n.  The frame is staged with the DESTINATION's offset, so
+//                       the 16-byte stores are aligned; the first and last chunk, shared with the neighbouring frames, go out
+//                       byte by byte.
+//   AugPlanesSink<OutT> the store phase of clip_normalize_kernel (clip_kernels.hpp) on the LDS frame: the last k channels as
+//                       planes of OutT = float | bf16, value lut[channel][byte], a flagged clip read backwards within each row.
+//                       There is no byte destination, so the frame is staged with the SOURCE's offset (0 for a black slot) and
+//                       staging always takes the aligned 16-byte path.  The k * 256 table entries are copied into the idle
+//                       frame buffer - no LDS beyond what the bytes sink asks for -; a frame whose buffer is too small for them
+//                       (fb < k * 1024) reads the table from global memory instead.
+struct AugBytesSink {
+  uint8_t* dst;
+  static constexpr bool STAGES_AT_SOURCE_OFFSET = false;
+  __device__ __forceinline__ bool is(const uint8_t* p) const { return dst == p; }
+  __device__ __forceinline__ int shift(int64_t frame, int n, const uint8_t*) const {
+    return (int)(reinterpret_cast<uintptr_t>(dst + frame * n) & 15u);
+  }
+  template <int C>
+  __device__ __forceinline__ void store(const uint8_t* res, uint8_t*, int, int shift, int64_t frame, int64_t, int H, int W,
+                                        int tid) const {
+    const int n = H * W * C;
+    const int chunks = (shift + n + 15) >> 4;
+    uint8_t* a0 = dst + frame * n - shift;
+    for (int i = tid; i < chunks; i += AUG_THREADS) {
+      const int off = 16 * i - shift;   // of the chunk's first byte inside the frame's byte range
+      if (off >= 0 && off + 16 <= n) {
+        *reinterpret_cast<uint4*>(a0 + 16 * i) = *reinterpret_cast<const uint4*>(res + 16 * i);
+      } else {  // the frame's first / last chunk is shared with its neighbours: only the bytes that are this frame's
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          if (off + q >= 0 && off + q < n) a0[16 * i + q] = res[16 * i + q];
+      }
+    }
+  }
+};
+
+// the k planes of one frame: every lane 16 bytes of ONE plane, consecutive lanes consecutive addresses, up to VEC - 1 scalar
+// stores in front of the first aligned vector and behind the last (a plane starts wherever it starts).  px: the frame's first
+// byte; table: the k * 256 entries of the kept channels, in LDS or in global memory
+template <int C, typename OutT>
+__device__ __forceinline__ void store_planes(const float* __restrict__ table, const uint8_t* __restrict__ px, OutT* __restrict__ dst,
+                                             int k, int layout, bool mirrored, int64_t b, int64_t t, int64_t T, int P, int W,
+                                             int tid) {
+  constexpr int VEC = 16 / (int)sizeof(OutT);
+  for (int ci = 0; ci < k; ++ci) {
+    const int64_t plane = layout == AVF_CLIP_CTHW ? (b * k + ci) * T + t : (b * T + t) * k + ci;
+    OutT* __restrict__ o = dst + plane * (int64_t)P;
+    const float* lt = table + ci * 256;
+    const uint8_t* sg = px + (C - k + ci);
+    // source pixel of output pixel j: the same, or the same row read backwards
+    auto one = [&](int j) -> float {
+      int sl = j;
+      if (mirrored) {
+        const int r = j / W;
+        sl = r * W + (W - 1 - (j - r * W));
+      }
+      return lt[sg[sl * C]];
+    };
+    const int head = head_elems(o, P);
+    const int nvec = (P - head) / VEC, tail = (P - head) - nvec * VEC;
+    if (tid < head) o[tid] = from_f32<OutT>(one(tid));
+    if (tid < tail) o[head + nvec * VEC + tid] = from_f32<OutT>(one(head + nvec * VEC + tid));
+    if (!mirrored) {
+      for (int v = tid; v < nvec; v += AUG_THREADS) {
+        const int j0 = head + v * VEC;
+        float x[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) x[i] = lt[sg[(j0 + i) * C]];
+        store_vec<OutT>(o + j0, x);
+      }
+    } else {
+      for (int v = tid; v < nvec; v += AUG_THREADS) {
+        const int j0 = head + v * VEC;
+        const int r = j0 / W;
+        int wl = j0 - r * W, row = r * W;   // a vector may run over the end of a row
+        float x[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          x[i] = lt[sg[(row + W - 1 - wl) * C]];
+          if (++wl == W) {
+            wl = 0;
+            row += W;
+          }
+        }
+        store_vec<OutT>(o + j0, x);
+      }
+    }
+  }
+}
+
+template <typename OutT>
+struct AugPlanesSink {
+  OutT* dst;             // [B, k, T, H, W] (cthw) or [B, T, k, H, W] (tchw)
+  const float* lut;      // [C, 256]
+  const uint8_t* flip;   // [B] or null: no clip is mirrored
+  int k, layout;
+  static constexpr bool STAGES_AT_SOURCE_OFFSET = true;
+  __device__ __forceinline__ bool is(const uint8_t*) const { return false; }
+  __device__ __forceinline__ int shift(int64_t, int, const uint8_t* first) const {
+    return first != nullptr ? (int)(reinterpret_cast<uintptr_t>(first) & 15u) : 0;
+  }
+  template <int C>
+  __device__ __forceinline__ void store(const uint8_t* res, uint8_t* idle, int fb, int shift, int64_t frame, int64_t T, int H, int W,
+                                        int tid) const {
+    const int64_t b = frame / T, t = frame - b * T;
+    const bool mirrored = flip != nullptr && flip[b] != 0;               // uniform over the workgroup
+    const float* table = lut + (C - k) * 256;
+    if (fb >= k * 256 * (int)sizeof(float)) {                            // (uniform)
+      float* table_s = reinterpret_cast<float*>(idle);
+      for (int i = tid; i < k * 256; i += AUG_THREADS) table_s[i] = table[i];
+      __syncthreads();
+      store_planes<C, OutT>(table_s, res + shift, dst, k, layout, mirrored, b, t, T, H * W, W, tid);
+    } else {  // a frame of a few pixels: correct, not fast
+      store_planes<C, OutT>(table, res + shift, dst, k, layout, mirrored, b, t, T, H * W, W, tid);
+    }
+  }
+};
+
+template <int C, typename Source, typename Sink>
+__global__ __launch_bounds__(AUG_THREADS) void clip_autoaugment_kernel(const Source src, const Sink sink, int64_t T,
                                                                       const int32_t* __restrict__ plan, int H, int W, int fb) {
   extern __shared__ __attribute__((aligned(16))) uint8_t aug_lds[];
   uint32_t* hist = reinterpret_cast<uint32_t*>(aug_lds + 2 * fb);                    // [3][256]
@@ -136,18 +260,17 @@ __global__ __launch_bounds__(AUG_THREADS) void clip_autoaugment_kernel(const Sou
     const int op = pl[s * AUG_SLOT_WORDS];
     ops[s] = (op >= OP_POSTERIZE && op <= OP_SHEARX) ? op : OP_NONE;
   }
-  if (ops[0] == OP_NONE && ops[1] == OP_NONE && dst == src.base()) return;
+  if (ops[0] == OP_NONE && ops[1] == OP_NONE && sink.is(src.base())) return;
 
   const uint8_t* first = src.frame(frame / T, frame % T, T, n);   // null: a black slot
-  uint8_t* first_out = dst + frame * n;
-  const int shift = (int)(reinterpret_cast<uintptr_t>(first_out) & 15u);
+  const int shift = sink.shift(frame, n, first);
   const int chunks = (shift + n + 15) >> 4;                                          // 16 * chunks <= fb
   int cur = 0;                                                                       // which frame buffer holds the frame
   {
     uint8_t* stage = aug_lds;
     if (first == nullptr) {
       zero_chunks<AUG_THREADS>(stage, chunks, tid);
-    } else if ((int)(reinterpret_cast<uintptr_t>(first) & 15u) == shift) {
+    } else if (Sink::STAGES_AT_SOURCE_OFFSET || (int)(reinterpret_cast<uintptr_t>(first) & 15u) == shift) {
       stage_chunks<AUG_THREADS>(stage, first, chunks, src.base(), src.bytes(), tid);
     } else {
       for (int k = tid; k < n; k += AUG_THREADS) stage[shift + k] = first[k];
@@ -335,18 +458,7 @@ __global__ __launch_bounds__(AUG_THREADS) void clip_autoaugment_kernel(const Sou
     __syncthreads();
   }
 
-  const uint8_t* res = aug_lds + cur * fb;
-  uint8_t* a0 = first_out - shift;
-  for (int i = tid; i < chunks; i += AUG_THREADS) {
-    const int off = 16 * i - shift;   // of the chunk's first byte inside the frame's byte range
-    if (off >= 0 && off + 16 <= n) {
-      *reinterpret_cast<uint4*>(a0 + 16 * i) = *reinterpret_cast<const uint4*>(res + 16 * i);
-    } else {  // the frame's first / last chunk is shared with its neighbours: only the bytes that are this frame's
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (off + q >= 0 && off + q < n) a0[16 * i + q] = res[16 * i + q];
-    }
-  }
+  sink.template store<C>(aug_lds + cur * fb, aug_lds + (cur ^ 1) * fb, fb, shift, frame, T, H, W, tid);
 }
 
 // what both entry points ask of the clip's shape
@@ -365,21 +477,54 @@ int aug_shape_ok(const char* who, int64_t B, int64_t T, int64_t H, int64_t W, in
   return 0;
 }
 
-template <int C, typename Source>
-int aug_launch(const char* who, const Source& src, uint8_t* dst, int64_t B, int64_t T, int H, int W, const int32_t* plan,
+template <int C, typename Source, typename Sink>
+int aug_launch(const char* who, const Source& src, const Sink& sink, int64_t B, int64_t T, int H, int W, const int32_t* plan,
                hipStream_t s) {
   static PerDeviceOnce once;
   if (once.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)clip_autoaugment_kernel<C, Source>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       AUG_LDS);
+    hipError_t e = hipFuncSetAttribute((const void*)clip_autoaugment_kernel<C, Source, Sink>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, AUG_LDS);
     AVF_REQUIRE(e == hipSuccess, "%s: cannot raise dynamic LDS limit: %s", who, hipGetErrorString(e));
     once.mark();
   }
   const int n = H * W * C, fb = aug_frame_buffer(n);
   const int lds = 2 * fb + AUG_FIXED;
   AVF_REQUIRE(lds <= AUG_LDS, "%s: %d bytes of LDS", who, lds);
-  clip_autoaugment_kernel<C, Source><<<(unsigned)(B * T), AUG_THREADS, (uint32_t)lds, s>>>(src, dst, T, plan, H, W, fb);
+  clip_autoaugment_kernel<C, Source, Sink><<<(unsigned)(B * T), AUG_THREADS, (uint32_t)lds, s>>>(src, sink, T, plan, H, W, fb);
   return check_launch("clip_autoaugment_kernel");
+}
+
+// the bytes sink, for either source
+template <typename Source>
+int aug_bytes_launch(const char* who, const Source& src, uint8_t* dst, int64_t B, int64_t T, int64_t H, int64_t W, int C,
+                     const int32_t* plan, hipStream_t s) {
+  const AugBytesSink to{dst};
+  return C == 3 ? aug_launch<3>(who, src, to, B, T, (int)H, (int)W, plan, s) : aug_launch<4>(who, src, to, B, T, (int)H, (int)W, plan, s);
+}
+
+// what the planes sink asks of its output side: the checks of clip_normalize_launch, and the table's alignment
+int aug_planes_ok(const char* who, int C, int k, const float* lut, const void* dst, int out_dtype, int layout) {
+  AVF_TRY(clip_output_ok(who, C, k, dst, out_dtype, layout));
+  AVF_REQUIRE(((uintptr_t)lut & 3u) == 0, "%s: lut is not aligned to its element", who);
+  return 0;
+}
+
+// the planes sink, for either source.  The caller has checked its pointers, the shape (aug_shape_ok), the output side
+// (aug_planes_ok) and that dst is apart from what the source reads.
+template <typename Source>
+int aug_planes_launch(const char* who, const Source& src, int64_t B, int64_t T, int64_t H, int64_t W, int C, const int32_t* plan,
+                      int k, const float* lut, const uint8_t* flip, void* dst, int out_dtype, int layout, hipStream_t s) {
+  if (out_dtype == AVF_F32) {
+    const AugPlanesSink<float> to{(float*)dst, lut, flip, k, layout};
+    return C == 3 ? aug_launch<3>(who, src, to, B, T, (int)H, (int)W, plan, s) : aug_launch<4>(who, src, to, B, T, (int)H, (int)W, plan, s);
+  }
+  const AugPlanesSink<bf16> to{(bf16*)dst, lut, flip, k, layout};
+  return C == 3 ? aug_launch<3>(who, src, to, B, T, (int)H, (int)W, plan, s) : aug_launch<4>(who, src, to, B, T, (int)H, (int)W, plan, s);
+}
+
+// bytes of the planes of B clips (after aug_planes_ok)
+int64_t aug_planes_bytes(int64_t B, int64_t T, int64_t H, int64_t W, int k, int out_dtype) {
+  return B * k * T * H * W * (out_dtype == AVF_F32 ? 4 : 2);
 }
 
 }  // namespace

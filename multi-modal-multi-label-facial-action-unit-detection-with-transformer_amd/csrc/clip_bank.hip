@@ -14,6 +14,11 @@
 //                              No uint8 clip exists.  A black slot is lut[c][0].
 // avf_clip_gather_autoaugment  one launch: bank -> augmented uint8 clip, augment.hip's clip_autoaugment_kernel with the bank as its
 //                              source.  A black slot goes through its two plan slots like any other frame.
+// avf_clip_gather_autoaugment_normalize
+//                              one launch: bank -> augmented, mirrored, normalised planes - the reference's aug_clip_transform
+//                              (dataloader/aff2compdataset.py:72-74, 163-164) -, the same kernel with the bank as its source and
+//                              the planes as its sink.  No uint8 clip exists.  A black slot goes through its two plan slots and
+//                              is THEN normalised: inverted it is lut[c][255].
 //
 // The file is compiled with -ffp-contract=off, like augment.hip.  gfx950 resources: see DESIGN.md section 9.
 #include "augment_kernels.hpp"
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void clip_gather_kernel(const ClipB
   }
 }
 
-// what the three entry points ask of the bank, the index and the rule; fills the source
+// what the entry points ask of the bank, the index and the rule; fills the source
 int bank_source(const char* who, const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present, const int64_t* index,
                 int64_t F, int64_t T, int64_t d, int64_t H, int64_t W, int C, ClipBankSource* out) {
   AVF_REQUIRE(bank, "%s: bank is null", who);
@@ -166,7 +171,23 @@ extern "C" int avf_clip_gather_autoaugment(const uint8_t* bank, const int32_t* v
   ClipBankSource from;
   AVF_TRY(bank_source(who, bank, video_db_nr, present, index, F, T, d, H, W, C, &from));
   AVF_TRY(apart(who, bank, from.total_bytes, dst, B * T * H * W * C));
-  hipStream_t s = (hipStream_t)stream;
-  return C == 3 ? aug_launch<3>(who, from, dst, B, T, (int)H, (int)W, plan, s)
-                : aug_launch<4>(who, from, dst, B, T, (int)H, (int)W, plan, s);
+  return aug_bytes_launch(who, from, dst, B, T, H, W, C, plan, (hipStream_t)stream);
+}
+
+extern "C" int avf_clip_gather_autoaugment_normalize(const uint8_t* bank, const int32_t* video_db_nr, const uint8_t* present,
+                                                     const int64_t* index, int64_t F, int64_t B, int64_t T, int64_t d, int64_t H,
+                                                     int64_t W, int C, const int32_t* plan, int k, const float* lut,
+                                                     const uint8_t* flip, void* dst, int out_dtype, int layout, void* stream) {
+  using namespace avf;
+  const char* who = "clip_gather_autoaugment_normalize";
+  AVF_REQUIRE(plan, "%s: plan is null", who);
+  AVF_REQUIRE(((uintptr_t)plan & 3u) == 0, "%s: plan is not aligned to its element", who);
+  AVF_REQUIRE(lut, "%s: lut is null", who);
+  AVF_REQUIRE(dst, "%s: dst is null", who);
+  AVF_TRY(aug_shape_ok(who, B, T, H, W, C));
+  AVF_TRY(aug_planes_ok(who, C, k, lut, dst, out_dtype, layout));
+  ClipBankSource from;
+  AVF_TRY(bank_source(who, bank, video_db_nr, present, index, F, T, d, H, W, C, &from));
+  AVF_TRY(apart(who, bank, from.total_bytes, dst, aug_planes_bytes(B, T, H, W, k, out_dtype)));
+  return aug_planes_launch(who, from, B, T, H, W, C, plan, k, lut, flip, dst, out_dtype, layout, (hipStream_t)stream);
 }

@@ -140,17 +140,22 @@ int clip_shape_ok(const char* who, int64_t B, int64_t T, int64_t H, int64_t W, i
   return 0;
 }
 
-
-// the checks of the output side, the tiling and the launch, for either source (the caller has checked its pointers and the shape)
-template <typename Source>
-int clip_normalize_launch(const char* who, const Source& from, int64_t B, int64_t T, int64_t H, int64_t W, int C, int k,
-                          const float* lut, const uint8_t* flip, void* dst, int out_dtype, int layout, hipStream_t s) {
+// what every entry point that writes planes asks of its output side
+int clip_output_ok(const char* who, int C, int k, const void* dst, int out_dtype, int layout) {
   AVF_REQUIRE(k >= 1 && k <= C, "%s: k is %d, outside 1..C = %d", who, k, C);
   AVF_REQUIRE(out_dtype == AVF_F32 || out_dtype == AVF_BF16, "%s: out_dtype is %d, neither AVF_F32 nor AVF_BF16", who,
               out_dtype);
   AVF_REQUIRE(layout == AVF_CLIP_CTHW || layout == AVF_CLIP_TCHW, "%s: layout is %d, neither cthw (0) nor tchw (1)", who,
               layout);
   AVF_REQUIRE(((uintptr_t)dst & (out_dtype == AVF_F32 ? 3u : 1u)) == 0, "%s: dst is not aligned to its element", who);
+  return 0;
+}
+
+// the checks of the output side, the tiling and the launch, for either source (the caller has checked its pointers and the shape)
+template <typename Source>
+int clip_normalize_launch(const char* who, const Source& from, int64_t B, int64_t T, int64_t H, int64_t W, int C, int k,
+                          const float* lut, const uint8_t* flip, void* dst, int out_dtype, int layout, hipStream_t s) {
+  AVF_TRY(clip_output_ok(who, C, k, dst, out_dtype, layout));
   // whole rows per tile where a row fits (then rows are contiguous in the source and in the planes), else row segments
   int rows_per_tile = 1, cols_per_tile, row_tiles, col_tiles = 1;
   if (W <= CLIP_TILE) {

@@ -87,10 +87,14 @@ class ClipAssembler(nn.Module):
     ``normalized(bank, index, front_end, flip=None)`` -> ``front_end(forward(bank, index), flip)``: the planes in the front end's
     layout, dtype and channel slice.
     ``augmented(bank, index, plan, augment)`` -> ``augment(forward(bank, index), plan)``: the augmented uint8 clip.
+    ``augmented_normalized(bank, index, plan, augment, front_end, flip=None)`` ->
+    ``front_end(augment(forward(bank, index), plan), flip)``: the reference's training transform (aff2compdataset.py:72-74) from
+    the bank, in the front end's layout, dtype and channel slice.
 
-    ``backend="torch"`` (default): ATen ops on any device, then the module that was passed in.  ``backend="hip"``: one launch of
-    csrc/clip_bank.hip per method - no uint8 clip is written by ``normalized``, no plain one by ``augmented`` -, the bank must be
-    on the GPU (no CPU fallback), under ``no_grad``; ``index`` and ``flip`` are read on the device.  Both give the same bytes."""
+    ``backend="torch"`` (default): ATen ops on any device, then the modules that were passed in.  ``backend="hip"``: one launch of
+    csrc/clip_bank.hip per method - no uint8 clip is written by ``normalized`` and ``augmented_normalized``, no plain one by
+    ``augmented`` -, the bank must be on the GPU (no CPU fallback), under ``no_grad``; ``index``, ``flip`` and ``plan`` are read on
+    the device.  Both give the same bytes."""
 
     def __init__(self, clip_len: int = 16, dilation: int = 3, backend: str = "torch"):
         super().__init__()
@@ -180,3 +184,37 @@ class ClipAssembler(nn.Module):
         with torch.no_grad():
             return ops.clip_gather_autoaugment(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len,
                                                self.dilation, plan.contiguous())
+
+    def augmented_normalized(self, bank: FrameBank, index: torch.Tensor, plan: torch.Tensor, augment: ClipAutoAugment,
+                             front_end: ClipFrontEnd, flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check(bank, index)
+        if not isinstance(augment, ClipAutoAugment):
+            raise ValueError(f"augment must be a ClipAutoAugment, got {type(augment).__name__}")
+        if not isinstance(front_end, ClipFrontEnd):
+            raise ValueError(f"front_end must be a ClipFrontEnd, got {type(front_end).__name__}")
+        B, T = index.numel(), self.clip_len
+        H, W, C = bank.frame_shape
+        if C not in (3, 4):
+            raise ValueError(f"the bank has {C} channels; the policy transforms RGB (C = 3) or RGB + mask (C = 4)")
+        if C != front_end.in_channels:
+            raise ValueError(f"front_end: the bank has {C} channels, mean / std have {front_end.in_channels}")
+        if not torch.is_tensor(plan) or plan.dtype != torch.int32:
+            raise ValueError("plan must be an int32 tensor (draw_plan / make_plan)")
+        if tuple(plan.shape) != (B, T, 2, 8):
+            raise ValueError(f"plan must be [{B}, {T}, 2, 8] for these clips, got {tuple(plan.shape)}")
+        flip = front_end._flags(flip, B, bank.device)
+        if self.backend != "hip":
+            return front_end(augment(self._gather(bank, index), plan), flip)
+        if augment.backend != "hip":
+            raise ValueError("ClipAssembler (HIP) runs the policy in its own launch: augment must be ClipAutoAugment(backend='hip')")
+        if front_end.lut.device != bank.device:
+            raise ValueError(f"front_end is on {front_end.lut.device}, the bank on {bank.device}")
+        if not plan.is_cuda:
+            _check_rotate_size(plan, H, W)
+            plan = plan.to(bank.device, non_blocking=True)
+        elif plan.device != bank.device:
+            raise ValueError(f"plan is on {plan.device}, the bank on {bank.device}")
+        with torch.no_grad():
+            return ops.clip_gather_autoaugment_normalize(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len,
+                                                         self.dilation, plan.contiguous(), front_end.lut, front_end.channels, flip,
+                                                         front_end.layout, front_end.out_dtype)

@@ -950,6 +950,33 @@ def clip_autoaugment(clip: torch.Tensor, plan: torch.Tensor, out: Optional[torch
     return out
 
 
+def _planes_out(B: int, T: int, H: int, W: int, Cn: int, lut: torch.Tensor, k: Optional[int], flip: Optional[torch.Tensor],
+                layout: str, out_dtype, device):
+    """the output side that the entry points writing planes share: checks lut fp32 [C, 256] and flip [B], returns k, the avf
+    dtype and layout codes and the empty output"""
+    k = Cn if k is None else int(k)
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (Cn, 256)
+    if flip is not None:
+        assert flip.dtype in (torch.bool, torch.uint8) and flip.is_contiguous() and tuple(flip.shape) == (B,)
+    dt, lay = torch_dtype(out_dtype), CLIP_LAYOUTS[layout]
+    shape = (B, k, T, H, W) if layout == "cthw" else (B, T, k, H, W)
+    return k, avf_dtype(dt), lay, torch.empty(shape, dtype=dt, device=device)
+
+
+def clip_autoaugment_normalize(clip: torch.Tensor, plan: torch.Tensor, lut: torch.Tensor, k: Optional[int] = None,
+                               flip: Optional[torch.Tensor] = None, layout: str = "cthw", out_dtype=torch.float32) -> torch.Tensor:
+    """avf_clip_autoaugment_normalize, one launch: clip_normalize(clip_autoaugment(clip, plan), lut, k, flip, layout, out_dtype)
+    without the augmented uint8 clip in between."""
+    _need_cuda(clip, plan, lut, flip)
+    assert clip.dim() == 5 and clip.dtype == torch.uint8 and clip.is_contiguous()
+    B, T, H, W, Cn = clip.shape
+    assert plan.dtype == torch.int32 and plan.is_contiguous() and tuple(plan.shape) == (B, T, 2, 8)
+    k, dt, lay, out = _planes_out(B, T, H, W, Cn, lut, k, flip, layout, out_dtype, clip.device)
+    _lib.check(_lib.load().avf_clip_autoaugment_normalize(_ptr(clip), B, T, H, W, Cn, _ptr(plan), k, _ptr(lut), _ptr(flip), _ptr(out),
+                                                          dt, lay, _stream()), "clip_autoaugment_normalize")
+    return out
+
+
 def _bank_args(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor):
     """the tensors that the avf_clip_gather* entry points share: bank uint8 [F, H, W, C], video_db_nr int32 [F], present uint8 /
     bool [F] or None, index int64 [B], contiguous and on one device"""
@@ -1011,6 +1038,24 @@ def clip_gather_autoaugment(bank: torch.Tensor, video_db_nr: torch.Tensor, prese
     out = torch.empty(B, T, H, W, Cn, dtype=torch.uint8, device=bank.device)
     _lib.check(_lib.load().avf_clip_gather_autoaugment(_ptr(bank), _ptr(video_db_nr), _ptr(present), _ptr(index), F, B, T, int(d), H,
                                                        W, Cn, _ptr(plan), _ptr(out), _stream()), "clip_gather_autoaugment")
+    return out
+
+
+def clip_gather_autoaugment_normalize(bank: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor],
+                                      index: torch.Tensor, T: int, d: int, plan: torch.Tensor, lut: torch.Tensor,
+                                      k: Optional[int] = None, flip: Optional[torch.Tensor] = None, layout: str = "cthw",
+                                      out_dtype=torch.float32) -> torch.Tensor:
+    """avf_clip_gather_autoaugment_normalize, one launch: clip_normalize(clip_gather_autoaugment(...), lut, k, flip, layout,
+    out_dtype) without a uint8 clip in between - the training transform from the bank."""
+    F, B = _bank_args(bank, video_db_nr, present, index)
+    _need_cuda(plan, lut, flip)
+    _, H, W, Cn = bank.shape
+    T = int(T)
+    assert plan.dtype == torch.int32 and plan.is_contiguous() and tuple(plan.shape) == (B, T, 2, 8)
+    k, dt, lay, out = _planes_out(B, T, H, W, Cn, lut, k, flip, layout, out_dtype, bank.device)
+    _lib.check(_lib.load().avf_clip_gather_autoaugment_normalize(_ptr(bank), _ptr(video_db_nr), _ptr(present), _ptr(index), F, B, T,
+                                                                 int(d), H, W, Cn, _ptr(plan), k, _ptr(lut), _ptr(flip), _ptr(out),
+                                                                 dt, lay, _stream()), "clip_gather_autoaugment_normalize")
     return out
 
 
