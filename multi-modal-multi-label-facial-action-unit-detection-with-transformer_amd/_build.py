@@ -28,9 +28,23 @@ EXTRA_FLAGS = {"gemm_f32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attn_f32_m
                "clip_bank.hip": ["-ffp-contract=off"]}
 
 
+def out_wt() -> int:
+    """AVF_OUT_WT (build-time macro of csrc/common.hpp, passed through from the environment): 1 (default) = the kernels store
+    their outputs write-through, 0 = plain stores.  The value is part of the object directory's and the library's name, so both
+    variants can sit side by side in lib/ and neither is taken for the other."""
+    v = os.environ.get("AVF_OUT_WT", "1").strip() or "1"
+    if v not in ("0", "1"):
+        raise RuntimeError(f"AVF_OUT_WT={v!r}: 0 or 1")
+    return int(v)
+
+
+def _variant() -> str:
+    return "" if out_wt() == 1 else "_wt0"
+
+
 def built_lib_path() -> str:
     """where build() puts the library"""
-    return os.path.join(LIBDIR, LIBNAME)
+    return os.path.join(LIBDIR, LIBNAME.replace(".so", _variant() + ".so"))
 
 
 def lib_path() -> str:
@@ -68,7 +82,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 def _build_locked(force: bool, verbose: bool) -> str:
     hipcc = _hipcc()
-    objdir = os.path.join(LIBDIR, "obj")
+    objdir = os.path.join(LIBDIR, "obj" + _variant())
+    flags = FLAGS + [f"-DAVF_OUT_WT={out_wt()}"]
     os.makedirs(objdir, exist_ok=True)
     jobs = []
     for src in SOURCES:
@@ -79,7 +94,7 @@ def _build_locked(force: bool, verbose: bool) -> str:
 
     def compile_one(job):
         s, o = job
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]
+        cmd = [hipcc] + flags + EXTRA_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {s}:\n{r.stdout}\n{r.stderr}")

@@ -741,10 +741,9 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
           const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
           const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
           if (q < N)
-            *reinterpret_cast<uint4*>(orow + ((lg & 1) ? (d + 1) * 16 + 4 * (lg - 1) : d * 16 + 4 * lg)) =
-                make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            store_out16(orow + ((lg & 1) ? (d + 1) * 16 + 4 * (lg - 1) : d * 16 + 4 * lg), make_uint4(s0[0], s1[0], s0[1], s1[1]));
         }
-        if (q < N && lg == 0) lse2[(int64_t)bh * N + q] = m[qb] + log2f(l);
+        if (q < N && lg == 0) store_out4(lse2 + (int64_t)bh * N + q, m[qb] + log2f(l));
       }
       if (oq) {  // wave-uniform: MX-FP8 image of the output rows (A operand of the out-projection in the fp8 mode); a
                  // 32-block of the head's 64 columns is two 16-column blocks x the 4 lane groups x 4 registers

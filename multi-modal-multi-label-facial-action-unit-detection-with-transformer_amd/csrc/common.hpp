@@ -218,6 +218,58 @@ __device__ __forceinline__ void store4<bf16>(bf16* p, float4 v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// output stores.  A kernel's end makes the eight XCD L2s coherent: every line the kernel left dirty is written back while the
+// chip waits.  store_out16 / store_out8 / store_out4 write 16 / 8 / 4 bytes of an OUTPUT - bytes no wave of the same launch
+// reads back - write-through (sc1), so the line travels during the kernel and is clean at its end.  -DAVF_OUT_WT=0: the plain
+// stores.  Same bytes either way.  Vector stores only; the "memory" clobber keeps them behind the computation, and a 16-byte
+// asm store ends with s_nop 1 (the next instruction must not overwrite its data registers before the store has read them).
+// Users (measured class by class): the NT GEMM epilogues (gemm_nt.hpp), the row8 LayerNorm
+// forward, the head-resident attention forward.  Measured NOT to win and left on plain stores: the merged attention backward,
+// the row8 LayerNorm backward, the grouped dW / fold / token kernels, Adam.  Convert a store only if no wave of the same
+// launch reads the bytes back (assumption, not measured here: a written-through line need not stay in the XCD's L2).
+// ---------------------------------------------------------------------------------------------
+#ifndef AVF_OUT_WT
+#define AVF_OUT_WT 1
+#endif
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_out16(void* p, uint4 v) {
+#if AVF_OUT_WT
+  const u32x4_t w = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(w) : "memory");
+#else
+  *reinterpret_cast<uint4*>(p) = v;
+#endif
+}
+__device__ __forceinline__ void store_out16(void* p, float4 v) {
+  store_out16(p, make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)));
+}
+__device__ __forceinline__ void store_out8(void* p, uint2 v) {
+#if AVF_OUT_WT
+  const u32x2_t w = {v.x, v.y};
+  asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
+#else
+  *reinterpret_cast<uint2*>(p) = v;
+#endif
+}
+__device__ __forceinline__ void store_out8(void* p, float2 v) { store_out8(p, make_uint2(__float_as_uint(v.x), __float_as_uint(v.y))); }
+__device__ __forceinline__ void store_out4(void* p, uint32_t v) {
+#if AVF_OUT_WT
+  asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+#else
+  *reinterpret_cast<uint32_t*>(p) = v;
+#endif
+}
+__device__ __forceinline__ void store_out4(void* p, float v) { store_out4(p, __float_as_uint(v)); }
+// 4 consecutive elements of an output (store4's values)
+template <typename T>
+__device__ __forceinline__ void store4_out(T* p, float4 v);
+template <>
+__device__ __forceinline__ void store4_out<float>(float* p, float4 v) { store_out16(p, v); }
+template <>
+__device__ __forceinline__ void store4_out<bf16>(bf16* p, float4 v) { store_out8(p, make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w))); }
+
+// ---------------------------------------------------------------------------------------------
 // wave (64 lanes) reductions
 // ---------------------------------------------------------------------------------------------
 // Wave-wide reductions on the VALU: four DPP steps inside each row of 16 lanes (quad_perm [1,0,3,2] and [2,3,0,1], row_ror 4

@@ -56,7 +56,7 @@ __device__ __forceinline__ void store_pair16(bf16* row, int n_j, int n_j1, int l
       const u32x4_nt v = {s0[0], s1[0], s0[1], s1[1]};
       __builtin_nontemporal_store(v, reinterpret_cast<u32x4_nt*>(row + col));
     } else {
-      *reinterpret_cast<uint4*>(row + col) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+      store_out16(row + col, make_uint4(s0[0], s1[0], s0[1], s1[1]));
     }
   }
 }
@@ -225,7 +225,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4_t (&acc)[MI
         if (wide_c) {
           cw[j][0] = pack_bf16x2(v[0], v[1]); cw[j][1] = pack_bf16x2(v[2], v[3]);
         } else if (ok) {
-          store4<CT>((CT*)p.C + (int64_t)mm[ii] * p.ldc + nn[j], make_float4(v[0], v[1], v[2], v[3]));
+          store4_out<CT>((CT*)p.C + (int64_t)mm[ii] * p.ldc + nn[j], make_float4(v[0], v[1], v[2], v[3]));
         }
         if (ok) {
 #pragma unroll
@@ -247,7 +247,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4_t (&acc)[MI
 #pragma unroll
           for (int j = 0; j < NI; j += 2)
             // the saved pre-activation is read again in backward only: non-temporal stores keep it out of the caches the
-            // next kernels work from (C2 2.078 -> 2.063 ms per step, C3 2.757 -> 2.747, same box; AVF_NT_WIDE=3: plain stores.
+            // next kernels work from (C2 2.078 -> 2.063 ms per step, C3 2.757 -> 2.747, same box; AVF_NT_WIDE=3: u stored as C is - write-through under AVF_OUT_WT=1.
             // The same hint on its LOAD in the dGELU epilogue changed nothing; on the folded weight gradients it cost 0.8 %:
             // the optimizer then reads them from HBM instead of the Infinity Cache)
             if (p.wide != 3)
@@ -292,8 +292,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4_t (&acc)[MI
 #pragma unroll
       for (int j = 0; j < NI; ++j)
         if (nn[j] < p.N)
-          *reinterpret_cast<float4*>(p.cs_partial + (int64_t)part_row * p.N + nn[j]) =
-              make_float4(cs[j][0], cs[j][1], cs[j][2], cs[j][3]);
+          store_out16(p.cs_partial + (int64_t)part_row * p.N + nn[j], make_float4(cs[j][0], cs[j][1], cs[j][2], cs[j][3]));
     }
   }
 }
@@ -327,7 +326,7 @@ __device__ __forceinline__ void nt_cs_flush(const NtParams& p, float (&cs)[NI][4
   if (li == 0) {
 #pragma unroll
     for (int j = 0; j < NI; ++j)
-      *reinterpret_cast<float4*>(p.cs_partial + (int64_t)part_row * p.N + n0 + 16 * j) = make_float4(cs[j][0], cs[j][1], cs[j][2], cs[j][3]);
+      store_out16(p.cs_partial + (int64_t)part_row * p.N + n0 + 16 * j, make_float4(cs[j][0], cs[j][1], cs[j][2], cs[j][3]));
   }
 }
 // CS: 0 = no column sums; 1 = summed and stored per call (row part_row of cs_partial); 2 = added into the caller's per-lane
@@ -475,9 +474,9 @@ __device__ __forceinline__ void nt_epilogue_lean_body(const NtParams& p, f32x4_t
       if (mok) {
         bf16* crow = (bf16*)p.C + (int64_t)m_base * p.ldc + (uint32_t)(lrow * (uint32_t)p.ldc + (uint32_t)cp0);
 #pragma unroll
-        for (int j = 0; j < NI; j += 2) *reinterpret_cast<uint4*>(crow + 16 * j) = sc[j >> 1];
+        for (int j = 0; j < NI; j += 2) store_out16(crow + 16 * j, sc[j >> 1]);
         if constexpr (EPI == AVF_EPI_BIAS_GELU) {
-          // the saved pre-activation is read again in backward only: non-temporal (as nt_epilogue; p.wide == 3: plain)
+          // the saved pre-activation is read again in backward only: non-temporal (as nt_epilogue; the lean body has no AVF_NT_WIDE=3 arm)
           typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));
           bf16* arow = (bf16*)p.aux + (int64_t)m_base * p.ldaux + (uint32_t)(lrow * (uint32_t)p.ldaux + (uint32_t)cp0);
 #pragma unroll
@@ -490,7 +489,7 @@ __device__ __forceinline__ void nt_epilogue_lean_body(const NtParams& p, f32x4_t
     } else if (mok) {
       float* crow = (float*)p.C + (int64_t)m_base * p.ldc + (uint32_t)(lrow * (uint32_t)p.ldc + (uint32_t)n0);
 #pragma unroll
-      for (int j = 0; j < NI; ++j) *reinterpret_cast<float4*>(crow + 16 * j) = vf[j];
+      for (int j = 0; j < NI; ++j) store_out16(crow + 16 * j, vf[j]);
     }
     if constexpr (MXO) {
       static_assert((NI & 1) == 0, "MX-FP8 image: 32-blocks are column-block pairs");

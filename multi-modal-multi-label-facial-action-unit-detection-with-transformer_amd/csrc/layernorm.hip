@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const bf16* __restrict
   for (int r = 0; r < RU; ++r) {
     if (row0 + r >= rows) break;
     if (lane == 0) {
-      mean[row0 + r] = mu[r];
-      rstd[row0 + r] = rs[r];
+      store_out4(mean + row0 + r, mu[r]);
+      store_out4(rstd + row0 + r, rs[r]);
     }
 #pragma unroll
     for (int i = 0; i < NV8; ++i) {
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const bf16* __restrict
         unpack8(raw[r][i], v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = (v[k] - mu[r]) * rs[r] * gm[i][k] + bt[i][k];
-        *reinterpret_cast<uint4*>(y + (row0 + r) * D + c) = pack8(o);
+        store_out16(y + (row0 + r) * D + c, pack8(o));
         if constexpr (MX) {  // (c < D is uniform over a quad: D % 32 == 0)
           const MxBlock mb = mx8_encode(o);
           *reinterpret_cast<uint2*>(yq + (row0 + r) * D + c) = mb.q;
