@@ -667,6 +667,44 @@ int avf_adam_batch_control(const float* ctl);
 int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
                   void* x_out, void* saved, void* workspace, void* stream);
 
+/* ---- the two ends of a fused stack (the stack's input is cat([clip, audio], 1) + pos) on the all-bf16 streams --------------
+ * Both apply to a layer with dtype AVF_BF16, resid_bf16 and grad_stream_bf16 set, dropout_p == 0, no mx8 and no key mask
+ * (dim % 8 == 0 follows from resid_bf16); the _ok functions answer 1 where the entry next to them can run, and a caller takes
+ * avf_fuse_tokens_bf16 + avf_layer_fwd, or avf_layer_bwd[_dx] + a column sum of dx_in, where they answer 0.
+ *   avf_layer_fwd_embed: avf_layer_fwd for the bottom layer without the separate embedding pass.  LayerNorm-1 builds each row as
+ *     bf16(clip[b, t] or audio[b, t - t_video], + pos[t]) - avf_fuse_tokens_bf16's values and rounding - and also stores it as
+ *     x0 [B*N, D] bf16, the tensor to pass as x_in to the backward of this layer.  clip [B, t_video, D], audio [B, N - t_video,
+ *     D], pos [N, D]: fp32, 16-byte aligned, 0 < t_video < N.  x0, x_out and everything saved are bit-identical to the two calls.
+ *   avf_layer_bwd_pos / avf_layer_bwd_dx_pos: avf_layer_bwd / avf_layer_bwd_dx for the bottom layer when below it only
+ *     d pos_embedding is wanted: d_pos[t, :] = sum_b dx_in[b * N + t, :], fp32 [N, D], written by a token-major LayerNorm-1
+ *     backward.  No dx_in, dx_in_lo or dx_in_colsum is produced.  batch must be within the token-major rule (layernorm.hip,
+ *     LNR8_TOK_MAX_BATCH).  d_pos and this layer's LayerNorm-1 gradients are summed in another order than by the plain entries
+ *     (fp32 rounding level), deterministically; every other gradient is bit-identical. */
+int avf_layer_fwd_embed_ok(const avf_layer_cfg* cfg);
+/* ... and the two LayerNorm launches behind them as operators.  avf_layernorm_fwd_embed: x0 = bf16(cat([clip, audio], 1) + pos)
+ * [B*(t_video+t_audio), D] and y (bf16), mean, rstd = LayerNorm(x0); dim % 8 == 0, dim <= 1536, t_video > 0, t_audio > 0.
+ * avf_layernorm_bwd_pos: the all-bf16 LayerNorm backward (dy, x, dres [batch*tokens, D] bf16; dres nullable) reduced over the
+ * clips: d_pos [tokens, D] fp32, dgamma, dbeta; workspace of avf_layernorm_bwd_pos_workspace_bytes; _ok: the batch is within
+ * the token-major rule. */
+int avf_layernorm_fwd_embed(const float* clip, const float* audio, const float* pos, int batch, int t_video, int t_audio,
+                            void* x0_bf16, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd, int dim,
+                            float eps, void* stream);
+int avf_layernorm_bwd_pos_ok(int batch, int tokens, int dim);
+size_t avf_layernorm_bwd_pos_workspace_bytes(int batch, int tokens, int dim);
+int avf_layernorm_bwd_pos(const void* dy_bf16, const void* x_bf16, const float* gamma, const float* mean, const float* rstd,
+                          const void* dres_bf16, float* d_pos, float* dgamma, float* dbeta, void* workspace, int batch, int tokens,
+                          int dim, void* stream);
+int avf_layer_fwd_embed(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const float* clip,
+                        const float* audio, const float* pos, int t_video, void* x0, void* x_out, void* saved, void* workspace,
+                        void* stream);
+int avf_layer_bwd_pos_ok(const avf_layer_cfg* cfg);
+int avf_layer_bwd_pos(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                      const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum, float* d_pos,
+                      const avf_layer_grads* g, void* workspace, void* stream);
+int avf_layer_bwd_dx_pos(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                         const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum, float* d_pos,
+                         const avf_layer_grads* g, void* workspace, void* dw_block, void* dw_desc, void* stream);
+
 /* dx_in (fp32) and all parameter gradients from dx_out (fp32).  dx_out_lo: optional bf16 copy of dx_out
  * (null => made internally); dx_in_lo: optional bf16 copy of dx_in to hand to the previous layer (with dropout
  * active it already carries layer_index-1's site-2 mask, which is what that layer's MLP gradients consume).

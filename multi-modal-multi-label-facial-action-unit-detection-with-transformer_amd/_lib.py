@@ -159,6 +159,17 @@ SIGNATURES = {
     "avf_layer_fwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp]),
     "avf_layer_bwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              C.POINTER(LayerPtrs), _vp, _vp]),
+    "avf_layernorm_fwd_embed": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _f, _vp]),
+    "avf_layernorm_bwd_pos_ok": (_int, [_int, _int, _int]),
+    "avf_layernorm_bwd_pos_workspace_bytes": (_sz, [_int, _int, _int]),
+    "avf_layernorm_bwd_pos": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
+    "avf_layer_fwd_embed_ok": (_int, [C.POINTER(LayerCfg)]),
+    "avf_layer_fwd_embed": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "avf_layer_bwd_pos_ok": (_int, [C.POINTER(LayerCfg)]),
+    "avf_layer_bwd_pos": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 C.POINTER(LayerPtrs), _vp, _vp]),
+    "avf_layer_bwd_dx_pos": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp]),
     "avf_layer_dw_defer_ok": (_int, [C.POINTER(LayerCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_layers_dw_max": (_int, []),
     "avf_layer_dw_block_bytes": (_sz, [C.POINTER(LayerCfg)]),

@@ -214,6 +214,25 @@ extern "C" int avf_layernorm_bwd_ex(const void* dy, int dy_dtype, const void* x,
   return layernorm_bwd(dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dx_lo, dgamma, dbeta, dcolsum, workspace, rows, dim,
                        (hipStream_t)stream, d, nullptr, dres ? dres_dtype : AVF_F32, x_dtype, nullptr, nullptr, dx_m);
 }
+// the two ends of a fused stack as operators (what avf_layer_fwd_embed / avf_layer_bwd_pos run for LayerNorm-1 of the bottom layer)
+extern "C" int avf_layernorm_fwd_embed(const float* clip, const float* audio, const float* pos, int batch, int t_video, int t_audio,
+                                       void* x0_bf16, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd,
+                                       int dim, float eps, void* stream) {
+  AVF_REQUIRE(gamma && beta, "layernorm_fwd_embed: null pointer");
+  return layernorm_fwd_embed(clip, audio, pos, batch, t_video, t_audio, x0_bf16, gamma, beta, y_bf16, mean, rstd, dim, eps,
+                             (hipStream_t)stream);
+}
+extern "C" int avf_layernorm_bwd_pos_ok(int batch, int tokens, int dim) { return layernorm_bwd_tok_ok(batch, tokens, dim) ? 1 : 0; }
+extern "C" size_t avf_layernorm_bwd_pos_workspace_bytes(int batch, int tokens, int dim) {
+  return layernorm_bwd_ws((int64_t)batch * tokens, dim, tokens);
+}
+extern "C" int avf_layernorm_bwd_pos(const void* dy_bf16, const void* x_bf16, const float* gamma, const float* mean, const float* rstd,
+                                     const void* dres_bf16, float* d_pos, float* dgamma, float* dbeta, void* workspace, int batch,
+                                     int tokens, int dim, void* stream) {
+  AVF_REQUIRE(dgamma && dbeta, "layernorm_bwd_pos: null pointer");
+  return layernorm_bwd_tok(dy_bf16, x_bf16, gamma, mean, rstd, dres_bf16, d_pos, dgamma, dbeta, workspace, batch, tokens, dim,
+                           (hipStream_t)stream);
+}
 extern "C" size_t avf_colsum_workspace_bytes(int64_t rows, int cols) { return colsum_ws(rows, cols); }
 extern "C" int avf_colsum(const void* in, int in_dtype, int64_t rows, int cols, int64_t ld, float* out,
                           void* workspace, void* stream) {

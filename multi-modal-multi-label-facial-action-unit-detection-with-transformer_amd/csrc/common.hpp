@@ -414,7 +414,16 @@ struct FoldJob;
 int layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
                   float* rstd, int64_t rows, int dim, float eps, hipStream_t s, void* mx_q = nullptr, void* mx_s = nullptr,
                   int x_dtype = AVF_F32);
-size_t layernorm_bwd_ws(int64_t rows, int dim);
+size_t layernorm_bwd_ws(int64_t rows, int dim, int tokens = 0);
+// the two ends of a fused stack on the all-bf16 streams (layernorm.hip): embed + LayerNorm in one launch, and d pos_embedding
+// straight from the bottom LayerNorm backward
+bool layernorm_fwd_embed_ok(int dim);
+int layernorm_fwd_embed(const float* clip, const float* audio, const float* pos, int batch, int t_video, int t_audio, void* x0,
+                        const float* gamma, const float* beta, void* y, float* mean, float* rstd, int dim, float eps, hipStream_t s);
+bool layernorm_bwd_tok_ok(int batch, int tokens, int dim);
+int layernorm_bwd_tok(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres,
+                      float* dpos, float* dgamma, float* dbeta, void* ws, int batch, int tokens, int dim, hipStream_t s,
+                      FoldJob* defer_fold = nullptr);
 // drop: mask applied to the bf16 copy dx_lo AND to the column sums (they feed the Linear behind a dropout site);
 // dx itself (the residual stream gradient) is never masked.
 // dres_dtype AVF_BF16 (bf16 gradient stream): dres is read as bf16, dx may be null (dx_lo is then the only output).

@@ -229,7 +229,7 @@ size_t carve_work(const Dims& d, void* base, Work* w) {
   t.dx_out_lo = c.take(d.dt == AVF_BF16 ? d.R * d.D * 2 : 0);
   t.delta = (float*)c.take((size_t)d.B * d.H * d.N * 4 * 2);  // delta, then the negated lse2 rows (bf16 backward)
   t.ln_ws = c.take(layernorm_bwd_ws(d.R, d.D));
-  t.ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D));  // LN1 partials (its fold may be deferred past LN2's)
+  t.ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D, d.N));  // LN1 partials (its fold may be deferred past LN2's; token-major: one row per token)
   t.cs_ws = c.take(work_colsum_bytes(d));
   size_t g = 0;
   if (d.dt == AVF_BF16) {
@@ -289,7 +289,7 @@ size_t carve_dw_block(const Dims& d, void* base, Work* w) {
   void* dx_mid_lo = c.take(d.R * d.D * 2);
   void* dx_out_lo = c.take(d.R * d.D * 2);
   void* ln_ws = c.take(layernorm_bwd_ws(d.R, d.D));
-  void* ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D));
+  void* ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D, d.N));
   void* cs_ws = c.take(work_colsum_bytes(d));
   if (w) {
     w->du = du; w->dqkv = dqkv; w->dx_mid_lo = dx_mid_lo; w->dx_out_lo = dx_out_lo;
@@ -482,10 +482,38 @@ extern "C" int avf_stack_quant_weights_mx8(const avf_layer_cfg* cfg, int layers,
   return quant_mx8_multi(jobs, n, (hipStream_t)stream);
 }
 
-extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
-                             void* x_out, void* saved, void* workspace, void* stream) {
+// The two ends of a fused stack (avf_layer_fwd_embed, avf_layer_bwd_pos / avf_layer_bwd_dx_pos): the all-bf16 streams of the
+// general bf16 layer - no dropout, no MX-FP8 images, no key mask - on the row8 LayerNorm kernels.  A caller asks the _ok function
+// and takes the plain entry points where it says no (the stack's own switch for A/B runs is AVF_STACK_ENDS, transformer.py).
+static bool stack_ends_mode_ok(const Dims& d) {
+  return d.dt == AVF_BF16 && d.rs16 && d.gs16 && !d.gsd && d.p == 0.f && !d.mx && !d.mxb &&
+         !d.keep && d.D % 8 == 0 && d.D <= 1536;
+}
+extern "C" int avf_layer_fwd_embed_ok(const avf_layer_cfg* cfg) {
+  Dims d;
+  return !make_dims(cfg, &d) && stack_ends_mode_ok(d) && layernorm_fwd_embed_ok(d.D);
+}
+extern "C" int avf_layer_bwd_pos_ok(const avf_layer_cfg* cfg) {
+  Dims d;
+  return !make_dims(cfg, &d) && stack_ends_mode_ok(d) && layernorm_bwd_tok_ok(d.B, d.N, d.D);
+}
+
+// emb (avf_layer_fwd_embed): the layer's input is cat([clip, audio], 1) + pos; LayerNorm-1 builds it and stores it as emb->x0
+struct EmbedSrc {
+  const float *clip, *audio, *pos;
+  int t_video;
+  void* x0;
+};
+static int layer_fwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in, void* x_out,
+                          void* saved, void* workspace, void* stream, const EmbedSrc* emb) {
   Dims d;
   AVF_TRY(make_dims(cfg, &d));
+  if (emb) {
+    AVF_REQUIRE(stack_ends_mode_ok(d) && layernorm_fwd_embed_ok(d.D) && emb->x0 && emb->t_video > 0 && emb->t_video < d.N,
+                "layer_fwd_embed: needs the all-bf16 streams without dropout, fp8 or mask, and both token groups (ask "
+                "avf_layer_fwd_embed_ok first)");
+    x_in = emb->x0;
+  }
   AVF_REQUIRE(p && x_in && x_out && saved, "layer_fwd: null pointer");
   AVF_REQUIRE(d.dt == AVF_F32 || lowp, "layer_fwd(bf16): lowp weights missing");
   hipStream_t s = (hipStream_t)stream;
@@ -538,7 +566,11 @@ extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p
                            make_drop(d.p0, d.seed, d.layer, 0, d.seed_dev), make_drop(d.p, d.seed, d.layer, 1, d.seed_dev),
                            make_drop(d.p, d.seed, d.layer, 2, d.seed_dev), s);
   }
-  AVF_TRY(layernorm_fwd(x_in, p->ln1_w, p->ln1_b, sv.h1, d.dt, sv.mean1, sv.rstd1, d.R, d.D, cfg->ln_eps, s, nullptr, nullptr, d.xdt));
+  if (emb)
+    AVF_TRY(layernorm_fwd_embed(emb->clip, emb->audio, emb->pos, d.B, emb->t_video, d.N - emb->t_video, emb->x0, p->ln1_w, p->ln1_b,
+                                sv.h1, sv.mean1, sv.rstd1, d.D, cfg->ln_eps, s));
+  else
+    AVF_TRY(layernorm_fwd(x_in, p->ln1_w, p->ln1_b, sv.h1, d.dt, sv.mean1, sv.rstd1, d.R, d.D, cfg->ln_eps, s, nullptr, nullptr, d.xdt));
   AVF_TRY(linear_fwd(d, sv.h1, d.D, wqkv, 3 * d.I, sv.qkv, d.dt, AVF_EPI_NONE, nullptr, nullptr, nullptr, s, kNoDrop, l.ws.wqkv_p));
   // token mask (heads.py:225-232): on the MFMA kernels where they carry it (bf16, dim_head 64, up to 512 tokens), else on
   // the fp32-arithmetic ones (attn_fwd_masked_bf16 chooses)
@@ -555,22 +587,40 @@ extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p
   return 0;
 }
 
+extern "C" int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                             void* x_out, void* saved, void* workspace, void* stream) {
+  return layer_fwd_impl(cfg, p, lowp, x_in, x_out, saved, workspace, stream, nullptr);
+}
+
+extern "C" int avf_layer_fwd_embed(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const float* clip,
+                                   const float* audio, const float* pos, int t_video, void* x0, void* x_out, void* saved,
+                                   void* workspace, void* stream) {
+  const EmbedSrc emb{clip, audio, pos, t_video, x0};
+  return layer_fwd_impl(cfg, p, lowp, nullptr, x_out, saved, workspace, stream, &emb);
+}
+
 // dw_block / dw_desc (both or neither): the weight gradients and the column folds of the layer are NOT launched - their
 // operands stay in dw_block and dw_desc describes them for avf_layers_dw
 static int layer_bwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
                           const void* saved, const float* dx_out, const void* dx_out_lo,
                           const float* dx_out_colsum, float* dx_in, void* dx_in_lo, float* dx_in_colsum,
-                          const avf_layer_grads* g, void* workspace, void* stream, void* dw_block, DwDeferred* dw_desc) {
+                          const avf_layer_grads* g, void* workspace, void* stream, void* dw_block, DwDeferred* dw_desc,
+                          float* d_pos = nullptr) {
+  // d_pos (avf_layer_bwd_pos / avf_layer_bwd_dx_pos, the bottom layer of a fused stack): LayerNorm-1 backward runs token-major
+  // and writes d pos_embedding [N, D] instead of dx_in / dx_in_lo, which are then not asked for
   Dims d;
   AVF_TRY(make_dims(cfg, &d));
+  AVF_REQUIRE(!d_pos || (stack_ends_mode_ok(d) && layernorm_bwd_tok_ok(d.B, d.N, d.D) && !dx_in && !dx_in_lo && !dx_in_colsum),
+              "layer_bwd_pos: needs the all-bf16 streams without dropout, fp8 or mask, a batch within the token-major rule (ask "
+              "avf_layer_bwd_pos_ok first) and no dx_in outputs");
   AVF_REQUIRE(!dw_desc || (dw_block && dw_defer_mode_ok(d) && ((uintptr_t)dw_block & 255) == 0),
               "layer_bwd_dx: this mode keeps its weight gradients in the layer (ask avf_layer_dw_defer_ok first), or the "
               "operand block is missing / not 256-byte aligned");
   AVF_REQUIRE(p && x_in && saved && g && workspace, "layer_bwd: null pointer");
   // bf16 gradient stream: the incoming gradient may come as its bf16 image alone, and the fp32 dx_in is optional (a caller
   // asks for it only where it consumes it, e.g. below the bottom layer)
-  AVF_REQUIRE(d.gs16 ? (dx_out || dx_out_lo) && (dx_in || dx_in_lo) : (dx_out && dx_in), "layer_bwd: null gradient pointer");
-  AVF_REQUIRE(!d.gs16 || dx_in_lo, "layer_bwd(grad_stream_bf16): dx_in_lo missing");
+  AVF_REQUIRE(d.gs16 ? (dx_out || dx_out_lo) && (dx_in || dx_in_lo || d_pos) : (dx_out && dx_in), "layer_bwd: null gradient pointer");
+  AVF_REQUIRE(!d.gs16 || dx_in_lo || d_pos, "layer_bwd(grad_stream_bf16): dx_in_lo missing");
   AVF_REQUIRE(d.dt == AVF_F32 || lowp, "layer_bwd(bf16): lowp weights missing");
   hipStream_t s = (hipStream_t)stream;
   Saved sv;
@@ -794,7 +844,10 @@ static int layer_bwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, c
   else
     AVF_TRY(linear_dx(d, w.dqkv, 3 * d.I, p->w_qkv, l.wqkv_t, d.D, w.dh, AVF_EPI_NONE, nullptr, s));
   // dx_in may alias dx_out, which the grouped dW2 GEMM does not read (it uses the bf16 copy gy)
-  if (d.gs16)  // (gsd: the masked image for the layer below goes behind the stream in dx_in_lo; layer 0 has no site below it)
+  if (d_pos)
+    AVF_TRY(layernorm_bwd_tok(w.dh, x_in, p->ln1_w, sv.mean1, sv.rstd1, w.dx_mid_lo, d_pos, g->ln1_w, g->ln1_b, w.ln_ws1, d.B, d.N,
+                              d.D, s, grouped ? &folds.job[2] : nullptr));
+  else if (d.gs16)  // (gsd: the masked image for the layer below goes behind the stream in dx_in_lo; layer 0 has no site below it)
     AVF_TRY(layernorm_bwd(w.dh, d.dt, x_in, p->ln1_w, sv.mean1, sv.rstd1, w.dx_mid_lo, dx_in, dx_in_lo, g->ln1_w, g->ln1_b,
                           dx_in_colsum, w.ln_ws1, d.R, d.D, s, dr_prev2, grouped ? &folds.job[2] : nullptr, AVF_BF16, d.xdt,
                           inq, ins, (d.gsd && dr_prev2.thresh16) ? (char*)dx_in_lo + grad_q_off(d.R, d.D) : nullptr));
@@ -846,6 +899,23 @@ extern "C" size_t avf_layer_dw_block_bytes(const avf_layer_cfg* cfg) {
   return align_up(carve_dw_block(d, nullptr, nullptr), 256);
 }
 extern "C" size_t avf_layer_dw_desc_bytes(void) { return sizeof(DwDeferred); }
+
+// the bottom layer of a fused stack when only d pos_embedding is wanted below it (see layer_bwd_impl, d_pos)
+extern "C" int avf_layer_bwd_pos(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                                 const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum,
+                                 float* d_pos, const avf_layer_grads* g, void* workspace, void* stream) {
+  AVF_REQUIRE(d_pos, "layer_bwd_pos: null d_pos");
+  return layer_bwd_impl(cfg, p, lowp, x_in, saved, dx_out, dx_out_lo, dx_out_colsum, nullptr, nullptr, nullptr, g, workspace, stream,
+                        nullptr, nullptr, d_pos);
+}
+extern "C" int avf_layer_bwd_dx_pos(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
+                                    const void* saved, const float* dx_out, const void* dx_out_lo, const float* dx_out_colsum,
+                                    float* d_pos, const avf_layer_grads* g, void* workspace, void* dw_block, void* dw_desc,
+                                    void* stream) {
+  AVF_REQUIRE(d_pos && dw_block && dw_desc, "layer_bwd_dx_pos: null d_pos / operand block / descriptor");
+  return layer_bwd_impl(cfg, p, lowp, x_in, saved, dx_out, dx_out_lo, dx_out_colsum, nullptr, nullptr, nullptr, g, workspace, stream,
+                        dw_block, (DwDeferred*)dw_desc, d_pos);
+}
 
 extern "C" int avf_layer_bwd_dx(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const void* x_in,
                                 const void* saved, const float* dx_out, const void* dx_out_lo,

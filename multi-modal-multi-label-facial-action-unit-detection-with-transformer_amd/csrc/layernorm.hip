@@ -155,8 +155,44 @@ static int ln_row8_on() {
 // flight before the first reduction: 4 x 4 rows per workgroup, ~10 waves per CU x RU KiB per stream in flight (the
 // one-row-per-wave form had 1 KiB per wave and ran at 2.5 TB/s; DESIGN_HISTORY.md section 14).
 // MX: also the MX-FP8 image of the rows (D % 32 == 0: a 32-block is the 8 columns of the four lanes of a quad)
-template <int NV8, int RU, bool MX = false>
-__global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const bf16* __restrict__ x, const float* __restrict__ gamma,
+// Src: where a row comes from.  LnRowBf16: the bf16 residual stream.  LnRowEmbed (the bottom layer of a fused stack): row b * T + t
+// is bf16(clip[b, t] or audio[b, t - Tv], + pos[t]) - fuse_tokens_kernel<bf16>'s values and rounding (one fp32 add, pack8) - and is
+// also stored as x0, the stream the rest of the layer reads; the statistics are those of the rounded values, so x0, y, mean and
+// rstd are the bits the two launches gave (one pass over the fp32 inputs instead of a bf16 round trip through memory).
+struct LnRowBf16 {
+  static constexpr bool kStoresRow = false;
+  const bf16* __restrict__ x;
+  struct Row { const bf16* p; };
+  __device__ __forceinline__ Row row(int64_t r, int D) const { return Row{x + r * D}; }
+  __device__ __forceinline__ uint4 load(const Row& r, int c) const { return *reinterpret_cast<const uint4*>(r.p + c); }
+  __device__ __forceinline__ void store_row(int64_t, int, int, uint4) const {}
+};
+struct LnRowEmbed {
+  static constexpr bool kStoresRow = true;
+  const float* __restrict__ clip;
+  const float* __restrict__ audio;
+  const float* __restrict__ pos;
+  bf16* __restrict__ x0;
+  int Tv, Ta;
+  struct Row { const float *p, *e; };
+  __device__ __forceinline__ Row row(int64_t r, int D) const {
+    const int T = Tv + Ta;
+    const int64_t b = r / T;
+    const int t = (int)(r - b * T);
+    return Row{t < Tv ? clip + (b * Tv + t) * D : audio + (b * Ta + (t - Tv)) * D, pos + (int64_t)t * D};
+  }
+  __device__ __forceinline__ uint4 load(const Row& r, int c) const {
+    float4 v0 = *reinterpret_cast<const float4*>(r.p + c), v1 = *reinterpret_cast<const float4*>(r.p + c + 4);
+    const float4 p0 = *reinterpret_cast<const float4*>(r.e + c), p1 = *reinterpret_cast<const float4*>(r.e + c + 4);
+    v0.x += p0.x; v0.y += p0.y; v0.z += p0.z; v0.w += p0.w;
+    v1.x += p1.x; v1.y += p1.y; v1.z += p1.z; v1.w += p1.w;
+    const float o[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    return pack8(o);
+  }
+  __device__ __forceinline__ void store_row(int64_t r, int D, int c, uint4 v) const { store_out16(x0 + r * D + c, v); }
+};
+template <int NV8, int RU, bool MX = false, typename Src = LnRowBf16>
+__global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const Src src, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, bf16* __restrict__ y,
                                                           float* __restrict__ mean, float* __restrict__ rstd, int64_t rows,
                                                           int D, float eps, uint8_t* __restrict__ yq = nullptr,
@@ -168,10 +204,11 @@ __global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const bf16* __restrict
 #pragma unroll
   for (int r = 0; r < RU; ++r) {
     const int64_t row = row0 + r < rows ? row0 + r : rows - 1;  // (rows past the end re-read the last one; nothing is stored)
+    const typename Src::Row sr = src.row(row, D);
 #pragma unroll
     for (int i = 0; i < NV8; ++i) {
       const int c = lane * 8 + 512 * i;
-      raw[r][i] = c < D ? *reinterpret_cast<const uint4*>(x + row * D + c) : make_uint4(0u, 0u, 0u, 0u);
+      raw[r][i] = c < D ? src.load(sr, c) : make_uint4(0u, 0u, 0u, 0u);
     }
   }
   float gm[NV8][8], bt[NV8][8];
@@ -229,6 +266,7 @@ __global__ __launch_bounds__(256) void ln_fwd_row8_kernel(const bf16* __restrict
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = (v[k] - mu[r]) * rs[r] * gm[i][k] + bt[i][k];
         store_out16(y + (row0 + r) * D + c, pack8(o));
+        if constexpr (Src::kStoresRow) src.store_row(row0 + r, D, c, raw[r][i]);
         if constexpr (MX) {  // (c < D is uniform over a quad: D % 32 == 0)
           const MxBlock mb = mx8_encode(o);
           *reinterpret_cast<uint2*>(yq + (row0 + r) * D + c) = mb.q;
@@ -256,13 +294,15 @@ static int launch_ln_fwd_reg(const TimingScope* ts, hipStream_t s, const InT* x,
   return check_launch(sizeof(InT) == 2 ? "ln_fwd_reg_kernel(bf16 in)" : MX ? "ln_fwd_reg_kernel(mx)" : "ln_fwd_kernel");
 }
 
-template <int NV8, bool MX>
-static int launch_ln_fwd_row8(const TimingScope* ts, hipStream_t s, const bf16* x, const float* gamma, const float* beta, bf16* y,
+template <int NV8, bool MX, typename Src>
+static int launch_ln_fwd_row8(const TimingScope* ts, hipStream_t s, const Src& src, const float* gamma, const float* beta, bf16* y,
                               float* mean, float* rstd, int64_t rows, int D, float eps, uint8_t* yq, uint8_t* ys) {
-  constexpr int RU = 4;  // four rows per wave, 16-byte accesses
-  launch_in_scope(ts, ln_fwd_row8_kernel<NV8, RU, MX>, dim3((unsigned)ceil_div(rows, 4 * RU)), dim3(256), 0, s, x, gamma, beta, y,
-                  mean, rstd, rows, D, eps, yq, ys);
-  return check_launch("ln_fwd_row8_kernel");
+  // four rows per wave, 16-byte accesses; two where the rows are built from the fp32 inputs (twice the bytes in flight per row:
+  // C2's embed launch 13.5 us at two rows, 17.1 at four - the two launches it stands for took 10.4 + 7.7)
+  constexpr int RU = Src::kStoresRow ? 2 : 4;
+  launch_in_scope(ts, ln_fwd_row8_kernel<NV8, RU, MX, Src>, dim3((unsigned)ceil_div(rows, 4 * RU)), dim3(256), 0, s, src, gamma, beta,
+                  y, mean, rstd, rows, D, eps, yq, ys);
+  return check_launch(Src::kStoresRow ? "ln_fwd_row8_kernel(embed)" : "ln_fwd_row8_kernel");
 }
 
 int layernorm_fwd(const void* xv, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
@@ -284,8 +324,8 @@ int layernorm_fwd(const void* xv, const float* gamma, const float* beta, void* y
   };
   if (x_dtype == AVF_BF16 && dim % 8 == 0 && (!mx_q || (mx_s && dim % 32 == 0)) && ln_row8_on()) {
     return ln_nv8(dim, [&](auto nv8, auto) {
-      if (mx_q) return launch_ln_fwd_row8<decltype(nv8)::value, true>(&ts, s, xb, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps, yq, ys);
-      return launch_ln_fwd_row8<decltype(nv8)::value, false>(&ts, s, xb, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps, yq, ys);
+      if (mx_q) return launch_ln_fwd_row8<decltype(nv8)::value, true>(&ts, s, LnRowBf16{xb}, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps, yq, ys);
+      return launch_ln_fwd_row8<decltype(nv8)::value, false>(&ts, s, LnRowBf16{xb}, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps, yq, ys);
     });
   }
   if (x_dtype == AVF_BF16) {  // bf16 residual stream: bf16 in, bf16 out (+ optional MX-FP8 image)
@@ -300,6 +340,24 @@ int layernorm_fwd(const void* xv, const float* gamma, const float* beta, void* y
   if (dim % 4 == 0 && dim <= 1536) return y_dtype == AVF_F32 ? reg(std::false_type{}, x, (float*)y) : reg(std::false_type{}, x, (bf16*)y);
   if (y_dtype == AVF_F32) return launch_ln_fwd(&ts, s, x, gamma, beta, (float*)y, mean, rstd, rows, dim, eps);
   return launch_ln_fwd(&ts, s, x, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps);
+}
+
+bool layernorm_fwd_embed_ok(int dim) { return dim % 8 == 0 && dim <= 1536 && ln_row8_on(); }
+
+// x0 = bf16(cat([clip, audio], 1) + pos) and y, mean, rstd = LayerNorm(x0) in one launch (LnRowEmbed)
+int layernorm_fwd_embed(const float* clip, const float* audio, const float* pos, int batch, int t_video, int t_audio, void* x0,
+                        const float* gamma, const float* beta, void* y, float* mean, float* rstd, int dim, float eps, hipStream_t s) {
+  AVF_REQUIRE(batch > 0 && t_video > 0 && t_audio > 0 && clip && audio && pos && x0 && y && mean && rstd,
+              "layernorm_fwd_embed: bad arguments (both token groups and the positional rows are needed)");
+  AVF_REQUIRE(layernorm_fwd_embed_ok(dim), "layernorm_fwd_embed: needs dim %% 8 == 0, dim <= 1536 and the row8 kernels (dim=%d)", dim);
+  AVF_REQUIRE((((uintptr_t)clip | (uintptr_t)audio | (uintptr_t)pos | (uintptr_t)x0 | (uintptr_t)y) & 15) == 0,
+              "layernorm_fwd_embed: pointers must be 16-byte aligned");
+  const int64_t rows = (int64_t)batch * (t_video + t_audio);
+  TimingScope ts(KC_LAYERNORM, 0.0, (double)rows * dim * (4.0 + 2.0 + 2.0) + (double)(t_video + t_audio) * dim * 4.0, s, /*per_kernel=*/true);
+  const LnRowEmbed src{clip, audio, pos, (bf16*)x0, t_video, t_audio};
+  return ln_nv8(dim, [&](auto nv8, auto) {
+    return launch_ln_fwd_row8<decltype(nv8)::value, false>(&ts, s, src, gamma, beta, (bf16*)y, mean, rstd, rows, dim, eps, nullptr, nullptr);
+  });
 }
 
 // =============================================================================================
@@ -513,7 +571,12 @@ __global__ __launch_bounds__(256) void ln_bwd_reg_kernel(const DyT* __restrict__
 // DROP (round 5): live dropout on the all-bf16 streams.  The row gradient leaves TWICE: dx_lo = the residual-gradient stream
 // (never masked: the next LayerNorm backward's dres) and dx_m = what the Linear behind the dropout site sees (masked, rescaled:
 // the GEMM operand; the column sums - that Linear's bias gradient - are those of the MASKED values, as ln_bwd_reg_kernel's).
-template <int NV8, int RU, bool DROP = false>
+// TOK (the bottom layer of a fused stack whose clip / audio gradients nobody asks for): token-major.  The workgroup owns token
+// blockIdx.x and walks that token's rows b * tokN + token over the clips b, batch (k, wave) taking clips (4 k + wave) RU ...
+// + RU - 1.  The column sums of dx over those rows are row `token` of d pos_embedding: acs accumulates them over the clips and
+// they leave through the same wave-ordered combine, so the row gradient itself is never stored (no dx_lo, no fp32 dx, no
+// column-sum pass over it); dgamma / dbeta leave as one partial row per workgroup as before.  Deterministic like the rest.
+template <int NV8, int RU, bool DROP = false, bool TOK = false>
 __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
                                                           const float* __restrict__ rstd, const bf16* __restrict__ dres,
@@ -521,7 +584,8 @@ __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict
                                                           int D, int want_colsum, uint8_t* __restrict__ dxq = nullptr,
                                                           uint8_t* __restrict__ dxs = nullptr, float* __restrict__ dx = nullptr,
                                                           DropCfg drop = kNoDrop, bf16* __restrict__ dx_m = nullptr,
-                                                          int rpb = LNR_ROWS_PER_BLOCK) {
+                                                          int rpb = LNR_ROWS_PER_BLOCK, int tokN = 0,
+                                                          float* __restrict__ dpos = nullptr) {
   // dx (optional, wave-uniform): the fp32 copy of the row gradient (the bottom layer hands it to the caller)
   // rpb: rows per workgroup, a multiple of 4 RU (host: lnr8_rows_per_block) - a wave's rows come in whole batches of RU
   uint64_t dkey = 0;
@@ -544,12 +608,15 @@ __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict
   const float invD = 1.0f / (float)D;
 #pragma unroll 1
   for (int batch = 0; batch < rpb / 4 / RU; ++batch) {
-  const int64_t row0 = (int64_t)blockIdx.x * rpb + wave * (rpb / 4) + batch * RU;
+  // i0 .. i0 + RU - 1 of iend: the batch's rows (TOK: its clips, the row of clip i being i * tokN + this workgroup's token)
+  const int64_t i0 = TOK ? (int64_t)(batch * 4 + wave) * RU : (int64_t)blockIdx.x * rpb + wave * (rpb / 4) + batch * RU;
+  const int64_t iend = TOK ? rows / tokN : rows;
+  const auto row_of = [&](int64_t i) { return TOK ? i * tokN + blockIdx.x : i; };
   uint4 rd[RU][NV8], rx[RU][NV8], rr[RU][NV8];
   float mu[RU], rs[RU];
 #pragma unroll
   for (int r = 0; r < RU; ++r) {
-    const int64_t row = row0 + r < rows ? row0 + r : rows - 1;
+    const int64_t row = row_of(i0 + r < iend ? i0 + r : iend - 1);
 #pragma unroll
     for (int i = 0; i < NV8; ++i) {
       const int c = lane * 8 + 512 * i;
@@ -590,7 +657,8 @@ __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict
   }
 #pragma unroll
   for (int r = 0; r < RU; ++r) {
-    if (row0 + r >= rows) break;
+    if (i0 + r >= iend) break;
+    const int64_t row = row_of(i0 + r);
 #pragma unroll
     for (int i = 0; i < NV8; ++i) {
       const int c = lane * 8 + 512 * i;
@@ -607,24 +675,25 @@ __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict
         adb[i][k] += d[k];
         if constexpr (!DROP) acs[i][k] += o[k];
       }
-      *reinterpret_cast<uint4*>(dx_lo + (row0 + r) * D + c) = pack8(o);
+      if constexpr (TOK) continue;  // (nothing of the row leaves: its column sums are the output)
+      *reinterpret_cast<uint4*>(dx_lo + row * D + c) = pack8(o);
       if (dx) {
-        *reinterpret_cast<float4*>(dx + (row0 + r) * D + c) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(dx + (row0 + r) * D + c + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        *reinterpret_cast<float4*>(dx + row * D + c) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(dx + row * D + c + 4) = make_float4(o[4], o[5], o[6], o[7]);
       }
       if constexpr (DROP) {  // the masked image (element index = row * D + column, as every other user of this site's mask)
-        const uint64_t e0 = (uint64_t)(row0 + r) * D + c;
+        const uint64_t e0 = (uint64_t)row * D + c;
         const float4 f0 = drop_factor4(drop, dkey, e0), f1 = drop_factor4(drop, dkey, e0 + 4);
         o[0] *= f0.x; o[1] *= f0.y; o[2] *= f0.z; o[3] *= f0.w;
         o[4] *= f1.x; o[5] *= f1.y; o[6] *= f1.z; o[7] *= f1.w;
 #pragma unroll
         for (int k = 0; k < 8; ++k) acs[i][k] += o[k];
-        *reinterpret_cast<uint4*>(dx_m + (row0 + r) * D + c) = pack8(o);
+        *reinterpret_cast<uint4*>(dx_m + row * D + c) = pack8(o);
       }
       if (dxq) {  // wave-uniform: MX-FP8 image of the same values (D % 32 == 0: the four lanes of a block are live together)
         const MxBlock mb = mx8_encode(o);
-        *reinterpret_cast<uint2*>(dxq + (row0 + r) * D + c) = mb.q;
-        if ((lane & 3) == 0) dxs[(row0 + r) * (D >> 5) + (c >> 5)] = (uint8_t)mb.scale;
+        *reinterpret_cast<uint2*>(dxq + row * D + c) = mb.q;
+        if ((lane & 3) == 0) dxs[row * (D >> 5) + (c >> 5)] = (uint8_t)mb.scale;
       }
     }
   }
@@ -647,7 +716,9 @@ __global__ __launch_bounds__(256) void ln_bwd_row8_kernel(const bf16* __restrict
   const int n4 = (want_colsum ? 3 * D : 2 * D) >> 2, w4 = (3 * D) >> 2;
   for (int i = threadIdx.x; i < n4; i += 256) {
     const float4 a = l4[i], b = l4[w4 + i], c = l4[2 * w4 + i], d = l4[3 * w4 + i];
-    out[i] = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
+    const float4 v = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
+    if (TOK && i >= (2 * D) >> 2) reinterpret_cast<float4*>(dpos + (int64_t)blockIdx.x * D)[i - ((2 * D) >> 2)] = v;
+    else out[i] = v;
   }
 }
 
@@ -664,8 +735,20 @@ static inline int ln_bwd_rows_per_block(LnBwdFamily f, int64_t rows) {
 }
 static inline int64_t ln_bwd_blocks(LnBwdFamily f, int64_t rows) { return ceil_div(rows, ln_bwd_rows_per_block(f, rows)); }
 
-size_t layernorm_bwd_ws(int64_t rows, int dim) {
-  const int64_t nb = std::max({ln_bwd_blocks(LN_BWD_GENERAL, rows), ln_bwd_blocks(LN_BWD_REG, rows), ln_bwd_blocks(LN_BWD_ROW8, rows)});
+// The token-major row8 backward (layernorm_bwd_tok) runs one workgroup per token, each walking the token's `batch` rows: up to
+// LNR8_TOK_MAX_BATCH clips.  Above it the row-major launch runs with more, shorter workgroups and d pos is summed from its fp32 dx.
+// Measured at 324 and 512 tokens x 512 columns, device time of the launches replaced: batch 32: 32.0 us (row-major with the fp32
+// dx 17.7 + column sums 14.3) against 11.1; host-timed back to back at batch 64 / 128 / 256: 42 / 77 / 140 us against 21 / 33 /
+// 56 - the token-major form was the faster one at every batch tried, so the bound is the largest batch that was measured.
+constexpr int LNR8_TOK_MAX_BATCH = 256;
+bool layernorm_bwd_tok_ok(int batch, int tokens, int dim) {
+  return batch > 0 && tokens > 0 && dim % 8 == 0 && dim <= 1536 && ln_row8_on() && batch <= LNR8_TOK_MAX_BATCH;
+}
+
+// tokens: the caller may run the token-major form on these rows (one partial row per token)
+size_t layernorm_bwd_ws(int64_t rows, int dim, int tokens) {
+  const int64_t nb = std::max({ln_bwd_blocks(LN_BWD_GENERAL, rows), ln_bwd_blocks(LN_BWD_REG, rows), ln_bwd_blocks(LN_BWD_ROW8, rows),
+                               (int64_t)tokens});
   return (size_t)nb * 3 * dim * sizeof(float);
 }
 
@@ -712,8 +795,51 @@ static int launch_ln_bwd_row8(const TimingScope* ts, hipStream_t s, const bf16* 
   }
   launch_in_scope(ts, ln_bwd_row8_kernel<NV8, RU, DROP>, dim3((unsigned)ln_bwd_blocks(LN_BWD_ROW8, rows)), dim3(256), (uint32_t)lds, s,
                   dy, x, gamma, mean, rstd, dres, dx_lo, partial, rows, D, wc, dxq, dxs, dx, drop, dx_m,
-                  ln_bwd_rows_per_block(LN_BWD_ROW8, rows));
+                  ln_bwd_rows_per_block(LN_BWD_ROW8, rows), 0, (float*)nullptr);
   return check_launch("ln_bwd_row8_kernel");
+}
+
+template <int NV8, int RU>
+static int launch_ln_bwd_row8_tok(const TimingScope* ts, hipStream_t s, const bf16* dy, const bf16* x, const float* gamma,
+                                  const float* mean, const float* rstd, const bf16* dres, float* dpos, float* partial, int batch,
+                                  int tokens, int D) {
+  const size_t lds = (size_t)4 * 3 * D * sizeof(float);
+  static PerDeviceOnce raised;
+  if (lds > 64 * 1024 && raised.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)ln_bwd_row8_kernel<NV8, RU, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       4 * 3 * 512 * NV8 * (int)sizeof(float));
+    AVF_REQUIRE(e == hipSuccess, "layernorm_bwd_tok: cannot raise dynamic LDS limit");
+    raised.mark();
+  }
+  const int nbatch = (int)ceil_div((int64_t)batch, 4 * RU);  // batches of RU clips per wave
+  launch_in_scope(ts, ln_bwd_row8_kernel<NV8, RU, false, true>, dim3((unsigned)tokens), dim3(256), (uint32_t)lds, s, dy, x, gamma, mean,
+                  rstd, dres, (bf16*)nullptr, partial, (int64_t)batch * tokens, D, 1, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                  (float*)nullptr, kNoDrop, (bf16*)nullptr, nbatch * 4 * RU, tokens, dpos);
+  return check_launch("ln_bwd_row8_kernel(tok)");
+}
+
+// the bottom LayerNorm of a fused stack, all-bf16 streams: dpos[t, :] = sum_b dx[b * tokens + t, :] (fp32 [tokens, dim]) with
+// dgamma / dbeta, and no dx at all (ln_bwd_row8_kernel, TOK); ws: layernorm_bwd_ws(rows, dim, tokens)
+int layernorm_bwd_tok(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres,
+                      float* dpos, float* dgamma, float* dbeta, void* ws, int batch, int tokens, int dim, hipStream_t s,
+                      FoldJob* defer_fold) {
+  AVF_REQUIRE(dy && x && gamma && mean && rstd && dpos && ws, "layernorm_bwd_tok: null pointer");
+  AVF_REQUIRE(layernorm_bwd_tok_ok(batch, tokens, dim), "layernorm_bwd_tok: shape outside the token-major rule (batch=%d dim=%d)", batch, dim);
+  AVF_REQUIRE((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dres | (uintptr_t)dpos | (uintptr_t)ws) & 15) == 0,
+              "layernorm_bwd_tok: pointers must be 16-byte aligned");
+  const int64_t rows = (int64_t)batch * tokens;
+  TimingScope ts(KC_LAYERNORM, 0.0, (double)rows * dim * (2.0 + 2.0 + (dres ? 2.0 : 0.0)) + (double)tokens * dim * 4.0, s, /*per_kernel=*/true);
+  float* partial = (float*)ws;
+  AVF_TRY(ln_nv8(dim, [&](auto nv8, auto ru) {
+    return launch_ln_bwd_row8_tok<decltype(nv8)::value, decltype(ru)::value>(&ts, s, (const bf16*)dy, (const bf16*)x, gamma, mean, rstd,
+                                                                             (const bf16*)dres, dpos, partial, batch, tokens, dim);
+  }));
+  const FoldJob job{partial, tokens, 3 * dim, dim, dgamma, dbeta, nullptr};
+  if (defer_fold) {
+    *defer_fold = job;
+    return 0;
+  }
+  return fold_job(job, s);
 }
 
 int layernorm_bwd(const void* dy, int dy_dtype, const void* xv, const float* gamma, const float* mean,

@@ -132,6 +132,45 @@ def layernorm_bwd_ex(dy, x, weight, mean, rstd, dres=None, want_dx=True, want_lo
     return dx, dx_lo, dx_m, dg, db, cs
 
 
+def layernorm_fwd_embed(clip: torch.Tensor, audio: torch.Tensor, pos: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                        eps: float = 1e-5):
+    """fuse_tokens(clip, audio, pos, out_bf16=True) and the bf16 LayerNorm of its rows in one launch (avf_layernorm_fwd_embed)
+    -> x0 [B, Tv+Ta, D] bf16, y (bf16, same shape), mean, rstd; bit-identical to the two launches."""
+    _need_cuda(clip, audio, pos, weight, bias)
+    clip, audio, pos = clip.contiguous(), audio.contiguous(), pos.contiguous()
+    B, Tv, D = clip.shape
+    Ta = audio.shape[1]
+    assert audio.shape[0] == B and audio.shape[2] == D and pos.numel() == (Tv + Ta) * D
+    assert clip.dtype == audio.dtype == pos.dtype == torch.float32
+    x0 = torch.empty((B, Tv + Ta, D), dtype=torch.bfloat16, device=clip.device)
+    y = torch.empty_like(x0)
+    mean = torch.empty(B * (Tv + Ta), dtype=torch.float32, device=clip.device)
+    rstd = torch.empty_like(mean)
+    _lib.check(_lib.load().avf_layernorm_fwd_embed(_ptr(clip), _ptr(audio), _ptr(pos), B, Tv, Ta, _ptr(x0), _ptr(weight), _ptr(bias),
+                                                   _ptr(y), _ptr(mean), _ptr(rstd), D, float(eps), _stream()), "layernorm_fwd_embed")
+    return x0, y, mean, rstd
+
+
+def layernorm_bwd_pos(dy, x, weight, mean, rstd, dres, batch: int, d_pos: Optional[torch.Tensor] = None):
+    """the all-bf16 LayerNorm backward of [batch * tokens, D] rows reduced over the clips (avf_layernorm_bwd_pos, token-major)
+    -> d_pos [tokens, D] fp32 (= the column sums of dx over the clips; optionally preallocated), dgamma, dbeta."""
+    _need_cuda(dy, x, weight, mean, rstd, dres, d_pos)
+    lib = _lib.load()
+    assert all(t is None or (t.is_contiguous() and t.shape == x.shape and t.dtype == torch.bfloat16) for t in (dy, x, dres))
+    rows, D = x.shape
+    tokens = rows // batch
+    assert tokens * batch == rows
+    dev = x.device
+    if d_pos is None:
+        d_pos = torch.empty((tokens, D), dtype=torch.float32, device=dev)
+    dg = torch.empty(D, dtype=torch.float32, device=dev)
+    db = torch.empty(D, dtype=torch.float32, device=dev)
+    ws = _bytes(lib.avf_layernorm_bwd_pos_workspace_bytes(batch, tokens, D), dev)
+    _lib.check(lib.avf_layernorm_bwd_pos(_ptr(dy), _ptr(x), _ptr(weight), _ptr(mean), _ptr(rstd), _ptr(dres), _ptr(d_pos), _ptr(dg),
+                                         _ptr(db), _ptr(ws), batch, tokens, D, _stream()), "layernorm_bwd_pos")
+    return d_pos, dg, db
+
+
 def colsum(t: torch.Tensor) -> torch.Tensor:
     """column sums over all leading axes; a 2-D view whose rows are a constant stride apart (unit column stride) is read
     in place"""

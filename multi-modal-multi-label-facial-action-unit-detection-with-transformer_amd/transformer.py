@@ -121,6 +121,14 @@ class _DwGroup:
     __slots__ = ("cfgs", "ws_bytes", "blocks", "descs", "desc_ptrs", "ws")
 
 
+def _stack_ends_on(part: str) -> bool:
+    """The fused ends of the stack: "embed" (the embedding inside layer 0's LayerNorm-1) and "pos" (d pos_embedding from its
+    token-major backward).  AVF_STACK_ENDS=0 switches both off, AVF_STACK_ENDS=embed or =pos leaves only that one on (the A/B
+    arms); unset or 1: both on.  Read per call."""
+    v = os.environ.get("AVF_STACK_ENDS", "1").strip()
+    return v != "0" and (v in ("", "1") or part in v.split(","))
+
+
 class _StackFn(torch.autograd.Function):
     """x -> L layers.  Saved activations live in per-layer byte buffers carved by the library."""
 
@@ -131,13 +139,19 @@ class _StackFn(torch.autograd.Function):
         storage type; backward then hands d clip / d audio / d pos back from the fp32 gradient of that sequence."""
         lib = _lib.load()
         ctx.fused = audio is not None
+        embed = None  # (clip, audio, pos rows): layer 0's LayerNorm-1 builds the fused sequence itself (avf_layer_fwd_embed)
         if ctx.fused:
             T = x.shape[1] + audio.shape[1]
             if pos.shape[-2] < T or pos.shape[-1] != x.shape[-1]:
                 raise ValueError(f"pos_embedding {tuple(pos.shape)} does not cover {T} tokens of width {x.shape[-1]}")
             ctx.tv, ctx.shape_pos = x.shape[1], pos.shape
-            x = ops.fuse_tokens(x.detach().float(), audio.detach().float(),
-                                pos.detach().reshape(pos.shape[-2], pos.shape[-1])[:T], out_bf16=mod.resid_bf16)
+            pos_rows = pos.detach().reshape(pos.shape[-2], pos.shape[-1])[:T]
+            if (mod.resid_bf16 and keep is None and x.shape[1] > 0 and audio.shape[1] > 0 and _stack_ends_on("embed")
+                    and lib.avf_layer_fwd_embed_ok(C.byref(mod._cfg(x.shape[0], T, 0, None, None)))):
+                embed = (x.detach().float().contiguous(), audio.detach().float().contiguous(), pos_rows.float().contiguous())
+                x = torch.empty((x.shape[0], T, x.shape[2]), dtype=torch.bfloat16, device=x.device)  # x0, written by layer 0
+            else:
+                x = ops.fuse_tokens(x.detach().float(), audio.detach().float(), pos_rows, out_bf16=mod.resid_bf16)
         B, N, D = x.shape
         dev = x.device
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -181,8 +195,13 @@ class _StackFn(torch.autograd.Function):
                 shared = shared if shared is not None else _alloc_bytes(saved_bytes, dev)
                 sv = shared
             x_out = torch.empty((B * N, D), dtype=torch.bfloat16 if rs16 else torch.float32, device=dev)
-            _lib.check(lib.avf_layer_fwd(C.byref(cfgs[l]), C.byref(pp), _ptr(lowps[l]), _ptr(xs[-1]), _ptr(x_out), _ptr(sv),
-                                         _ptr(ws), stream), f"layer_fwd[{l}]")
+            if l == 0 and embed is not None:
+                _lib.check(lib.avf_layer_fwd_embed(C.byref(cfgs[0]), C.byref(pp), _ptr(lowps[0]), _ptr(embed[0]), _ptr(embed[1]),
+                                                   _ptr(embed[2]), ctx.tv, _ptr(x0), _ptr(x_out), _ptr(sv), _ptr(ws), stream),
+                           "layer_fwd_embed[0]")
+            else:
+                _lib.check(lib.avf_layer_fwd(C.byref(cfgs[l]), C.byref(pp), _ptr(lowps[l]), _ptr(xs[-1]), _ptr(x_out), _ptr(sv),
+                                             _ptr(ws), stream), f"layer_fwd[{l}]")
             saved.append(sv)
             xs.append(x_out)
         ctx.mod = mod
@@ -229,12 +248,19 @@ class _StackFn(torch.autograd.Function):
         lo_b = torch.empty(lo_bytes, dtype=torch.uint8, device=dev) if bf16 else None
         have_lo = False
         top_colsum = False
+        # below the bottom layer only d pos_embedding is wanted: its LayerNorm-1 backward runs token-major and writes d_pos itself
+        # (no fp32 dx of the sequence, no column sum over the clips) - avf_layer_bwd_pos / avf_layer_bwd_dx_pos
+        d_pos = None
+        if (ctx.fused and ctx.grad_in[2] and not ctx.grad_in[0] and not ctx.grad_in[1] and cfg.grad_stream_bf16
+                and _stack_ends_on("pos") and lib.avf_layer_bwd_pos_ok(C.byref(cfg))):
+            d_pos = torch.empty((N, D), dtype=torch.float32, device=dev)
         if ctx.pool:
             # dy is the gradient of the pooled [B, D] output: one kernel writes the top layer's incoming gradient in fp32
             # and (no dropout mask to apply on it) in bf16, and its column sums - the top layer's b2 gradient - directly
             g = dy.contiguous().to(torch.float32)
-            dx = torch.empty((B * N, D), dtype=torch.float32, device=dev)
             have_lo = top_colsum = bf16 and cfg.dropout_p == 0.0
+            # (the fp32 gradient of the sequence has no reader when the bf16 image feeds the top layer and d_pos the bottom one)
+            dx = None if (have_lo and d_pos is not None) else torch.empty((B * N, D), dtype=torch.float32, device=dev)
         else:
             dx = dy.contiguous().view(B * N, D).to(torch.float32)
             if dx.data_ptr() == dy.data_ptr():
@@ -297,15 +323,20 @@ class _StackFn(torch.autograd.Function):
                 # with it) and out of the bottom one; in between the layers hand each other the bf16 image alone
                 dx_out_p = None if (gs16 and have_lo) else _ptr(dx)
                 dx_in_p = None if (gs16 and l > 0) else _ptr(dx)
-                args = (C.byref(cfgs[l]), C.byref(pp), _ptr(ctx.lowps[l]), _ptr(ctx.xs[l]),
+                lead = (C.byref(cfgs[l]), C.byref(pp), _ptr(ctx.lowps[l]), _ptr(ctx.xs[l]),
                         _ptr(ctx.saved_bufs[l]), dx_out_p, _ptr(lo_a) if have_lo else None,
-                        _ptr(views[l][B2]) if (l < L - 1 or top_colsum) else None, dx_in_p, _ptr(lo_b),
-                        _ptr(views[l - 1][B2]) if l > 0 else None, C.byref(gp), _ptr(ws))
+                        _ptr(views[l][B2]) if (l < L - 1 or top_colsum) else None)
+                if l == 0 and d_pos is not None:
+                    args = lead + (_ptr(d_pos), C.byref(gp), _ptr(ws))
+                    fn, fn_dx, what = lib.avf_layer_bwd_pos, lib.avf_layer_bwd_dx_pos, "layer_bwd_pos"
+                else:
+                    args = lead + (dx_in_p, _ptr(lo_b), _ptr(views[l - 1][B2]) if l > 0 else None, C.byref(gp), _ptr(ws))
+                    fn, fn_dx, what = lib.avf_layer_bwd, lib.avf_layer_bwd_dx, "layer_bwd"
                 if dw is None:
-                    _lib.check(lib.avf_layer_bwd(*args, stream), f"layer_bwd[{l}]")
+                    _lib.check(fn(*args, stream), f"{what}[{l}]")
                     lo_a, lo_b = lo_b, lo_a
                 else:
-                    _lib.check(lib.avf_layer_bwd_dx(*args, _ptr(dw.blocks[k]), dw.descs[k], stream), f"layer_bwd_dx[{l}]")
+                    _lib.check(fn_dx(*args, _ptr(dw.blocks[k]), dw.descs[k], stream), f"{what}_dx[{l}]")
                     held.append(lo_a)
                     lo_a, lo_b = lo_b, torch.empty(lo_bytes, dtype=torch.uint8, device=dev)
                 have_lo = bf16
@@ -319,14 +350,14 @@ class _StackFn(torch.autograd.Function):
         ctx.saved_bufs = None
         ctx.xs = None
         tail = (None, None, None, *([None] * (L * PARAMS_PER_LAYER)))
-        dx = dx.view(B, N, D)
+        dx = None if dx is None else dx.view(B, N, D)
         if not ctx.fused:
             return (dx, None, None) + tail
         d_clip = dx[:, :ctx.tv] if ctx.grad_in[0] else None
         d_audio = dx[:, ctx.tv:] if ctx.grad_in[1] else None
-        d_pos = None
-        if ctx.grad_in[2]:  # d pos = sum over the clips (fp32 column sums of the [B, T*D] view)
-            d_pos = ops.colsum(dx.view(B, N * D)).view(N, D)
+        if ctx.grad_in[2]:
+            if d_pos is None:  # d pos = sum over the clips (fp32 column sums of the [B, T*D] view)
+                d_pos = ops.colsum(dx.view(B, N * D)).view(N, D)
             if ctx.shape_pos[-2] > N:  # embedding table longer than the sequence: the unused rows get zero gradient
                 d_pos = torch.nn.functional.pad(d_pos, (0, 0, 0, ctx.shape_pos[-2] - N))
             d_pos = d_pos.view(ctx.shape_pos)
