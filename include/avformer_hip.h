@@ -750,6 +750,33 @@ size_t avf_layers_dw_workspace_bytes(const avf_layer_cfg* cfgs, int n_layers);
 int avf_layers_dw(const avf_layer_cfg* cfgs, int n_layers, const void* const* descs, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* ---- frozen ResNet BasicBlock stages, forward only (csrc/conv.hip) ----------------------------------------------------------
+ * The conv stages around the S-Former's token section: conv3x3 / conv1x1 (vformer.py:117-125), BasicBlock.forward
+ * (vformer.py:149-165: conv1 - bn1 - relu - conv2 - bn2 - += identity - relu, identity = downsample(x) = conv1x1 + BatchNorm2d,
+ * vformer.py:218-221), layer1..layer4 and avgpool + flatten of ResFormer.forward (vformer.py:242-244, 261-265).  Activations are
+ * NHWC, so the stage-3 map [B', 7, 7, 256] IS the token tensor [B', 49, 256] of vformer.py:247-259 and no permute is run.
+ * BatchNorm2d is folded in eval mode (running statistics): "frozen" means eval-mode here.  No gradients.
+ *   avf_conv_pack_weight: w [Cout, Cin, k, k] fp32 (nn.Conv2d, bias=False) -> w_packed [Cout, k, k, Cin] bf16 (RNE);
+ *     scale[c] = gamma[c] / sqrt(running_var[c] + eps), shift[c] = beta[c] - running_mean[c] * scale[c], computed in fp64 and
+ *     stored as fp32 [Cout].  The scale stays in the epilogue: it is not multiplied into the bf16 weights.  Once per weight load.
+ *   avf_conv2d_nhwc: out[n, oy, ox, co] = act( (sum_{ky,kx,ci} x[n, oy*stride - pad + ky, ox*stride - pad + kx, ci] *
+ *     w_packed[co, ky, kx, ci]) * scale[co] + shift[co] (+ residual[n, oy, ox, co]) ), act = ReLU when relu != 0; positions
+ *     outside the image count as zero and are never read.  k = 3 (pad 1) or 1 (pad 0), stride 1 or 2, Ho = (H + 2 pad - k) /
+ *     stride + 1; Cin % 32 == 0, Cout % 16 == 0.  x [N, H, W, Cin] fp32 (rounded to bf16, RNE, as it is staged) or bf16;
+ *     residual (null: none) and out [N, Ho, Wo, Cout] fp32 or bf16 (RNE), each with its own type.  bf16 products accumulate in
+ *     fp32 (v_mfma_f32_16x16x32_bf16); the epilogue is fp32.  Every operand 16-byte aligned; out may not overlap an input.
+ *   avf_conv_plan: the tile avf_conv2d_nhwc runs a shape on: *tile = its id (0: 128 pixels x 64 channels, 1: 64 x 32), *tile_m /
+ *     *tile_n its extent.  Same argument checks as the launch.
+ *   avf_avgpool_nhwc: x [N, HW, C] fp32 or bf16 -> out [N, C] fp32, the mean over HW accumulated in fp32 (C % 4 == 0). */
+int avf_conv_pack_weight(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                         const float* running_var, double eps, void* w_packed, float* scale, float* shift, int Cout, int Cin,
+                         int k, void* stream);
+int avf_conv2d_nhwc(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift,
+                    const void* residual, int res_dtype, int relu, int k, int stride, void* out, int out_dtype, int N, int H,
+                    int W, int Cin, int Cout, void* stream);
+int avf_conv_plan(int N, int H, int W, int Cin, int Cout, int k, int stride, int* tile, int* tile_m, int* tile_n);
+int avf_avgpool_nhwc(const void* x, int x_dtype, float* out, int64_t N, int HW, int C, void* stream);
+
 /* test aid: the keep/(1-p) factors (0 or 1/(1-p_eff)) dropout site `site` (0 after to_out, 1 after GELU, 2 after
  * net.3) of layer `layer_index` applies to a [rows, cols] activation, as fp32 [rows, cols] (cols % 4 == 0). */
 int avf_dropout_factors(uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site, float p, int64_t rows, int cols,

@@ -1,0 +1,230 @@
+"""The frozen ResNet stages of the reference's S-Former (``ResFormer``, vformer.py:128-268; copied in sformer.py, tformer.py,
+dual_sformer.py): ``FrozenBasicBlock`` and ``FrozenResFormer``, forward only.
+
+"Frozen" means eval-mode here: BatchNorm2d always uses its running statistics, whatever ``train()`` says.  That is exact for
+``evaluate()`` (train.py:106-169) and whole-dataset inference (test_aff2.py); the reference itself runs the BatchNorm of its
+"frozen" streams in train mode while ``model.train()`` is on (avformer.py:78-85 only clears ``requires_grad``), a quirk this
+package does not reproduce.
+
+Every module takes ``backend=``: ``"torch"`` (default) is the definition - the reference's op sequence in fp32, NCHW, runs
+anywhere; ``"hip"`` runs csrc/conv.hip: NHWC activations, bf16 between launches, each conv one launch with the folded BatchNorm,
+the identity add and the ReLU in its epilogue.  The stage-3 map [B', 7, 7, 256] in NHWC IS the token tensor [B', 49, 256], so the
+hip backend runs no map/token permute on either side of ``spatial_transformer``.
+
+The hip backend computes no gradients: with grad mode on and an input or parameter that requires grad, ``forward`` raises
+instead of silently cutting the graph."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from . import ops
+from .heads import ResFormerTokens
+
+BACKENDS = ("torch", "hip")
+_CH = 32  # the conv kernel's channel granule (Cin % 32 == 0): other widths run zero-padded to it
+
+
+def _check_backend(backend):
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    return backend
+
+
+def _pad_to(n: int) -> int:
+    return -(-n // _CH) * _CH
+
+
+def _no_grad_or_raise(module: nn.Module, x: torch.Tensor, who: str):
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
+        raise RuntimeError(f"{who}(backend='hip') is forward-only: it computes no gradients, and its input or one of its "
+                           "parameters requires grad - run it under torch.no_grad() or freeze its parameters "
+                           "(requires_grad_(False)); backend='torch' differentiates")
+
+
+def to_nhwc(x: torch.Tensor, channels: Optional[int] = None) -> torch.Tensor:
+    """NCHW -> NHWC bf16 (contiguous), zero-padded to ``channels``"""
+    x = x.permute(0, 2, 3, 1)
+    if channels is not None and channels != x.shape[-1]:
+        x = F.pad(x, (0, channels - x.shape[-1]))
+    return x.to(torch.bfloat16).contiguous()
+
+
+class FrozenBasicBlock(nn.Module):
+    """``BasicBlock`` (vformer.py:128-166) in eval mode: ``conv1``, ``bn1``, ``conv2``, ``bn2``, ``downsample.0``, ``downsample.1``
+    are ordinary ``nn.Conv2d`` / ``nn.BatchNorm2d`` children with the reference's state_dict keys and shapes.
+    ``forward`` takes and returns NCHW fp32 with either backend; ``forward_nhwc`` is the hip backend's native form (two launches, or
+    three with a downsample).  The packed bf16 weights and folded BatchNorm are rebuilt whenever a parameter or buffer changes
+    (version counters, and a ``load_state_dict`` hook); writes through ``.data`` bypass the counters: call ``refresh_weights()``."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, backend="torch"):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride, self.inplanes, self.planes = stride, inplanes, planes
+        self.backend = _check_backend(backend)
+        self._packed = None
+
+    @staticmethod
+    def _bn(x, bn):
+        return F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+
+    def _forward_torch(self, x):
+        out = F.relu(self._bn(self.conv1(x), self.bn1))
+        out = self._bn(self.conv2(out), self.bn2)
+        identity = x if self.downsample is None else self._bn(self.downsample[0](x), self.downsample[1])
+        return F.relu(out + identity)
+
+    # ---- hip ------------------------------------------------------------------------------------
+    def _pairs(self):
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)]
+        if self.downsample is not None:
+            pairs.append((self.downsample[0], self.downsample[1]))
+        return pairs
+
+    def _state_key(self, device):
+        ts = [t for conv, bn in self._pairs() for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        return (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+
+    def refresh_weights(self):
+        self._packed = None
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._packed = None
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _pack(self, device):
+        key = self._state_key(device)
+        if self._packed is None or self._packed[0] != key:
+            packs = []
+            for conv, bn in self._pairs():
+                w, ts = conv.weight.detach(), [t.detach() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+                if not w.is_cuda:
+                    raise RuntimeError("FrozenBasicBlock(backend='hip'): parameters must be on the MI355X (module.to('cuda')); "
+                                       "there is no CPU fallback")
+                co, ci = _pad_to(w.shape[0]), _pad_to(w.shape[1])
+                if (co, ci) != tuple(w.shape[:2]):  # zero weights, gamma = beta = mean = 0, var = 1: the padded channels stay 0
+                    w = F.pad(w, (0, 0, 0, 0, 0, ci - w.shape[1], 0, co - w.shape[0]))
+                    ts = [F.pad(t, (0, co - t.numel()), value=float(i == 3)) for i, t in enumerate(ts)]
+                packs.append(ops.conv_pack_weight(w.float(), *[t.float() for t in ts], eps=bn.eps))
+            self._packed = (key, packs)
+        return self._packed[1]
+
+    def forward_nhwc(self, x, out_dtype=torch.bfloat16):
+        """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(planes)] in ``out_dtype``"""
+        _no_grad_or_raise(self, x, "FrozenBasicBlock")
+        p = self._pack(x.device)
+        h = ops.conv2d_nhwc(x, *p[0], k=3, stride=self.stride, relu=True)
+        identity = x if self.downsample is None else ops.conv2d_nhwc(x, *p[2], k=1, stride=self.stride)
+        return ops.conv2d_nhwc(h, *p[1], k=3, stride=1, residual=identity, relu=True, out_dtype=out_dtype)
+
+    def forward(self, x):
+        if self.backend == "torch":
+            return self._forward_torch(x)
+        ops._need_cuda(x)
+        y = self.forward_nhwc(to_nhwc(x, _pad_to(self.inplanes)), out_dtype=torch.float32)
+        return y[..., :self.planes].permute(0, 3, 1, 2).contiguous()
+
+
+class _Stage(nn.Sequential):
+    """one ``layerN``: its blocks in a row; NHWC in, NHWC out, the last block writing ``out_dtype``"""
+
+    def forward_nhwc(self, x, out_dtype=torch.bfloat16):
+        for i, blk in enumerate(self):
+            x = blk.forward_nhwc(x, out_dtype if i == len(self) - 1 else torch.bfloat16)
+        return x
+
+
+class FrozenResFormer(ResFormerTokens):
+    """The whole S-Former, ``ResFormer(BasicBlock, layers)`` (vformer.py:168-268), with the reference's names - ``conv1``, ``bn1``,
+    ``maxpool``, ``layer1`` .. ``layer4``, ``avgpool``, ``pos_embedding``, ``spatial_transformer.*`` - so that a reference checkpoint
+    loads with every key matched.  x [B, T, C, H, W] or [B', C, H, W] -> [B', 512] fp32.
+
+    ``backend="hip"``: the 7x7 ``conv1`` / ``bn1`` / ReLU / ``maxpool`` stay torch ops (3 input channels need another kernel),
+    one NCHW -> NHWC bf16 conversion follows, then ``layer1`` .. ``layer3`` on the conv kernel; the last launch of ``layer3`` writes
+    the fp32 tokens, ``pos_embedding`` is added, ``spatial_transformer`` runs, and its output goes straight into ``layer4``;
+    ``avgpool`` is the NHWC pool kernel.  The token section is this package's ``Transformer`` with either backend, so the
+    module needs the GPU either way."""
+
+    def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16"):
+        super().__init__(dropout=dropout, compute_dtype=compute_dtype)
+        self.backend = _check_backend(backend)
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(64, layers[0])
+        self.layer2 = self._make_layer(128, layers[1], stride=2)
+        self.layer3 = self._make_layer(256, layers[2], stride=2)
+        self.layer4 = self._make_layer(512, layers[3], stride=2)
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self._modules["spatial_transformer"] = self._modules.pop("spatial_transformer")  # the reference's state_dict order
+        for m in self.modules():                                                        # vformer.py:200-205
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+
+    def _make_layer(self, planes, blocks, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes:
+            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes, kernel_size=1, stride=stride, bias=False), nn.BatchNorm2d(planes))
+        stage = [FrozenBasicBlock(self.inplanes, planes, stride, downsample, backend=self.backend)]
+        self.inplanes = planes
+        stage += [FrozenBasicBlock(planes, planes, backend=self.backend) for _ in range(1, blocks)]
+        return _Stage(*stage)
+
+    def set_backend(self, backend):
+        self.backend = _check_backend(backend)
+        for m in self.modules():
+            if isinstance(m, FrozenBasicBlock):
+                m.backend = backend
+        return self
+
+    def stem(self, x):
+        """conv1 - bn1 - relu - maxpool (vformer.py:238-241), eval-mode BatchNorm, torch ops with either backend"""
+        return self.maxpool(F.relu(FrozenBasicBlock._bn(self.conv1(x), self.bn1)))
+
+    def stages_to_tokens(self, x):
+        """hip: the stem's NCHW output -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens + pos_embedding, (h, w))"""
+        x = self.layer3.forward_nhwc(self.layer2.forward_nhwc(self.layer1.forward_nhwc(to_nhwc(x))), out_dtype=torch.float32)
+        t = x.view(x.shape[0], x.shape[1] * x.shape[2], x.shape[3])               # NHWC IS [B', tokens, C]: no permute
+        return t + self.pos_embedding[:, :t.shape[1]], (x.shape[1], x.shape[2])   # vformer.py:253
+
+    def tokens_to_features(self, t, hw):
+        """hip: the transformer's [B', h*w, 256] fp32 output -> layer4 -> avgpool -> [B', 512] fp32"""
+        x = self.layer4.forward_nhwc(t.view(t.shape[0], hw[0], hw[1], t.shape[2]))
+        return ops.avgpool_nhwc(x)
+
+    def forward(self, x):
+        if x.dim() == 5:
+            x = x.contiguous().view(-1, *x.shape[2:])                             # vformer.py:234-235
+        if self.backend == "torch":
+            x = self.layer3(self.layer2(self.layer1(self.stem(x))))
+            x = self.layer4(ResFormerTokens.forward(self, x))                     # vformer.py:245-261
+            return torch.flatten(self.avgpool(x), 1)
+        ops._need_cuda(x)
+        _no_grad_or_raise(self, x, "FrozenResFormer")
+        t, hw = self.stages_to_tokens(self.stem(x))
+        return self.tokens_to_features(self.spatial_transformer(t), hw)
+
+
+class FrozenVideoModel(nn.Module):
+    """``VideoModel`` (vformer.py:295-311) with its fc replaced by the identity, as avformer.py:61-66 uses it: clip [B, C, T, H, W]
+    -> the last ``num_channels`` channels -> ``s_former`` -> ``t_former`` -> [B, 512]"""
+
+    def __init__(self, backend="torch", compute_dtype="bf16"):
+        super().__init__()
+        from .heads import TFormer
+        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype)
+        self.t_former = TFormer(compute_dtype=compute_dtype)
+        self.num_channels = 3
+
+    def forward(self, x):
+        x = x[:, -self.num_channels:].permute(0, 2, 1, 3, 4)
+        return self.t_former(self.s_former(x))

@@ -9,7 +9,8 @@ takes them as two modules, ``stem`` (frames [B', C, H, W] -> stage-3 feature map
 -> pooled features [B', 512]); ``ResFormerShell`` runs the token section between them exactly where ``ResFormer.forward``
 does.  Without a backbone the models consume what the backbone would produce (a [B', 256, 7, 7] map, ``tail`` = global
 average pool + a fixed channel tiling to 512 features), which is enough to drive the token path, the heads and the
-[B, 21] output contract.  Module / parameter names follow the reference so that its checkpoints load with strict=False.
+[B, 21] output contract.  ``backbone="resnet18_frozen"`` builds the stages themselves: ``backbone.FrozenResFormer``, the reference's whole
+``ResFormer`` in eval mode on the HIP conv kernels, forward only (csrc/conv.hip).  Module / parameter names follow the reference so that its checkpoints load with strict=False.
 The small ``fc`` heads (BatchNorm1d / Linear) are plain PyTorch modules - plumbing either side of the hot path."""
 from __future__ import annotations
 
@@ -51,6 +52,21 @@ class ResFormerShell(ResFormerTokens):
         return self.tail(super().forward(self.stem(x)))
 
 
+FROZEN_BACKBONES = ("resnet18_frozen",)
+
+
+def _s_former(backbone, num_channels=3, **kw):
+    """the S-Former of a ``*former`` model: ``backbone=None`` or a ``(stem, tail)`` pair -> ``ResFormerShell``;
+    ``backbone="resnet18_frozen"`` -> ``backbone.FrozenResFormer`` on the HIP conv kernels (eval-mode stages, forward only), whose
+    ``conv1`` takes the ``num_channels`` channels the modality selects (vformer.py:313-331)"""
+    if isinstance(backbone, str):
+        if backbone not in FROZEN_BACKBONES:
+            raise ValueError(f"backbone must be None, a (stem, tail) pair or one of {FROZEN_BACKBONES}, got {backbone!r}")
+        from .backbone import FrozenResFormer
+        return FrozenResFormer(backend="hip", in_channels=num_channels, **kw)
+    return ResFormerShell(backbone, **kw)
+
+
 def _fc_head(in_features):
     return nn.Sequential(nn.BatchNorm1d(in_features), nn.Linear(in_features, 256), nn.BatchNorm1d(256), nn.Linear(256, 12 + 7 + 2))
 
@@ -80,8 +96,8 @@ class SpatialFormerModel(_FormerTask):
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
-        self.base_model = ResFormerShell(backbone, dropout=0.2, compute_dtype=compute_dtype)
         self._config(modality, task)
+        self.base_model = _s_former(backbone, self.num_channels, dropout=0.2, compute_dtype=compute_dtype)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype)
@@ -103,9 +119,9 @@ class SpatialFormerModel(_FormerTask):
 
 
 class _VideoModel(nn.Module):
-    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype):
+    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype, num_channels=3):
         super().__init__()
-        self.s_former = ResFormerShell(backbone, compute_dtype=compute_dtype)
+        self.s_former = _s_former(backbone, num_channels, compute_dtype=compute_dtype)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype) if au_tokens else None
         self.t_former = TFormer(dim=temporal_dim, compute_dtype=compute_dtype)
 
@@ -123,8 +139,8 @@ class VisualFormerModel(_FormerTask):
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
-        self.video_model = _VideoModel(backbone, 512, False, compute_dtype)
         self._config(modality, task)
+        self.video_model = _VideoModel(backbone, 512, False, compute_dtype, self.num_channels)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vformer'])
@@ -140,8 +156,8 @@ class SpatialTemporalFormerModel(_FormerTask):
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
         super().__init__()
         self.has_backbone = backbone is not None
-        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype)
         self._config(modality, task)
+        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype, self.num_channels)
         self.task, self.modes = task, ["clip"]
         self.au_head = tformer_AU_head(dropout=0.2, compute_dtype=compute_dtype)
         self.fc = _fc_head(128 * 12)

@@ -6,7 +6,9 @@ attributes, ``forward(dict) -> [B,21]`` layout ([0:12] AU logits, [12:19] EX, [1
 ``get_*_loss`` methods, so the step loop of the reference's ``train.py:206-237`` runs on it
 unchanged.  Its CNN feature extractors (ResNet18 on mel-spectrograms, Former-DFER video model) are
 out of scope: ``AudioFormer`` / ``VisualFormer`` take a ``backbone``
-module and default to the identity, i.e. they consume per-clip feature vectors [B, 512].
+module and default to the identity, i.e. they consume per-clip feature vectors [B, 512]; ``VisualFormer(backbone="resnet18_frozen")``
+/ ``TwoStreamAuralVisualFormer(video_backbone="resnet18_frozen")`` put the reference's frozen ``VideoModel`` there, its ResNet
+stages on the HIP conv kernels (backbone.py), and consume clips [B, C, T, H, W].
 
 ``SyntheticAVFormer`` is the BASELINE.json scale-up of the same block: video tokens [B,T_v,D] and
 audio tokens [B,T_a,D] fused on the SEQUENCE axis, + positional embedding -> Transformer(D, L) ->
@@ -49,6 +51,13 @@ class VisualFormer(nn.Module):
     def __init__(self, modality='A;V', video_pretrained=True, task='EX', backbone=None, in_features=512,
                  compute_dtype="bf16"):
         super().__init__()
+        if isinstance(backbone, str):
+            # "resnet18_frozen": the reference's own VideoModel (vformer.py:295-311, fc = identity as in avformer.py:61-66) with
+            # its ResNet stages on the HIP conv kernels - eval-mode, forward only (backbone.py); consumes clips [B, C, T, H, W]
+            if backbone != "resnet18_frozen":
+                raise ValueError(f"backbone must be None, a module or 'resnet18_frozen', got {backbone!r}")
+            from .backbone import FrozenVideoModel
+            backbone = FrozenVideoModel(backend="hip", compute_dtype=compute_dtype)
         self.video_model = backbone if backbone is not None else nn.Identity()
         self.task = task
         self.modes = ["clip"]
@@ -138,10 +147,11 @@ class _TaskLossMixin:
 
 class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
     def __init__(self, modality='A;V;M', video_pretrained=True, audio_pretrained=True, task='EX',
-                 video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain"):
+                 video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain", video_backbone=None):
         super().__init__()
         self.audio_model = AudioFormer(compute_dtype=compute_dtype)
-        self.video_model = VisualFormer(compute_dtype=compute_dtype)
+        # video_backbone="resnet18_frozen": the video stream consumes clips through the frozen S-Former on the HIP path
+        self.video_model = VisualFormer(backbone=video_backbone, compute_dtype=compute_dtype)
         if video_pretrained and load_pretrain(self.video_model, video_weights):
             for p in self.video_model.parameters():
                 p.requires_grad = False

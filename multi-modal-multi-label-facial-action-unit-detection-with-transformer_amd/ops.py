@@ -1139,6 +1139,75 @@ def token_mean_bwd(g: torch.Tensor, tokens: int, want_bf16: bool = False, want_c
     return dy, lo, cs
 
 
+# frozen ResNet stages (csrc/conv.hip) ---------------------------------------------------------------
+def conv_pack_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                     running_var: torch.Tensor, eps: float = 1e-5):
+    """nn.Conv2d weight [Cout, Cin, k, k] fp32 + BatchNorm2d's eval-mode statistics -> (w_packed [Cout, k*k*Cin] bf16 ordered
+    tap-major / channel-minor, scale [Cout], shift [Cout] fp32) for ``conv2d_nhwc`` (avf_conv_pack_weight)."""
+    _need_cuda(w, gamma, beta, running_mean, running_var)
+    ts = [t.detach().contiguous() for t in (w, gamma, beta, running_mean, running_var)]
+    assert all(t.dtype == torch.float32 for t in ts) and ts[0].dim() == 4 and ts[0].shape[2] == ts[0].shape[3]
+    Cout, Cin, k, _ = ts[0].shape
+    assert all(t.numel() == Cout for t in ts[1:])
+    wp = torch.empty((Cout, k * k * Cin), dtype=torch.bfloat16, device=w.device)
+    scale = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    shift = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().avf_conv_pack_weight(*[_ptr(t) for t in ts], float(eps), _ptr(wp), _ptr(scale), _ptr(shift), Cout, Cin, k,
+                                                _stream()), "conv_pack_weight")
+    return wp, scale, shift
+
+
+def conv_out_hw(H: int, W: int, k: int, stride: int) -> Tuple[int, int]:
+    pad = 1 if k == 3 else 0
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def conv_plan(N: int, H: int, W: int, Cin: int, Cout: int, k: int, stride: int = 1) -> dict:
+    """The tile ``conv2d_nhwc`` runs this shape on (avf_conv_plan): dict(tile = 0 | 1, tile_m, tile_n).  Raises on a shape
+    the kernel does not take."""
+    out = [C.c_int(-1) for _ in range(3)]
+    _lib.check(_lib.load().avf_conv_plan(int(N), int(H), int(W), int(Cin), int(Cout), int(k), int(stride), *[C.byref(o) for o in out]),
+               "conv_plan")
+    return dict(tile=out[0].value, tile_m=out[1].value, tile_n=out[2].value)
+
+
+def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, k: int, stride: int = 1,
+                residual: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None,
+                out_dtype=torch.bfloat16) -> torch.Tensor:
+    """relu?(conv(x, w) * scale + shift (+ residual)) on NHWC activations (avf_conv2d_nhwc): x [N, H, W, Cin] fp32 or bf16,
+    w_packed / scale / shift from ``conv_pack_weight``, k = 3 (pad 1) or 1 (pad 0), stride 1 or 2; residual / out
+    [N, Ho, Wo, Cout] fp32 or bf16.  Forward only."""
+    _need_cuda(x, w_packed, scale, shift, residual, out)
+    N, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    Ho, Wo = conv_out_hw(H, W, k, stride)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), dtype=torch_dtype(out_dtype), device=x.device)
+    for name, t, shape in (("x", x, (N, H, W, Cin)), ("w_packed", w_packed, (Cout, k * k * Cin)), ("scale", scale, (Cout,)),
+                           ("shift", shift, (Cout,)), ("residual", residual, (N, Ho, Wo, Cout)), ("out", out, (N, Ho, Wo, Cout))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"conv2d_nhwc: {name} must be a contiguous {shape} tensor (got {tuple(t.shape)}, strides {t.stride()})")
+    assert w_packed.dtype == torch.bfloat16 and scale.dtype == shift.dtype == torch.float32
+    _lib.check(_lib.load().avf_conv2d_nhwc(_ptr(x), avf_dtype(x.dtype), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(residual),
+                                           avf_dtype(residual.dtype) if residual is not None else F32, int(bool(relu)), int(k),
+                                           int(stride), _ptr(out), avf_dtype(out.dtype), N, H, W, Cin, Cout, _stream()), "conv2d_nhwc")
+    return out
+
+
+def avgpool_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, ..., C] fp32 or bf16 (NHWC map or [N, HW, C] tokens) -> [N, C] fp32, the mean over the middle axes (avf_avgpool_nhwc)"""
+    _need_cuda(x, out)
+    if not x.is_contiguous():
+        raise ValueError("avgpool_nhwc: x must be contiguous")
+    N, Cn = x.shape[0], x.shape[-1]
+    HW = x.numel() // (N * Cn)
+    if out is None:
+        out = torch.empty((N, Cn), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (N, Cn) and out.is_contiguous()
+    _lib.check(_lib.load().avf_avgpool_nhwc(_ptr(x), avf_dtype(x.dtype), _ptr(out), N, HW, Cn, _stream()), "avgpool_nhwc")
+    return out
+
+
 def dropout_factors(seed: int, layer: int, site: int, p: float, rows: int, cols: int, device="cuda") -> torch.Tensor:
     """keep/(1-p) factors of dropout site `site` of layer `layer` for a [rows, cols] activation (test aid)."""
     out = torch.empty((rows, cols), dtype=torch.float32, device=device)

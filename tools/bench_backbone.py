@@ -1,0 +1,177 @@
+"""The frozen ResNet stages of the S-Former (backbone.FrozenResFormer) on the HIP conv kernels against the two ways PyTorch runs
+them, on one box, in one process, the arms alternated.
+
+    python tools/bench_backbone.py [--frames 1024 16] [--size 112] [--groups 7] [--calls 5] [--warmup 2]
+
+  a   FrozenResFormer(backend="torch"): fp32, NCHW, as the reference runs it
+  b   the same torch ops on a bf16 channels_last copy of the conv stages: the vendor library's best case (the token section is
+      this package's Transformer in every arm; b reaches it through the reference's permutes)
+  c   FrozenResFormer(backend="hip")
+Per frame count B' (1024 = 64 clips x 16 frames, 16 = batch-1 inference) three sections are timed separately: layer1..3 (from
+the stem's output to the stage-3 map / tokens), the layer4 + avgpool tail (from a stage-3 map), and the whole module.  A timed
+window is --calls calls between two device events; the groups alternate over all arms after --warmup calls of each; the
+result is the median of the groups.  Then every distinct conv shape of the stages runs alone on avf_conv2d_nhwc and its
+achieved fraction of the bf16 MFMA peak (2.5 PFLOP/s dense) is reported, and the device operations of arm c from the stage-3
+tokens to the pooled features are counted with torch.profiler: next to the token section's own there must be the positional
+add, layer4's five conv launches and the pool, and no permute.  Writes <out-dir>/<name>.json (default
+profiles/ab/backbone_frozen.json) and prints the medians."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PEAK_BF16 = 2.5e15
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, nargs="+", default=[1024, 16])
+    ap.add_argument("--size", type=int, default=112)
+    ap.add_argument("--groups", type=int, default=7)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--name", default="backbone_frozen")
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "ab"))
+    args = ap.parse_args()
+    if args.groups < 5:
+        ap.error("--groups must be at least 5 (the result is a median)")
+    import torch
+    from torch.nn import functional as F
+    import avformer_amd as A
+    from tools.ab_bench import box_id
+    from tools.bench_mel import device_ops, shader_clock
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_backbone.py measures on the GPU; no device found")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    m_a = A.FrozenResFormer(backend="torch").to(dev).eval()
+    for p in m_a.parameters():
+        p.requires_grad_(False)
+    m_c = copy.deepcopy(m_a).set_backend("hip")
+    m_b = copy.deepcopy(m_a)
+    stages_b = torch.nn.ModuleDict({n: getattr(m_b, n) for n in ("conv1", "bn1", "layer1", "layer2", "layer3", "layer4")})
+    stages_b.to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+
+    def stem_b(x):
+        return m_b.maxpool(F.relu(A.FrozenBasicBlock._bn(m_b.conv1(x), m_b.bn1)))
+
+    def l123(m, h):
+        return m.layer3(m.layer2(m.layer1(h)))
+
+    def tail(m, f):
+        return torch.flatten(m.avgpool(m.layer4(f)), 1)
+
+    def whole_b(x):
+        f = l123(m_b, stem_b(x.to(dtype=torch.bfloat16, memory_format=torch.channels_last)))
+        f = A.ResFormerTokens.forward(m_b, f.float()).to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+        return tail(m_b, f).float()
+
+    clock_before = shader_clock()
+    result = {}
+    with torch.no_grad():
+        for Bp in args.frames:
+            x = torch.randn(Bp, 3, args.size, args.size, device=dev)
+            h = m_a.stem(x)                                              # [B', 64, 28, 28]
+            f3 = l123(m_a, h)                                            # [B', 256, 7, 7]
+            h_b = h.to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+            f3_b = f3.to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+            tok = f3.permute(0, 2, 3, 1).reshape(Bp, -1, f3.shape[1]).contiguous()   # what the transformer hands to layer4 in arm c
+            hw = tuple(f3.shape[2:])
+            arms = {"a_l123": lambda: l123(m_a, h), "b_l123": lambda: l123(m_b, h_b), "c_l123": lambda: m_c.stages_to_tokens(h),
+                    "a_tail": lambda: tail(m_a, f3), "b_tail": lambda: tail(m_b, f3_b), "c_tail": lambda: m_c.tokens_to_features(tok, hw),
+                    "a_whole": lambda: m_a(x), "b_whole": lambda: whole_b(x), "c_whole": lambda: m_c(x)}
+            for fn in arms.values():
+                for _ in range(args.warmup):
+                    fn()
+            torch.cuda.synchronize()
+            want = m_a(x)
+            err = {k: float((arms[k]().float() - want).norm() / want.norm()) for k in ("b_whole", "c_whole")}
+            runs = {k: [] for k in arms}
+            for r in range(args.groups):
+                for name, fn in arms.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.calls):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    runs[name].append(round(e0.elapsed_time(e1) / args.calls, 5))
+                print(f"B'={Bp} group {r + 1}: " + "  ".join(f"{k} {v[-1]:.3f}" for k, v in runs.items()) + " ms", flush=True)
+            med = {k: statistics.median(v) for k, v in runs.items()}
+
+            # every distinct conv shape of the stages, alone
+            shapes, seen, xs = [], set(), stage_conv_shapes(m_c, Bp, h.shape[2], h.shape[3])
+            for (N, H, W, Cin, Cout, k, s) in xs:
+                if (N, H, W, Cin, Cout, k, s) in seen:
+                    continue
+                seen.add((N, H, W, Cin, Cout, k, s))
+                xi = torch.randn(N, H, W, Cin, device=dev).bfloat16()
+                wp = torch.randn(Cout, k * k * Cin, device=dev).bfloat16()
+                sc = torch.ones(Cout, device=dev)
+                out = A.ops.conv2d_nhwc(xi, wp, sc, sc, k, s, relu=True)
+                n = 20 if Bp <= 64 else 5
+                t = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(n):
+                        A.ops.conv2d_nhwc(xi, wp, sc, sc, k, s, relu=True, out=out)
+                    e1.record()
+                    e1.synchronize()
+                    t.append(e0.elapsed_time(e1) / n)
+                ms = statistics.median(t)
+                flops = 2.0 * out.numel() * k * k * Cin
+                shapes.append({"x": [N, H, W, Cin], "Cout": Cout, "k": k, "stride": s, "M": out.numel() // Cout, "K": k * k * Cin,
+                               "tile": A.ops.conv_plan(N, H, W, Cin, Cout, k, s)["tile"], "ms": round(ms, 5),
+                               "tflops": round(flops / ms / 1e9, 2), "fraction_of_bf16_peak": round(flops / (ms * 1e-3) / PEAK_BF16, 4)})
+            # device operations of arm c from the stage-3 tokens to the pooled features
+            st = m_c.spatial_transformer
+            t_in = tok + m_c.pos_embedding
+            n_mid, names_mid = device_ops(lambda: m_c.tokens_to_features(st(tok + m_c.pos_embedding[:, :tok.shape[1]]), hw))
+            n_st, _ = device_ops(lambda: st(t_in))
+            permutes = None if n_mid is None else [n for n in names_mid if any(s in n.lower() for s in ("permute", "transpose", "copy"))]
+            result[str(Bp)] = {
+                "ms_per_call": runs, "median_ms_per_call": med,
+                "spread_ms_max_minus_min": {k: round(max(v) - min(v), 5) for k, v in runs.items()},
+                "c_over_b": {s: round(med["c_" + s] / med["b_" + s], 3) for s in ("l123", "tail", "whole")},
+                "c_over_a": {s: round(med["c_" + s] / med["a_" + s], 3) for s in ("l123", "tail", "whole")},
+                "rel_fro_vs_a_whole": err, "conv_shapes": shapes,
+                "tokens_to_features_device_ops": {"count": n_mid, "of_the_token_section_alone": n_st, "names": names_mid,
+                                                  "expected_next_to_the_token_section": "1 positional add + 5 conv launches + 1 pool = 7",
+                                                  "permute_or_copy_kernels": permutes}}
+            del x, h, f3, h_b, f3_b, tok
+    out = {"name": args.name, "frame_counts": args.frames, "size": args.size, "box": box_id(), "clock_before": clock_before,
+           "clock_after": shader_clock(), "device": torch.cuda.get_device_name(0), "alternations": args.groups,
+           "calls_per_group": args.calls, "warmup_calls": args.warmup, "bf16_peak_flops_assumed": PEAK_BF16,
+           "launch": "eager, device events around the calls, inputs already on the device, torch.no_grad()", "frames": result}
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, args.name + ".json"), "w") as f:
+        json.dump(out, f, indent=1)
+    for Bp, r in result.items():
+        print(json.dumps({"frames": Bp, "median_ms_per_call": r["median_ms_per_call"], "c_over_b": r["c_over_b"], "c_over_a": r["c_over_a"],
+                          "rel_fro_vs_a_whole": r["rel_fro_vs_a_whole"],
+                          "device_ops": {k: r["tokens_to_features_device_ops"][k] for k in ("count", "of_the_token_section_alone", "permute_or_copy_kernels")}}))
+        for s in r["conv_shapes"]:
+            print(json.dumps(s))
+
+
+def stage_conv_shapes(model, Bp, H, W):
+    """(N, H, W, Cin, Cout, k, stride) of every conv launch of layer1 .. layer4, in order"""
+    out = []
+    for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
+        for blk in stage:
+            s = blk.stride
+            out.append((Bp, H, W, blk.inplanes, blk.planes, 3, s))
+            if blk.downsample is not None:
+                out.append((Bp, H, W, blk.inplanes, blk.planes, 1, s))
+            H, W = (H - 1) // s + 1, (W - 1) // s + 1
+            out.append((Bp, H, W, blk.planes, blk.planes, 3, 1))
+    return out
+
+
+if __name__ == "__main__":
+    main()
