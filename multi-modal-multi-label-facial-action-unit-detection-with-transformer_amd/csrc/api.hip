@@ -261,12 +261,10 @@ extern "C" int avf_gemm(int dtype, int transA, int transB, int64_t M, int64_t N,
                         const void* B, int64_t ldb, void* C, int64_t ldc, int c_dtype, int epilogue, const float* bias,
                         const float* residual, int64_t ldres, void* aux, int64_t ldaux, void* workspace, void* stream) {
   AVF_REQUIRE(A && B && C, "gemm: null pointer");
-  GemmArgs a;
-  a.dtype = dtype; a.transA = transA; a.transB = transB;
-  a.M = M; a.N = N; a.K = K;
+  GemmArgs a = gemm_dense(dtype, transA, transB, M, N, K);
   a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
   a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
-  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace; a.colsum = nullptr; a.drop = kNoDrop; a.defer_fold = nullptr;
+  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace;
   return gemm(a, (hipStream_t)stream);
 }
 
@@ -277,54 +275,43 @@ extern "C" size_t avf_gemm_nt_ws_workspace_bytes(int64_t M, int64_t N) { return 
 // 1 when avf_gemm / the layer calls send this shape and epilogue to the persistent kernel (aligned operands, no dropout, no
 // column sums except on DGELU): what a test or a profile tool asks to know which kernel it is looking at
 extern "C" int avf_gemm_nt_ws_dispatch(int64_t M, int64_t N, int64_t K, int epilogue, int c_dtype) {
-  GemmArgs a;
-  a.dtype = AVF_BF16; a.transA = 0; a.transB = 1;
-  a.M = M; a.N = N; a.K = K;
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
   void* aligned = (void*)(uintptr_t)256;  // never dereferenced: the predicates look at alignment only
-  a.A = aligned; a.lda = K; a.B = nullptr; a.ldb = K; a.C = aligned; a.ldc = N;
-  a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = (epilogue == AVF_EPI_BIAS_RES || epilogue == AVF_EPI_BIAS_GELU) ? (const float*)aligned : nullptr;
-  a.residual = epilogue == AVF_EPI_BIAS_RES ? aligned : nullptr; a.ldres = N;
-  a.aux = (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) ? aligned : nullptr; a.ldaux = N;
-  a.workspace = nullptr; a.colsum = nullptr; a.drop = kNoDrop; a.defer_fold = nullptr;
-  a.Bp = aligned; a.ws_force = 0; a.mx_q = nullptr; a.mx_s = nullptr;
+  a.A = aligned; a.C = aligned; a.Bp = aligned;
+  a.c_dtype = c_dtype; a.epilogue = epilogue;
+  if (epilogue == AVF_EPI_BIAS_RES || epilogue == AVF_EPI_BIAS_GELU) a.bias = (const float*)aligned;
+  if (epilogue == AVF_EPI_BIAS_RES) a.residual = aligned;
+  if (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) a.aux = aligned;
   return gemm_bf16_nt_ws_preferred(a) ? 1 : 0;
 }
 // ---- the tiled / register-staged bf16 NT GEMM with everything a layer can ask of it (test plumbing) ----
-static int fill_nt_ex(GemmArgs* a, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
-                      int64_t ldc, int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux,
-                      int64_t ldaux, void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site,
-                      float p, const char* who) {
-  AVF_REQUIRE(A && B && C, "%s: null pointer", who);
-  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "%s: bad dropout site %d / p %g", who, site, (double)p);
-  a->dtype = AVF_BF16; a->transA = 0; a->transB = 1;
-  a->M = M; a->N = N; a->K = K;
-  a->A = A; a->lda = lda; a->B = B; a->ldb = ldb; a->C = C; a->ldc = ldc;
-  a->c_dtype = c_dtype; a->epilogue = epilogue; a->bias = bias; a->residual = residual; a->ldres = ldres;
-  a->aux = aux; a->ldaux = ldaux; a->workspace = workspace; a->colsum = colsum;
-  a->drop = p > 0.f ? make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site) : kNoDrop;
-  a->defer_fold = nullptr;
-  a->Bp = nullptr; a->ws_force = 0; a->mx_q = nullptr; a->mx_s = nullptr;
-  return 0;
-}
 extern "C" int avf_gemm_nt_ex(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                               int64_t ldc, int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres,
                               void* aux, int64_t ldaux, void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi,
                               int layer_index, int site, float p, void* stream) {
-  GemmArgs a;
-  AVF_TRY(fill_nt_ex(&a, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, epilogue, bias, residual, ldres, aux, ldaux, workspace, colsum,
-                     seed_lo, seed_hi, layer_index, site, p, "gemm_nt_ex"));
+  AVF_REQUIRE(A && B && C, "gemm_nt_ex: null pointer");
+  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "gemm_nt_ex: bad dropout site %d / p %g", site, (double)p);
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
+  a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
+  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace; a.colsum = colsum;
+  if (p > 0.f) a.drop = make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site);
   return gemm_bf16_nt(a, (hipStream_t)stream);
 }
 extern "C" int avf_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int c_dtype, int epilogue,
                                 int has_bias, int64_t ldres, int64_t ldaux, int want_colsum, float p, int* kind, int* tile,
                                 int* lean, int* wpf) {
   AVF_REQUIRE(kind && tile && lean && wpf, "gemm_nt_plan: null pointer");
+  AVF_REQUIRE(p >= 0.f && p < 1.f, "gemm_nt_plan: bad dropout site %d / p %g", 0, (double)p);
   void* aligned = (void*)(uintptr_t)256;  // never dereferenced: the predicates look at null-ness and alignment only
-  GemmArgs a;
-  AVF_TRY(fill_nt_ex(&a, M, N, K, aligned, lda, aligned, ldb, aligned, ldc, c_dtype, epilogue, has_bias ? (const float*)aligned : nullptr,
-                     epilogue == AVF_EPI_BIAS_RES ? aligned : nullptr, ldres,
-                     (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) ? aligned : nullptr, ldaux,
-                     want_colsum ? aligned : nullptr, want_colsum ? (float*)aligned : nullptr, 1u, 0u, 0, 0, p, "gemm_nt_plan"));
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = aligned; a.lda = lda; a.B = aligned; a.ldb = ldb; a.C = aligned; a.ldc = ldc;
+  a.c_dtype = c_dtype; a.epilogue = epilogue; a.ldres = ldres; a.ldaux = ldaux;
+  if (has_bias) a.bias = (const float*)aligned;
+  if (epilogue == AVF_EPI_BIAS_RES) a.residual = aligned;
+  if (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) a.aux = aligned;
+  if (want_colsum) { a.workspace = aligned; a.colsum = (float*)aligned; }
+  if (p > 0.f) a.drop = make_drop(p, 1, 0, 0);
   NtPlan pl;
   AVF_TRY(gemm_bf16_nt_plan(a, &pl));
   *kind = pl.kind; *tile = pl.tile; *lean = pl.lean; *wpf = pl.wpf;
@@ -337,12 +324,10 @@ extern "C" int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, in
                               int64_t ldc, int c_dtype, int epilogue, const float* bias, const void* residual, int64_t ldres,
                               void* aux, int64_t ldaux, void* workspace, float* colsum, void* mx_q, void* mx_s, void* stream) {
   AVF_REQUIRE(A && B_packed && C, "gemm_nt_ws: null pointer");
-  GemmArgs a;
-  a.dtype = AVF_BF16; a.transA = 0; a.transB = 1;
-  a.M = M; a.N = N; a.K = K;
-  a.A = A; a.lda = lda; a.B = nullptr; a.ldb = K; a.C = C; a.ldc = ldc;
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = A; a.lda = lda; a.C = C; a.ldc = ldc;
   a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
-  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace; a.colsum = colsum; a.drop = kNoDrop; a.defer_fold = nullptr;
+  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace; a.colsum = colsum;
   a.Bp = B_packed; a.ws_force = 1;
   a.mx_q = mx_q; a.mx_s = mx_s;
   AVF_REQUIRE(gemm_bf16_nt_ws_ok(a), "gemm_nt_ws: the weight-stationary kernel takes K == 512, N %% 256 == 0, M >= 2048, 16-byte "
@@ -430,12 +415,10 @@ extern "C" int avf_gemm_mx8_nt(int64_t M, int64_t N, int64_t K, const void* a_q,
                                const float* residual, int64_t ldres, void* aux, int64_t ldaux, void* c_q, void* c_scales,
                                void* stream) {
   AVF_REQUIRE(a_q && a_scales && b_q && b_scales && C, "gemm_mx8_nt: null pointer");
-  GemmArgs a;
-  a.dtype = AVF_BF16; a.transA = 0; a.transB = 1;
-  a.M = M; a.N = N; a.K = K;
-  a.A = a_q; a.lda = K; a.B = b_q; a.ldb = K; a.C = C; a.ldc = ldc;
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = a_q; a.B = b_q; a.C = C; a.ldc = ldc;
   a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
-  a.aux = aux; a.ldaux = ldaux; a.workspace = nullptr; a.colsum = nullptr; a.drop = kNoDrop; a.defer_fold = nullptr;
+  a.aux = aux; a.ldaux = ldaux;
   return gemm_mx8_nt(a, a_scales, b_scales, (hipStream_t)stream, c_q, c_scales);
 }
 

@@ -512,26 +512,23 @@ struct PrepDesc { const float* w; bf16* lo; bf16* t; int R, C; float lo_scale; i
 struct PrepBatch { PrepDesc d[4]; };
 int prep_weights_multi(const PrepBatch& b, int count, hipStream_t s);
 
+// Every field has a default: a filler sets only what it means.
 struct GemmArgs {
-  int dtype, transA, transB;
-  int64_t M, N, K;
-  const void* A;
-  int64_t lda;
-  const void* B;
-  int64_t ldb;
-  void* C;
-  int64_t ldc;
-  int c_dtype;
-  int epilogue;
-  const float* bias;
-  const void* residual;  // BIAS_RES: fp32 when C is fp32; bf16 when C is bf16 (bf16 residual stream)
-  int64_t ldres;
-  void* aux;
-  int64_t ldaux;
-  void* workspace;
-  float* colsum;  // optional: column sums of the stored C (bf16 NT only; partials go to workspace)
-  DropCfg drop;   // bf16 NT only: BIAS_RES masks (acc+bias) before the residual, BIAS_GELU masks gelu(u), DGELU masks acc
-  FoldJob* defer_fold;  // with colsum: do not launch the fold, describe it here instead
+  int dtype = AVF_F32, transA = 0, transB = 0;
+  int64_t M = 0, N = 0, K = 0;
+  const void *A = nullptr, *B = nullptr;
+  void* C = nullptr;
+  int64_t lda = 0, ldb = 0, ldc = 0;
+  int c_dtype = AVF_F32;
+  int epilogue = AVF_EPI_NONE;
+  const float* bias = nullptr;
+  const void* residual = nullptr;  // BIAS_RES: fp32 when C is fp32; bf16 when C is bf16 (bf16 residual stream)
+  void* aux = nullptr;
+  int64_t ldres = 0, ldaux = 0;
+  void* workspace = nullptr;
+  float* colsum = nullptr;  // optional: column sums of the stored C (bf16 NT only; partials go to workspace)
+  DropCfg drop = kNoDrop;   // bf16 NT only: BIAS_RES masks (acc+bias) before the residual, BIAS_GELU masks gelu(u), DGELU masks acc
+  FoldJob* defer_fold = nullptr;  // with colsum: do not launch the fold, describe it here instead
   // bf16 NT only, optional: the fragment-major image of B (pack_ws; K == 512, N % 256 == 0) - the GEMM then runs on the
   // weight-stationary persistent kernel (gemm_ws.hip) when the shape qualifies
   const void* Bp = nullptr;
@@ -541,6 +538,16 @@ struct GemmArgs {
   void* mx_q = nullptr;
   void* mx_s = nullptr;
 };
+// C[M, N] = op(A) op(B) on dense row-major operands: the leading dimensions follow from the form (NT: C = A B^T, the nn.Linear
+// forward and the bf16 dX on a transposed weight image; NN: the fp32 dX; TN: dW = dY^T X).  ldres / ldaux are C's.
+// a: fields a caller has set already (an epilogue, say); shape and leading dimensions are filled in here.
+inline GemmArgs gemm_dense(int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K, GemmArgs a = {}) {
+  a.dtype = dtype; a.transA = transA; a.transB = transB;
+  a.M = M; a.N = N; a.K = K;
+  a.lda = transA ? M : K; a.ldb = transB ? K : N;
+  a.ldc = a.ldres = a.ldaux = N;
+  return a;
+}
 // weight-stationary persistent NT GEMM (gemm_ws.hip; DESIGN_HISTORY.md section 18)
 // byte offset of element (n, k) of a weight [N][512] in its fragment-major image: 1 KiB pieces (panel of 256 rows, wave's 32
 // rows, 16-row block j, k-step s of 32), inside a piece lane (li = n % 16, lg = (k % 32) / 8) owns 16 bytes = 8 consecutive k
