@@ -681,6 +681,12 @@ int avf_layer_fwd(const avf_layer_cfg* cfg, const avf_layer_params* p, const voi
  *     LNR8_TOK_MAX_BATCH).  d_pos and this layer's LayerNorm-1 gradients are summed in another order than by the plain entries
  *     (fp32 rounding level), deterministically; every other gradient is bit-identical. */
 int avf_layer_fwd_embed_ok(const avf_layer_cfg* cfg);
+/* Which kernels a layer of this configuration runs (pure host code, computed by the expressions the dispatch itself uses): a bit
+ * set - bit 0: avf_layer_fwd is the single-launch short-sequence forward; bit 1: avf_layer_bwd runs the two fused short-sequence
+ * kernels; bit 2: the second of them also runs the attention backward.  0: the per-operator path (or an invalid cfg).  The
+ * short-sequence kernels take dtype AVF_BF16, dim_head 32, 1..16 tokens, dim / heads * dim_head / mlp_dim in {128, 256}, the fp32
+ * residual stream, no mx8 and no key mask. */
+int avf_layer_small_path(const avf_layer_cfg* cfg);
 /* ... and the two LayerNorm launches behind them as operators.  avf_layernorm_fwd_embed: x0 = bf16(cat([clip, audio], 1) + pos)
  * [B*(t_video+t_audio), D] and y (bf16), mean, rstd = LayerNorm(x0); dim % 8 == 0, dim <= 1536, t_video > 0, t_audio > 0.
  * avf_layernorm_bwd_pos: the all-bf16 LayerNorm backward (dy, x, dres [batch*tokens, D] bf16; dres nullable) reduced over the

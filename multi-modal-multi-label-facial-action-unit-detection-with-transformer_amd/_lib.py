@@ -168,6 +168,7 @@ SIGNATURES = {
     "avf_layernorm_bwd_pos_workspace_bytes": (_sz, [_int, _int, _int]),
     "avf_layernorm_bwd_pos": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
     "avf_layer_fwd_embed_ok": (_int, [C.POINTER(LayerCfg)]),
+    "avf_layer_small_path": (_int, [C.POINTER(LayerCfg)]),
     "avf_layer_fwd_embed": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "avf_layer_bwd_pos_ok": (_int, [C.POINTER(LayerCfg)]),
     "avf_layer_bwd_pos": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp,

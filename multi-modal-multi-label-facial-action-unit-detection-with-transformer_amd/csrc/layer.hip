@@ -454,6 +454,26 @@ extern "C" int avf_layer_bwd_pos_ok(const avf_layer_cfg* cfg) {
   return !make_dims(cfg, &d) && stack_ends_mode_ok(d) && layernorm_bwd_tok_ok(d.B, d.N, d.D);
 }
 
+// The three decisions of the short-sequence layer (layer_small.hip), each taken at ONE place - layer_fwd_impl, LayerBwd::begin,
+// LayerBwd::small - and answered to a caller by avf_layer_small_path from the same three functions.
+static bool small_fwd_taken(const Dims& d) {  // the whole forward in one launch
+  return !d.mx && !d.rs16 && !d.keep && small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M);
+}
+static bool small_bwd_taken(const Dims& d) {  // the two fused kernels around the attention backward
+  static const int small_bwd_on = tuning_int("AVF_LAYER_SMALL_BWD", 1);  // tuning / A-B aid
+  return d.dt == AVF_BF16 && !d.rs16 && !d.mx && !d.keep && small_bwd_on && small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M);
+}
+static bool small_att_fused(const Dims& d) {  // ... the second of which runs the attention backward itself
+  static const int small_att_on = tuning_int("AVF_LAYER_SMALL_ATT", 1);  // tuning / A-B aid: 0 = per-operator attention backward
+  return small_att_on && d.H <= 16;
+}
+extern "C" int avf_layer_small_path(const avf_layer_cfg* cfg) {
+  Dims d;
+  if (make_dims(cfg, &d)) return 0;
+  const bool bwd = small_bwd_taken(d);
+  return (small_fwd_taken(d) ? 1 : 0) | (bwd ? 2 : 0) | (bwd && small_att_fused(d) ? 4 : 0);
+}
+
 // emb (avf_layer_fwd_embed): the layer's input is cat([clip, audio], 1) + pos; LayerNorm-1 builds it and stores it as emb->x0
 struct EmbedSrc { const float *clip, *audio, *pos; int t_video; void* x0; };
 struct LayerFwdIO { const void* x_in; void *x_out, *saved; const EmbedSrc* emb; };  // x_in: null with emb
@@ -502,7 +522,7 @@ static int layer_fwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, c
     // out-proj: its A operand is produced per head; the head-resident attention kernel writes the image from its epilogue
     static const int o_mx_on = tuning_int("AVF_MX8_OUTPROJ", 1);  // tuning / A-B aid: 0 = out-projection on bf16 operands
     o_mx = o_mx_on && !d.keep && attn_fwd_emits_mx8(d.N, d.dh) && d.I % 128 == 0;
-  } else if (!d.rs16 && !d.keep && small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M)) {  // short sequences: the whole layer in one launch
+  } else if (small_fwd_taken(d)) {  // short sequences: the whole layer in one launch
     const bool lo = d.dt == AVF_BF16;
     const float sc = attn_q_prescale_on() ? 1.0f : 1.4426950408889634f / sqrtf((float)d.dh);
     return layer_fwd_small(d.B, d.N, d.D, d.H, d.M, cfg->ln_eps, sc, p, lo ? qkv.lo : (const void*)qkv.w, lo ? out.lo : (const void*)out.w,
@@ -622,8 +642,7 @@ int LayerBwd::begin(const avf_layer_cfg* cfg, const avf_layer_params* params, co
   dr = make_drops(d);
   // short sequences (the reference's 12-token stacks): the six dependent launches around the attention backward run as two
   // fused kernels (layer_small.hip), which also make the bf16 image of the incoming gradient when the caller gave none
-  static const int small_bwd_on = tuning_int("AVF_LAYER_SMALL_BWD", 1);  // tuning / A-B aid
-  small_bwd = lo && !d.rs16 && !d.mx && !d.keep && small_bwd_on && small_layer_ok(d.dt, d.N, d.D, d.H, d.dh, d.M);
+  small_bwd = small_bwd_taken(d);
   if (d.mxb && io.dx_in_lo) {
     inq = (char*)io.dx_in_lo + grad_q_off(d.R, d.D);
     ins = (char*)io.dx_in_lo + grad_s_off(d.R, d.D);
@@ -722,8 +741,7 @@ int LayerBwd::small() {
   ha.dr0 = dr.site0; ha.dr1 = dr.site1; ha.dr2 = dr.site2;
   AVF_TRY(layer_bwd_small_a(d.B, d.N, d.D, d.I, d.M, ha, s));
   AVF_TRY(db2());
-  static const int small_att_on = tuning_int("AVF_LAYER_SMALL_ATT", 1);  // tuning / A-B aid: 0 = per-operator attention backward
-  const bool fuse_att = small_att_on && d.H <= 16;
+  const bool fuse_att = small_att_fused(d);
   if (!fuse_att)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
                           d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), w.delta + (size_t)d.B * d.H * d.N));

@@ -558,6 +558,16 @@ def attn_masked_on_mfma(tokens: int, dim_head: int) -> bool:
     return bool(_lib.load().avf_attn_masked_on_mfma(int(tokens), int(dim_head)))
 
 
+LAYER_SMALL_FWD, LAYER_SMALL_BWD, LAYER_SMALL_ATT = 1, 2, 4
+
+
+def layer_small_path(cfg: "_lib.LayerCfg") -> int:
+    """which kernels a layer of this configuration (``Transformer._cfg(batch, tokens, keep=...)``) runs (avf_layer_small_path, pure
+    host code): LAYER_SMALL_FWD - the single-launch short-sequence forward, LAYER_SMALL_BWD - the two fused backward kernels,
+    LAYER_SMALL_ATT - the second of them runs the attention backward too; 0: the per-operator path"""
+    return int(_lib.load().avf_layer_small_path(C.byref(cfg)))
+
+
 def attn_fwd_masked(qkv: torch.Tensor, keep: torch.Tensor, batch: int, tokens: int, heads: int, dim_head: int,
                     q_prescaled: bool = False):
     """attn_fwd with the token mask of heads.py:225-232: keep [B, N] uint8 / bool, 1 = token kept (the reference's mask after

@@ -30,3 +30,10 @@ def test_fuzz_layer_fixed_budget(seed):
     """whole stacks at random widths / token counts: the parity mode (both arithmetics) against the CPU oracle's autograd, the
     bf16 / bf16-residual / mx8 modes at their bounds - 12 configurations per seed"""
     _load("fuzz_layer").run(count=12, seed=seed, verbose=False)
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_fuzz_small_layer_fixed_budget(seed):
+    """random eligible shapes of the short-sequence fused layer kernels (widths 128 / 256, 1..16 tokens, 1..3 layers, up to 64
+    clips), bf16 against the parity mode on the same weights, each asserted to run the fused kernels - 8 configurations per seed"""
+    _load("fuzz_small_layer").run(count=8, seed=seed, verbose=False, max_batch=64)
