@@ -783,6 +783,33 @@ int avf_conv2d_nhwc(const void* x, int x_dtype, const void* w_packed, const floa
 int avf_conv_plan(int N, int H, int W, int Cin, int Cout, int k, int stride, int* tile, int* tile_m, int* tile_n);
 int avf_avgpool_nhwc(const void* x, int x_dtype, float* out, int64_t N, int HW, int C, void* stream);
 
+/* ---- frozen ResNet stem, forward only (csrc/stem.hip) -----------------------------------------------------------------------
+ * What stands in front of layer1: conv1 (7x7, stride 2, pad 3, bias=False) - bn1 - relu - maxpool (3x3, stride 2, pad 1) of
+ * ResFormer.forward (vformer.py:238-241) and of the audio stream's ResNet18 (audio.py:22-39, one input channel), in ONE launch
+ * from the front ends' NCHW planes to the NHWC map avf_conv2d_nhwc reads.  BatchNorm2d is folded in eval mode.  No gradients.
+ *   avf_stem_packed_k: Kp, the row length of the packed weight image for Cin input channels (Cin in {1, 3, 4}: 64 / 192 / 224);
+ *     0 and an error message for any other Cin.
+ *   avf_stem_pack_weight: w [64, Cin, 7, 7] fp32 -> w_packed [64, Kp] bf16 (RNE); the order of a row and its zero padding are the
+ *     kernel's own (csrc/stem.hip).  scale / shift [64] fp32 as avf_conv_pack_weight folds them (fp64), not multiplied into the
+ *     weights.  Cout must be 64 and Cin in {1, 3, 4}: anything else is an error that names the limit.  Once per weight load.
+ *   avf_stem_nchw: out[n, py, px, co] = max over the 3x3 window (2 py - 1 + dy, 2 px - 1 + dx) INSIDE the Hc x Wc conv map of
+ *     relu( (sum_{ci,ky,kx} x[n, ci, 2 cy - 3 + ky, 2 cx - 3 + kx] * w[co, ci, ky, kx]) * scale[co] + shift[co] ); positions outside
+ *     the image count as zero for the convolution and are never read, positions outside the conv map take no part in the max.
+ *     Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1, the same for W; any H, W >= 1.  x [N, Cin, H, W] contiguous planes, fp32
+ *     (rounded to bf16, RNE, as it is staged) or bf16, aligned to its element only (a 1001-wide row is not 16-byte aligned);
+ *     nothing outside [x, x + N*Cin*H*W) is read.  out [N, Hp, Wp, 64] NHWC, fp32 or bf16 (RNE), 16-byte aligned as are
+ *     w_packed / scale / shift; out may not overlap an input.  bf16 products accumulate in fp32 (v_mfma_f32_16x16x32_bf16); the
+ *     epilogue and the max are fp32 arithmetic with one rounding per stored value.  Every global index is 64-bit.
+ *   avf_stem_plan: the tile of POOLED outputs (of one image) a workgroup owns for this shape: *tile_h x *tile_w.  It computes the
+ *     (2 tile_h + 1) x (2 tile_w + 1) conv pixels the tile needs itself (halo recompute).  Same argument checks as the launch. */
+int avf_stem_packed_k(int Cin);
+int avf_stem_pack_weight(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                         const float* running_var, double eps, void* w_packed, float* scale, float* shift, int Cout, int Cin,
+                         void* stream);
+int avf_stem_nchw(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
+                  int out_dtype, int N, int Cin, int H, int W, void* stream);
+int avf_stem_plan(int N, int Cin, int H, int W, int* tile_h, int* tile_w);
+
 /* test aid: the keep/(1-p) factors (0 or 1/(1-p_eff)) dropout site `site` (0 after to_out, 1 after GELU, 2 after
  * net.3) of layer `layer_index` applies to a [rows, cols] activation, as fp32 [rows, cols] (cols % 4 == 0). */
 int avf_dropout_factors(uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site, float p, int64_t rows, int cols,

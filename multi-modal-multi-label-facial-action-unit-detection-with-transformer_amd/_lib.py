@@ -149,6 +149,10 @@ SIGNATURES = {
     "avf_conv2d_nhwc": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "avf_conv_plan": (_int, [_int, _int, _int, _int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_avgpool_nhwc": (_int, [_vp, _int, _vp, _i64, _int, _int, _vp]),
+    "avf_stem_packed_k": (_int, [_int]),
+    "avf_stem_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _vp]),
+    "avf_stem_nchw": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _vp]),
+    "avf_stem_plan": (_int, [_int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

@@ -1,5 +1,6 @@
 """The frozen ResNet stages of the reference's S-Former (``ResFormer``, vformer.py:128-268; copied in sformer.py, tformer.py,
-dual_sformer.py): ``FrozenBasicBlock`` and ``FrozenResFormer``, forward only.
+dual_sformer.py): ``FrozenBasicBlock`` and ``FrozenResFormer``, and the audio stream's ResNet18 (``AudioModel``, audio.py:22-39):
+``FrozenAudioModel``; forward only.
 
 "Frozen" means eval-mode here: BatchNorm2d always uses its running statistics, whatever ``train()`` says.  That is exact for
 ``evaluate()`` (train.py:106-169) and whole-dataset inference (test_aff2.py); the reference itself runs the BatchNorm of its
@@ -9,7 +10,9 @@ package does not reproduce.
 Every module takes ``backend=``: ``"torch"`` (default) is the definition - the reference's op sequence in fp32, NCHW, runs
 anywhere; ``"hip"`` runs csrc/conv.hip: NHWC activations, bf16 between launches, each conv one launch with the folded BatchNorm,
 the identity add and the ReLU in its epilogue.  The stage-3 map [B', 7, 7, 256] in NHWC IS the token tensor [B', 49, 256], so the
-hip backend runs no map/token permute on either side of ``spatial_transformer``.
+hip backend runs no map/token permute on either side of ``spatial_transformer``.  ``stem="hip"`` (with ``backend="hip"``) runs
+``conv1`` / ``bn1`` / ReLU / ``maxpool`` as the one launch of csrc/stem.hip, from NCHW planes straight to the NHWC bf16 map
+``layer1`` reads: no torch compute op and no layout conversion between the front end's planes and the pooled features.
 
 The hip backend computes no gradients: with grad mode on and an input or parameter that requires grad, ``forward`` raises
 instead of silently cutting the graph."""
@@ -25,6 +28,7 @@ from . import ops
 from .heads import ResFormerTokens
 
 BACKENDS = ("torch", "hip")
+STEMS = ("torch", "hip")
 _CH = 32  # the conv kernel's channel granule (Cin % 32 == 0): other widths run zero-padded to it
 
 
@@ -32,6 +36,14 @@ def _check_backend(backend):
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
     return backend
+
+
+def _check_stem(stem, backend):
+    if stem not in STEMS:
+        raise ValueError(f"stem must be one of {STEMS}, got {stem!r}")
+    if stem == "hip" and backend != "hip":
+        raise ValueError(f"stem='hip' is the first launch of the hip backend: it needs backend='hip' (got backend={backend!r})")
+    return stem
 
 
 def _pad_to(n: int) -> int:
@@ -142,20 +154,59 @@ class _Stage(nn.Sequential):
         return x
 
 
-class FrozenResFormer(ResFormerTokens):
+class _HipStem:
+    """``conv1`` - ``bn1`` - relu - ``maxpool`` of a ResNet (children ``conv1`` 7x7 / 2 / pad 3 with 1, 3 or 4 input channels,
+    ``bn1``, ``maxpool`` 3x3 / 2 / pad 1) in both forms: ``stem`` is the definition in torch ops, ``stem_nhwc`` the one launch of
+    csrc/stem.hip.  The packed stem image follows ``conv1`` / ``bn1`` as ``FrozenBasicBlock._pack`` follows its pairs: version
+    counters, and a ``load_state_dict`` hook; writes through ``.data`` bypass the counters: call ``refresh_weights()``."""
+    _stem_packed = None
+
+    def stem(self, x):
+        """conv1 - bn1 - relu - maxpool (vformer.py:238-241), eval-mode BatchNorm, torch ops: NCHW fp32 in and out"""
+        return self.maxpool(F.relu(FrozenBasicBlock._bn(self.conv1(x), self.bn1)))
+
+    def refresh_weights(self):
+        self._stem_packed = None
+        for m in self.modules():
+            if isinstance(m, FrozenBasicBlock):
+                m.refresh_weights()
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._stem_packed = None
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _stem_pack(self, device):
+        ts = (self.conv1.weight, self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var)
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+        if self._stem_packed is None or self._stem_packed[0] != key:
+            if not ts[0].is_cuda:
+                raise RuntimeError(f"{type(self).__name__}(stem='hip'): parameters must be on the MI355X (module.to('cuda')); "
+                                   "there is no CPU fallback")
+            self._stem_packed = (key, ops.stem_pack_weight(*[t.detach().float() for t in ts], eps=self.bn1.eps))
+        return self._stem_packed[1]
+
+    def stem_nhwc(self, x):
+        """x [N, Cin, H, W] fp32 or bf16 planes -> [N, Hp, Wp, 64] NHWC bf16, what ``layer1.forward_nhwc`` reads (ops.stem_nchw)"""
+        ops._need_cuda(x)
+        return ops.stem_nchw(x.contiguous(), *self._stem_pack(x.device))
+
+
+class FrozenResFormer(_HipStem, ResFormerTokens):
     """The whole S-Former, ``ResFormer(BasicBlock, layers)`` (vformer.py:168-268), with the reference's names - ``conv1``, ``bn1``,
     ``maxpool``, ``layer1`` .. ``layer4``, ``avgpool``, ``pos_embedding``, ``spatial_transformer.*`` - so that a reference checkpoint
     loads with every key matched.  x [B, T, C, H, W] or [B', C, H, W] -> [B', 512] fp32.
 
-    ``backend="hip"``: the 7x7 ``conv1`` / ``bn1`` / ReLU / ``maxpool`` stay torch ops (3 input channels need another kernel),
-    one NCHW -> NHWC bf16 conversion follows, then ``layer1`` .. ``layer3`` on the conv kernel; the last launch of ``layer3`` writes
+    ``backend="hip"``: with ``stem="torch"`` (default) the 7x7 ``conv1`` / ``bn1`` / ReLU / ``maxpool`` are torch ops and one NCHW
+    -> NHWC bf16 conversion follows; with ``stem="hip"`` they are the one launch of csrc/stem.hip, which reads x as it is and
+    writes that NHWC bf16 map (``in_channels`` 1, 3 or 4).  Then ``layer1`` .. ``layer3`` on the conv kernel; the last launch of ``layer3`` writes
     the fp32 tokens, ``pos_embedding`` is added, ``spatial_transformer`` runs, and its output goes straight into ``layer4``;
     ``avgpool`` is the NHWC pool kernel.  The token section is this package's ``Transformer`` with either backend, so the
     module needs the GPU either way."""
 
-    def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16"):
+    def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16", stem="torch"):
         super().__init__(dropout=dropout, compute_dtype=compute_dtype)
         self.backend = _check_backend(backend)
+        self.stem_backend = _check_stem(stem, backend)
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -179,20 +230,22 @@ class FrozenResFormer(ResFormerTokens):
         stage += [FrozenBasicBlock(planes, planes, backend=self.backend) for _ in range(1, blocks)]
         return _Stage(*stage)
 
-    def set_backend(self, backend):
-        self.backend = _check_backend(backend)
+    def set_backend(self, backend, stem=None):
+        """``stem=None`` keeps the stem where it is"""
+        stem = _check_stem(self.stem_backend if stem is None else stem, _check_backend(backend))
+        self.backend, self.stem_backend = backend, stem
         for m in self.modules():
             if isinstance(m, FrozenBasicBlock):
                 m.backend = backend
         return self
 
-    def stem(self, x):
-        """conv1 - bn1 - relu - maxpool (vformer.py:238-241), eval-mode BatchNorm, torch ops with either backend"""
-        return self.maxpool(F.relu(FrozenBasicBlock._bn(self.conv1(x), self.bn1)))
-
     def stages_to_tokens(self, x):
         """hip: the stem's NCHW output -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens + pos_embedding, (h, w))"""
-        x = self.layer3.forward_nhwc(self.layer2.forward_nhwc(self.layer1.forward_nhwc(to_nhwc(x))), out_dtype=torch.float32)
+        return self.nhwc_to_tokens(to_nhwc(x))
+
+    def nhwc_to_tokens(self, x):
+        """hip: the stem's NHWC bf16 map -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens + pos_embedding, (h, w))"""
+        x = self.layer3.forward_nhwc(self.layer2.forward_nhwc(self.layer1.forward_nhwc(x)), out_dtype=torch.float32)
         t = x.view(x.shape[0], x.shape[1] * x.shape[2], x.shape[3])               # NHWC IS [B', tokens, C]: no permute
         return t + self.pos_embedding[:, :t.shape[1]], (x.shape[1], x.shape[2])   # vformer.py:253
 
@@ -210,18 +263,82 @@ class FrozenResFormer(ResFormerTokens):
             return torch.flatten(self.avgpool(x), 1)
         ops._need_cuda(x)
         _no_grad_or_raise(self, x, "FrozenResFormer")
-        t, hw = self.stages_to_tokens(self.stem(x))
+        t, hw = self.nhwc_to_tokens(self.stem_nhwc(x)) if self.stem_backend == "hip" else self.stages_to_tokens(self.stem(x))
         return self.tokens_to_features(self.spatial_transformer(t), hw)
+
+
+class _FrozenResNet18(_HipStem, nn.Module):
+    """torchvision's ``resnet18`` as audio.py:25-31 rebuilds it - ``conv1`` with ``in_channels`` inputs, ``bn1``, ``relu``,
+    ``maxpool``, ``layer1`` .. ``layer4``, ``avgpool``, ``fc`` - with torchvision's state_dict keys, written out here because
+    torchvision is not a dependency.  ``fc`` is the identity, as avformer.py:50 leaves it."""
+
+    def __init__(self, layers=(2, 2, 2, 2), in_channels=1, backend="torch"):
+        super().__init__()
+        self.backend = backend
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(64, layers[0])
+        self.layer2 = self._make_layer(128, layers[1], stride=2)
+        self.layer3 = self._make_layer(256, layers[2], stride=2)
+        self.layer4 = self._make_layer(512, layers[3], stride=2)
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Identity()
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+
+    _make_layer = FrozenResFormer._make_layer
+
+    def forward(self, x):
+        if self.backend == "torch":
+            x = self.layer4(self.layer3(self.layer2(self.layer1(self.stem(x)))))
+            return self.fc(torch.flatten(self.avgpool(x), 1))
+        x = self.stem_nhwc(x)
+        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
+            x = stage.forward_nhwc(x)
+        return self.fc(ops.avgpool_nhwc(x))
+
+
+class FrozenAudioModel(nn.Module):
+    """``AudioModel`` (audio.py:22-39) with its fc replaced by the identity, as avformer.py:40-50 uses it: the mel map
+    [B, 1, 64, 1001] -> ``resnet`` (ResNet18 with a one-channel ``conv1``) -> [B, 512] fp32.  The state_dict keys are torchvision's
+    ResNet18 keys under ``resnet.``; a checkpoint's ``resnet.fc.*`` keys have no counterpart and are skipped by a
+    ``strict=False`` load.
+
+    ``backend="torch"`` (default) is the definition; ``backend="hip"`` is the stem kernel (csrc/stem.hip), the four stages on
+    the conv kernel and ``ops.avgpool_nhwc``: NCHW planes in, no torch compute op, forward only (``_no_grad_or_raise``)."""
+
+    def __init__(self, backend="torch", layers=(2, 2, 2, 2)):
+        super().__init__()
+        self.backend = _check_backend(backend)
+        self.resnet = _FrozenResNet18(layers, in_channels=1, backend=backend)
+        self.modes = ["audio_features"]
+
+    def set_backend(self, backend):
+        self.backend = self.resnet.backend = _check_backend(backend)
+        for m in self.modules():
+            if isinstance(m, FrozenBasicBlock):
+                m.backend = backend
+        return self
+
+    def forward(self, x):
+        if self.backend == "hip":
+            ops._need_cuda(x)
+            _no_grad_or_raise(self, x, "FrozenAudioModel")
+        return self.resnet(x)
 
 
 class FrozenVideoModel(nn.Module):
     """``VideoModel`` (vformer.py:295-311) with its fc replaced by the identity, as avformer.py:61-66 uses it: clip [B, C, T, H, W]
     -> the last ``num_channels`` channels -> ``s_former`` -> ``t_former`` -> [B, 512]"""
 
-    def __init__(self, backend="torch", compute_dtype="bf16"):
+    def __init__(self, backend="torch", compute_dtype="bf16", stem="torch"):
         super().__init__()
         from .heads import TFormer
-        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype)
+        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype, stem=stem)
         self.t_former = TFormer(compute_dtype=compute_dtype)
         self.num_channels = 3
 

@@ -17,6 +17,11 @@ from typing import Dict, Iterable, Optional, Tuple
 import torch
 
 DEFAULT_RENAMES = (("module.", ""), ("base_model.", "s_former."))
+# an ``AudioFormer`` / ``Audio_only`` checkpoint (avformer.py:40-50, audio.py:42-50: keys ``audio_model.resnet.*``, saved under
+# DataParallel as ``module.audio_model.resnet.*``) into a bare ``backbone.FrozenAudioModel`` (keys ``resnet.*``).  Into an
+# ``AudioFormer`` the default renames do: its child is called ``audio_model`` too.  ``resnet.fc.*`` has no counterpart
+# (the fc is the identity, avformer.py:50) and is skipped by the ``strict=False`` load, as the reference's loader skips it.
+AUDIO_MODEL_RENAMES = (("module.", ""), ("audio_model.", ""))
 
 
 def remap_state_dict(sd: Dict[str, torch.Tensor], renames: Iterable[Tuple[str, str]] = DEFAULT_RENAMES) -> "OrderedDict":

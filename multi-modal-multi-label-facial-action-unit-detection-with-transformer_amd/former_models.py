@@ -52,18 +52,21 @@ class ResFormerShell(ResFormerTokens):
         return self.tail(super().forward(self.stem(x)))
 
 
-FROZEN_BACKBONES = ("resnet18_frozen",)
+# "resnet18_frozen": the ResNet stages on the HIP conv kernel behind a torch stem; "resnet18_frozen_fused": the same module
+# with stem="hip" - conv1 / bn1 / relu / maxpool as the one launch of csrc/stem.hip (1, 3 or 4 input channels)
+FROZEN_BACKBONES = ("resnet18_frozen", "resnet18_frozen_fused")
 
 
 def _s_former(backbone, num_channels=3, **kw):
     """the S-Former of a ``*former`` model: ``backbone=None`` or a ``(stem, tail)`` pair -> ``ResFormerShell``;
     ``backbone="resnet18_frozen"`` -> ``backbone.FrozenResFormer`` on the HIP conv kernels (eval-mode stages, forward only), whose
-    ``conv1`` takes the ``num_channels`` channels the modality selects (vformer.py:313-331)"""
+    ``conv1`` takes the ``num_channels`` channels the modality selects (vformer.py:313-331); ``"resnet18_frozen_fused"`` -> the
+    same with the stem on its HIP kernel too"""
     if isinstance(backbone, str):
         if backbone not in FROZEN_BACKBONES:
             raise ValueError(f"backbone must be None, a (stem, tail) pair or one of {FROZEN_BACKBONES}, got {backbone!r}")
         from .backbone import FrozenResFormer
-        return FrozenResFormer(backend="hip", in_channels=num_channels, **kw)
+        return FrozenResFormer(backend="hip", in_channels=num_channels, stem="hip" if backbone.endswith("_fused") else "torch", **kw)
     return ResFormerShell(backbone, **kw)
 
 

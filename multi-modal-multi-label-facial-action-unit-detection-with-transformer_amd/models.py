@@ -8,7 +8,9 @@ unchanged.  Its CNN feature extractors (ResNet18 on mel-spectrograms, Former-DFE
 out of scope: ``AudioFormer`` / ``VisualFormer`` take a ``backbone``
 module and default to the identity, i.e. they consume per-clip feature vectors [B, 512]; ``VisualFormer(backbone="resnet18_frozen")``
 / ``TwoStreamAuralVisualFormer(video_backbone="resnet18_frozen")`` put the reference's frozen ``VideoModel`` there, its ResNet
-stages on the HIP conv kernels (backbone.py), and consume clips [B, C, T, H, W].
+stages on the HIP conv kernels (backbone.py), and consume clips [B, C, T, H, W] (``"resnet18_frozen_fused"``: its stem on the
+HIP stem kernel too); ``AudioFormer(backbone="resnet18_frozen")`` / ``TwoStreamAuralVisualFormer(audio_backbone="resnet18_frozen")``
+put the reference's frozen ``AudioModel`` (ResNet18, fc = identity) there on the same kernels and consume mel maps [B, 1, 64, 1001].
 
 ``SyntheticAVFormer`` is the BASELINE.json scale-up of the same block: video tokens [B,T_v,D] and
 audio tokens [B,T_a,D] fused on the SEQUENCE axis, + positional embedding -> Transformer(D, L) ->
@@ -38,6 +40,13 @@ def load_pretrain(model, weight_path):
 class AudioFormer(nn.Module):
     def __init__(self, modality='A', audio_pretrained=False, task='EX', backbone=None, compute_dtype="bf16"):
         super().__init__()
+        if isinstance(backbone, str):
+            # "resnet18_frozen": the reference's AudioModel (audio.py:22-39, fc = identity as in avformer.py:50) on the HIP stem and
+            # conv kernels - eval-mode, forward only (backbone.py); consumes mel maps [B, 1, 64, 1001]
+            if backbone != "resnet18_frozen":
+                raise ValueError(f"backbone must be None, a module or 'resnet18_frozen', got {backbone!r}")
+            from .backbone import FrozenAudioModel
+            backbone = FrozenAudioModel(backend="hip")
         self.audio_model = backbone if backbone is not None else nn.Identity()
         self.task = task
         self.modes = ['audio_features']
@@ -54,10 +63,12 @@ class VisualFormer(nn.Module):
         if isinstance(backbone, str):
             # "resnet18_frozen": the reference's own VideoModel (vformer.py:295-311, fc = identity as in avformer.py:61-66) with
             # its ResNet stages on the HIP conv kernels - eval-mode, forward only (backbone.py); consumes clips [B, C, T, H, W]
-            if backbone != "resnet18_frozen":
-                raise ValueError(f"backbone must be None, a module or 'resnet18_frozen', got {backbone!r}")
+            # "resnet18_frozen_fused": the same with the stem on its HIP kernel too (csrc/stem.hip)
+            from .former_models import FROZEN_BACKBONES
+            if backbone not in FROZEN_BACKBONES:
+                raise ValueError(f"backbone must be None, a module or one of {FROZEN_BACKBONES}, got {backbone!r}")
             from .backbone import FrozenVideoModel
-            backbone = FrozenVideoModel(backend="hip", compute_dtype=compute_dtype)
+            backbone = FrozenVideoModel(backend="hip", compute_dtype=compute_dtype, stem="hip" if backbone.endswith("_fused") else "torch")
         self.video_model = backbone if backbone is not None else nn.Identity()
         self.task = task
         self.modes = ["clip"]
@@ -147,10 +158,14 @@ class _TaskLossMixin:
 
 class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
     def __init__(self, modality='A;V;M', video_pretrained=True, audio_pretrained=True, task='EX',
-                 video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain", video_backbone=None):
+                 video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain", video_backbone=None,
+                 audio_backbone=None):
         super().__init__()
-        self.audio_model = AudioFormer(compute_dtype=compute_dtype)
-        # video_backbone="resnet18_frozen": the video stream consumes clips through the frozen S-Former on the HIP path
+        # audio_backbone="resnet18_frozen": the aural stream consumes mel maps [B, 1, 64, 1001] through the frozen ResNet18 on the
+        # HIP path (backbone.FrozenAudioModel)
+        self.audio_model = AudioFormer(backbone=audio_backbone, compute_dtype=compute_dtype)
+        # video_backbone="resnet18_frozen" / "resnet18_frozen_fused": the video stream consumes clips through the frozen S-Former on
+        # the HIP path (the second with its stem on the HIP kernel too)
         self.video_model = VisualFormer(backbone=video_backbone, compute_dtype=compute_dtype)
         if video_pretrained and load_pretrain(self.video_model, video_weights):
             for p in self.video_model.parameters():

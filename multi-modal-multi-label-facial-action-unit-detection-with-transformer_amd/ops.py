@@ -1218,6 +1218,82 @@ def avgpool_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return out
 
 
+# frozen ResNet stem (csrc/stem.hip) -------------------------------------------------------------------
+STEM_COUT = 64
+
+
+def stem_packed_k(Cin: int) -> int:
+    """row length of ``stem_pack_weight``'s image for ``Cin`` input channels (avf_stem_packed_k); raises unless Cin is 1, 3 or 4"""
+    kp = _lib.load().avf_stem_packed_k(int(Cin))
+    if kp <= 0:
+        _lib.check(1, "stem_packed_k")
+    return kp
+
+
+def stem_out_hw(H: int, W: int) -> Tuple[int, int]:
+    """(Hp, Wp) of conv 7x7 / 2 / pad 3 followed by maxpool 3x3 / 2 / pad 1"""
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+
+
+def stem_plan(N: int, Cin: int, H: int, W: int) -> dict:
+    """The tile of pooled outputs one workgroup of ``stem_nchw`` owns (avf_stem_plan): dict(tile_h, tile_w).  Raises on a
+    shape the kernel does not take."""
+    out = [C.c_int(-1) for _ in range(2)]
+    _lib.check(_lib.load().avf_stem_plan(int(N), int(Cin), int(H), int(W), *[C.byref(o) for o in out]), "stem_plan")
+    return dict(tile_h=out[0].value, tile_w=out[1].value)
+
+
+def stem_pack_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                     running_var: torch.Tensor, eps: float = 1e-5):
+    """nn.Conv2d weight [64, Cin, 7, 7] fp32 + BatchNorm2d's eval-mode statistics -> (w_packed [64, stem_packed_k(Cin)] bf16 in the
+    kernel's own order, scale [64], shift [64] fp32) for ``stem_nchw`` (avf_stem_pack_weight).  Cin in {1, 3, 4}."""
+    _need_cuda(w, gamma, beta, running_mean, running_var)
+    ts = [t.detach().contiguous() for t in (w, gamma, beta, running_mean, running_var)]
+    if not (all(t.dtype == torch.float32 for t in ts) and ts[0].dim() == 4 and tuple(ts[0].shape[2:]) == (7, 7)):
+        raise ValueError(f"stem_pack_weight: w must be a [Cout, Cin, 7, 7] fp32 tensor and the BatchNorm tensors fp32 (got {tuple(w.shape)})")
+    Cout, Cin = ts[0].shape[:2]
+    if not all(t.numel() == Cout for t in ts[1:]):
+        raise ValueError(f"stem_pack_weight: the BatchNorm tensors must have Cout = {Cout} elements")
+    lib = _lib.load()
+    kp = lib.avf_stem_packed_k(int(Cin))  # 0 for a Cin the kernel does not take: the pack call below names the limit
+    wp = torch.zeros((Cout, max(kp, 32)), dtype=torch.bfloat16, device=w.device)
+    scale = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    shift = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    _lib.check(lib.avf_stem_pack_weight(*[_ptr(t) for t in ts], float(eps), _ptr(wp), _ptr(scale), _ptr(shift), int(Cout), int(Cin),
+                                        _stream()), "stem_pack_weight")
+    return wp, scale, shift
+
+
+def stem_nchw(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, out: Optional[torch.Tensor] = None,
+              out_dtype=torch.bfloat16) -> torch.Tensor:
+    """maxpool3x3/2(relu(conv7x7/2(x, w) * scale + shift)) in one launch (avf_stem_nchw): x [N, Cin, H, W] contiguous planes, fp32
+    or bf16, Cin in {1, 3, 4}, any H, W >= 1; w_packed / scale / shift from ``stem_pack_weight``; -> out [N, Hp, Wp, 64] NHWC,
+    fp32 or bf16.  x may start at any element (a view into a larger buffer); out must be 16-byte aligned.  Forward only."""
+    _need_cuda(x, w_packed, scale, shift, out)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"stem_nchw: x must be a contiguous [N, Cin, H, W] tensor (got {tuple(x.shape)}, strides {x.stride()})")
+    N, Cin, H, W = x.shape
+    Hp, Wp = stem_out_hw(H, W)
+    if out is None:
+        out = torch.empty((N, Hp, Wp, STEM_COUT), dtype=torch_dtype(out_dtype), device=x.device)
+    if tuple(out.shape) != (N, Hp, Wp, STEM_COUT) or not out.is_contiguous():
+        raise ValueError(f"stem_nchw: out must be a contiguous {(N, Hp, Wp, STEM_COUT)} tensor (got {tuple(out.shape)}, strides {out.stride()})")
+    lib = _lib.load()
+    kp = lib.avf_stem_packed_k(int(Cin))
+    if kp > 0 and (tuple(w_packed.shape) != (STEM_COUT, kp) or not w_packed.is_contiguous()):
+        raise ValueError(f"stem_nchw: w_packed must be the contiguous {(STEM_COUT, kp)} image of stem_pack_weight for Cin = {Cin} "
+                         f"(got {tuple(w_packed.shape)})")
+    for name, t in (("scale", scale), ("shift", shift)):
+        if tuple(t.shape) != (STEM_COUT,) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"stem_nchw: {name} must be a contiguous fp32 [{STEM_COUT}] tensor")
+    if w_packed.dtype != torch.bfloat16:
+        raise ValueError("stem_nchw: w_packed must be bf16")
+    _lib.check(lib.avf_stem_nchw(_ptr(x), avf_dtype(x.dtype), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out), avf_dtype(out.dtype),
+                                 N, Cin, H, W, _stream()), "stem_nchw")
+    return out
+
+
 def dropout_factors(seed: int, layer: int, site: int, p: float, rows: int, cols: int, device="cuda") -> torch.Tensor:
     """keep/(1-p) factors of dropout site `site` of layer `layer` for a [rows, cols] activation (test aid)."""
     out = torch.empty((rows, cols), dtype=torch.float32, device=device)

@@ -14,7 +14,20 @@ result is the median of the groups.  Then every distinct conv shape of the stage
 achieved fraction of the bf16 MFMA peak (2.5 PFLOP/s dense) is reported, and the device operations of arm c from the stage-3
 tokens to the pooled features are counted with torch.profiler: next to the token section's own there must be the positional
 add, layer4's five conv launches and the pool, and no permute.  Writes <out-dir>/<name>.json (default
-profiles/ab/backbone_frozen.json) and prints the medians."""
+profiles/ab/backbone_frozen.json) and prints the medians.
+
+    python tools/bench_backbone.py --stem [--groups 7] [--calls 5] [--warmup 2]
+
+The stem in front of those stages (conv1 7x7 / 2 - bn1 - relu - maxpool 3x3 / 2), on [1024, 3, 112, 112] and [16, 3, 112, 112] video
+frames and the [64, 1, 64, 1001] mel maps of the audio stream, fp32 planes in, the NHWC bf16 map of layer1 out:
+  a        the torch stem (fp32, NCHW) plus backbone.to_nhwc: the path before csrc/stem.hip
+  b        the same ops on a bf16 channels_last copy (the conversion of x included; its output is the NHWC bf16 map already): the
+           vendor library's best case
+  c        ops.stem_nchw: one launch
+  whole    FrozenResFormer(backend="hip") with stem="torch" and with stem="hip" (the video shapes), FrozenAudioModel on both backends
+           (the mel shape)
+Same windows, alternation and medians.  Per shape the JSON also holds the bytes the stem must move (x in once, out once) and the
+rate arm c reaches on them.  Writes <out-dir>/backbone_stem.json."""
 import argparse
 import copy
 import json
@@ -34,11 +47,16 @@ def main():
     ap.add_argument("--groups", type=int, default=7)
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--name", default="backbone_frozen")
+    ap.add_argument("--stem", action="store_true", help="time the stem arms instead (profiles/ab/backbone_stem.json)")
+    ap.add_argument("--name", default=None)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "ab"))
     args = ap.parse_args()
     if args.groups < 5:
         ap.error("--groups must be at least 5 (the result is a median)")
+    if args.name is None:
+        args.name = "backbone_stem" if args.stem else "backbone_frozen"
+    if args.stem:
+        return stem_main(args)
     import torch
     from torch.nn import functional as F
     import avformer_amd as A
@@ -157,6 +175,105 @@ def main():
                           "device_ops": {k: r["tokens_to_features_device_ops"][k] for k in ("count", "of_the_token_section_alone", "permute_or_copy_kernels")}}))
         for s in r["conv_shapes"]:
             print(json.dumps(s))
+
+
+STEM_SHAPES = ((1024, 3, 112, 112), (16, 3, 112, 112), (64, 1, 64, 1001))
+
+
+def stem_main(args):
+    import torch
+    from torch.nn import functional as F
+    import avformer_amd as A
+    from tools.ab_bench import box_id
+    from tools.bench_mel import shader_clock
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_backbone.py measures on the GPU; no device found")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    video = A.FrozenResFormer(backend="hip").to(dev).eval()
+    audio = A.FrozenAudioModel(backend="torch").to(dev).eval()
+    for m in (video, audio):
+        for p in m.parameters():
+            p.requires_grad_(False)
+    video_fused = copy.deepcopy(video).set_backend("hip", stem="hip")
+    audio_hip = copy.deepcopy(audio).set_backend("hip")
+
+    def timed(arms):
+        for fn in arms.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        runs = {k: [] for k in arms}
+        for r in range(args.groups):
+            for name, fn in arms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.calls):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                runs[name].append(round(e0.elapsed_time(e1) / args.calls, 5))
+            print(f"group {r + 1}: " + "  ".join(f"{k} {v[-1]:.3f}" for k, v in runs.items()) + " ms", flush=True)
+        return runs
+
+    clock_before = shader_clock()
+    result = {}
+    with torch.no_grad():
+        for shape in STEM_SHAPES:
+            N, Cin, H, W = shape
+            x = torch.randn(*shape, device=dev)
+            net = video if Cin == 3 else audio.resnet          # conv1 / bn1 / maxpool of the module the shape belongs to
+            net_b = copy.deepcopy(torch.nn.ModuleDict({"conv1": net.conv1, "bn1": net.bn1}))
+            net_b.to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+            packed = net._stem_pack(dev)
+            Hp, Wp = A.ops.stem_out_hw(H, W)
+            out_c = torch.empty(N, Hp, Wp, 64, dtype=torch.bfloat16, device=dev)
+
+            def arm_a():
+                return A.backbone.to_nhwc(net.stem(x))
+
+            def arm_b():
+                xb = x.to(dtype=torch.bfloat16, memory_format=torch.channels_last)
+                return net.maxpool(F.relu(A.FrozenBasicBlock._bn(net_b["conv1"](xb), net_b["bn1"])))
+
+            def arm_c():
+                return A.ops.stem_nchw(x, *packed, out=out_c)
+
+            arms = {"a_stem": arm_a, "b_stem": arm_b, "c_stem": arm_c}
+            if Cin == 3:
+                arms.update({"whole_stem_torch": lambda: video(x), "whole_stem_hip": lambda: video_fused(x)})
+            else:
+                arms.update({"whole_torch": lambda: audio(x), "whole_hip": lambda: audio_hip(x)})
+            want = arm_a().float()
+            err = {"b_stem": float((arm_b().permute(0, 2, 3, 1).float() - want).norm() / want.norm()),
+                   "c_stem": float((arm_c().float() - want).norm() / want.norm())}
+            wholes = [k for k in arms if k.startswith("whole")]
+            ref = arms[wholes[0]]().float()
+            err[wholes[1] + "_vs_" + wholes[0]] = float((arms[wholes[1]]().float() - ref).norm() / ref.norm())
+            print(f"shape {shape}", flush=True)
+            runs = timed(arms)
+            med = {k: statistics.median(v) for k, v in runs.items()}
+            spread = {k: round(max(v) - min(v), 5) for k, v in runs.items()}
+            must_move = x.numel() * x.element_size() + out_c.numel() * out_c.element_size()
+            result["x".join(map(str, shape))] = {
+                "ms_per_call": runs, "median_ms_per_call": med, "spread_ms_max_minus_min": spread,
+                "c_over_a": round(med["c_stem"] / med["a_stem"], 4), "c_over_b": round(med["c_stem"] / med["b_stem"], 4),
+                "a_minus_c_ms": round(med["a_stem"] - med["c_stem"], 5),
+                "c_below_a_by_more_than_the_spread_of_a": bool(med["a_stem"] - med["c_stem"] > spread["a_stem"]),
+                "c_below_b": bool(med["c_stem"] < med["b_stem"]),
+                "whole_ratio_" + wholes[1] + "_over_" + wholes[0]: round(med[wholes[1]] / med[wholes[0]], 4),
+                "stem_bytes_x_in_once_out_once": must_move, "c_stem_gb_per_s": round(must_move / (med["c_stem"] * 1e-3) / 1e9, 1),
+                "stem_tile": A.ops.stem_plan(*shape), "rel_fro": err}
+            del x, out_c
+    out = {"name": args.name, "shapes": [list(s) for s in STEM_SHAPES], "box": box_id(), "clock_before": clock_before,
+           "clock_after": shader_clock(), "device": torch.cuda.get_device_name(0), "alternations": args.groups,
+           "calls_per_group": args.calls, "warmup_calls": args.warmup,
+           "launch": "eager, device events around the calls, inputs already on the device, torch.no_grad()", "stem": result}
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, args.name + ".json"), "w") as f:
+        json.dump(out, f, indent=1)
+    for k, r in result.items():
+        print(json.dumps({"shape": k, **{n: r[n] for n in r if n != "ms_per_call"}}))
 
 
 def stage_conv_shapes(model, Bp, H, W):
