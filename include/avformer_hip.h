@@ -278,6 +278,22 @@ int avf_attn_bwd(int dtype, const void* qkv, const void* o, const void* d_o, con
 int avf_attn_fwd_qs(const void* qkv, void* o, float* lse2, int batch, int tokens, int heads, int dim_head, void* stream);
 int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, void* workspace,
                     int batch, int tokens, int heads, int dim_head, void* stream);
+/* Which kernels the bf16 attention core launches for a shape - host code only, decided by the functions the launchers
+ * themselves switch on.  masked = 0: avf_attn_fwd / avf_attn_bwd on AVF_BF16 (q_prescaled = 0) and avf_attn_fwd_qs /
+ * avf_attn_bwd_qs (q_prescaled = 1); masked = 1: avf_attn_fwd_masked_qs / avf_attn_bwd_masked_qs and the layer.
+ *   *fwd: AVF_ATTN_RES8 | RES12 | RES_MULTI - the head-resident kernel with up to 8 / 12 waves in one pass, or 8 waves in
+ *         several; AVF_ATTN_STREAM - the streaming kernel; AVF_ATTN_F32 - the fp32-arithmetic kernel (masked = 1 only).
+ *   *bwd: the same values for the two head-resident kernels, delta + the two streaming kernels, the fp32-arithmetic ones;
+ *         or AVF_ATTN_MERGED + 2 * KB + ragged - the merged kernel with KB = 1 .. 4 key blocks per wave, ragged = 1 when
+ *         the last key block holds rows past `tokens` (always under a mask).
+ * The tuning switches of the library (AVF_TUNING=1) move the answers exactly as they move the launches. */
+#define AVF_ATTN_RES8 0
+#define AVF_ATTN_RES12 1
+#define AVF_ATTN_RES_MULTI 2
+#define AVF_ATTN_STREAM 3
+#define AVF_ATTN_F32 4
+#define AVF_ATTN_MERGED 8
+int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int masked, int* fwd, int* bwd);
 /* ... with the token mask of heads.py:225-232 (keep: device bytes [batch, tokens], 1 = kept - ANY pattern, token 0 and
  * whole clips included): the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8
  * stack - one internal helper picks the kernels for the layer and for these calls.  avf_attn_masked_on_mfma(tokens,

@@ -462,6 +462,13 @@ extern "C" int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, 
                        dim_head, (hipStream_t)stream, true, w + (size_t)batch * tokens * heads);
 }
 
+// which kernels those calls launch (masked = 0) and the masked ones below (masked = 1): host code only, answered by the
+// functions the launchers themselves switch on
+extern "C" int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int masked, int* fwd, int* bwd) {
+  AVF_REQUIRE(fwd && bwd, "attn_plan: null pointer");
+  return attn_bf16_plan(tokens, dim_head, q_prescaled != 0, masked != 0, fwd, bwd);
+}
+
 // ... with the token mask: the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8 stack
 // (attn_fwd_masked_bf16 / attn_bwd_masked_bf16 choose the kernels for both).  workspace: 2 * avf_attn_bwd_workspace_bytes.
 extern "C" int avf_attn_masked_on_mfma(int tokens, int dim_head) { return attn_masked_bf16_ok(tokens, dim_head, true) ? 1 : 0; }

@@ -17,6 +17,12 @@
 // dim_head 32 / 64: NW = 4 (32 rows per wave, two 16-row blocks).  dim_head 128: NW = 8 (16 rows per wave) - with two blocks
 // per wave the dK/dV kernel's accumulators alone take 128 registers and all three kernels spill at 256; with one they need
 // 150 / 162 / 238 VGPRs (forward / dQ / dK-dV), no scratch, one 512-thread workgroup per CU (73.7 KB static LDS each).
+// Rounding points (what tests/attn_bf16_util.py emulates; everything else - scores, running maximum, l, lse2, delta - is fp32):
+//   forward   the unnormalised P = exp2(s - m) is rounded to bf16 (round to nearest even: pack_pair) before O^T += V^T P^T;
+//             o = acc / l is rounded once.  The head-resident kernel takes l from the MFMA of a ones row with the ROUNDED P,
+//             the streaming kernel sums the unrounded P on the VALU.
+//   backward  P = exp2(s - lse2) in fp32; dS = P * (dP - delta) from that UNROUNDED P, rounded to bf16 before dQ and dK; P
+//             rounded to bf16 before dV; delta = fp32 sum of dO * o over the bf16 o it is given; dq, dk, dv rounded once.
 #include <type_traits>
 
 #include "attn_dispatch.hpp"
@@ -1397,13 +1403,25 @@ bool use_resident(int N, int dh) {
 
 // The head-resident variant for N tokens.  V = ceil(N/32) row groups: up to 8 take the 8-wave kernel and 9 .. 12 the 12-wave
 // one, a wave per row group in a single pass; more are spread over ceil(V/8) passes of the 8-wave multi-pass kernel.
+// -> ATTN_RES8 | ATTN_RES12 | ATTN_RES_MULTI, *W: waves per workgroup
+int res_variant(int N, int* W) {
+  const int V = (int)ceil_div(N, 32);
+  if (V > 12) {
+    *W = (int)ceil_div(V, ceil_div(V, 8));
+    return ATTN_RES_MULTI;
+  }
+  *W = V;
+  return V <= 8 ? ATTN_RES8 : ATTN_RES12;
+}
 // f(int_c<MAXW>{}, std::bool_constant<MULTI>{}, waves per workgroup)
 template <typename F>
 int with_res_variant(int N, F&& f) {
-  const int V = (int)ceil_div(N, 32);
-  if (V > 12) return f(int_c<8>{}, std::true_type{}, (int)ceil_div(V, ceil_div(V, 8)));
-  if (V <= 8) return f(int_c<8>{}, std::false_type{}, V);
-  return f(int_c<12>{}, std::false_type{}, V);
+  int W = 0;
+  switch (res_variant(N, &W)) {
+    case ATTN_RES_MULTI: return f(int_c<8>{}, std::true_type{}, W);
+    case ATTN_RES8: return f(int_c<8>{}, std::false_type{}, W);
+    default: return f(int_c<12>{}, std::false_type{}, W);
+  }
 }
 // ... as check_launch and the error messages name it behind the kernel's name: "<8,multi,qs,mask>"
 template <int MAXW, bool MULTI, bool QS, bool MASKED = false>
@@ -1448,6 +1466,40 @@ bool attn_masked_bf16_ok(int N, int dh, bool q_prescaled) {
   return on && q_prescaled && use_resident(N, dh) && N >= 1 && N <= 512;
 }
 
+// the kernel attn_fwd_bf16 launches (it switches on this value): a head-resident variant or the streaming kernel
+int attn_fwd_bf16_kind(int N, int dh) {
+  int W = 0;
+  return use_resident(N, dh) ? res_variant(N, &W) : ATTN_STREAM;
+}
+// ... and attn_bwd_bf16: the merged kernel (under a token mask always: its masked instantiation is a ragged one), the two
+// head-resident kernels, or delta + the two streaming kernels
+int attn_bwd_bf16_kind(int N, int dh, bool q_prescaled, bool masked, int* kb, bool* ragged) {
+  *kb = 0;
+  *ragged = false;
+  if (masked || attn_bwd_merged_ok(N, dh, q_prescaled)) {
+    *kb = attn_bwd_merged_kb(N, ragged);
+    if (masked) *ragged = true;
+    return ATTN_MERGED;
+  }
+  return attn_fwd_bf16_kind(N, dh);  // (the same split: use_resident and the row groups of N)
+}
+
+int attn_bf16_plan(int N, int dh, bool q_prescaled, bool masked, int* fwd, int* bwd) {
+  AVF_REQUIRE(N >= 1, "attn_plan: tokens %d", N);
+  if (masked && !attn_masked_bf16_ok(N, dh, q_prescaled)) {  // attn_fwd_masked_bf16 / attn_bwd_masked_bf16: attn_fwd_vec / attn_bwd_vec
+    AVF_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64 || dh == 128, "attn_plan: unsupported dim_head %d (8,16,32,64,128)", dh);
+    *fwd = *bwd = ATTN_F32;
+    return 0;
+  }
+  AVF_REQUIRE(dh == 32 || dh == 64 || dh == 128, "attn_plan: unsupported dim_head %d (32, 64 or 128)", dh);
+  int kb = 0;
+  bool ragged = false;
+  *fwd = attn_fwd_bf16_kind(N, dh);
+  *bwd = attn_bwd_bf16_kind(N, dh, q_prescaled, masked, &kb, &ragged);
+  if (*bwd == ATTN_MERGED) *bwd += 2 * kb + (ragged ? 1 : 0);
+  return 0;
+}
+
 int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled,
                   void* mx_q, void* mx_s, const void* keep) {
   AVF_REQUIRE(!keep || (attn_masked_bf16_ok(N, dh, q_prescaled) && !mx_q),
@@ -1461,7 +1513,7 @@ int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, in
   if (shape_log_on())
     shape_log("attn_fwd,attn_fwd,%d,%d,%d,%d,%d,%.0f,%.0f", B * H, B, N, H * dh, -1, 4.0 * B * H * (double)N * N * dh,
               2.0 * 4.0 * B * N * H * dh);
-  if (use_resident(N, dh)) {
+  if (attn_fwd_bf16_kind(N, dh) != ATTN_STREAM) {
     const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2 + (keep ? (size_t)((N + 63) & ~63) : 0);
     return with_res_variant(N, [&](auto mw, auto mu, int W) {
       auto launch = [&](auto q, auto masked, uint8_t* mq, uint8_t* ms) {
@@ -1507,9 +1559,12 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
   if (shape_log_on())
     shape_log("attn_bwd,%s,%d,%d,%d,%d,%d,%.0f,%.0f", attn_bwd_merged_ok(N, dh, q_prescaled) ? "attn_bwd_m4_kernel" : "attn_dq+attn_dkv",
               B * H, B, N, H * dh, -1, 10.0 * B * H * (double)N * N * dh, 2.0 * 8.0 * B * N * H * dh);
-  if (keep) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, keep);  // (the merged kernel at every N <= 512)
-  if (attn_bwd_merged_ok(N, dh, q_prescaled)) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, nullptr, dq_q, dq_s);
-  if (use_resident(N, dh)) {  // delta comes out of the dQ kernel
+  int kb = 0;
+  bool ragged = false;
+  const int kind = attn_bwd_bf16_kind(N, dh, q_prescaled, keep != nullptr, &kb, &ragged);
+  // (under a mask the merged kernel at every N <= 512; no fp8 image then: checked above)
+  if (kind == ATTN_MERGED) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, keep, dq_q, dq_s);
+  if (kind != ATTN_STREAM) {  // head-resident: delta comes out of the dQ kernel
     const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2, smem_kv = smem + (size_t)((N + 63) & ~63) * 8;
     AVF_REQUIRE(!q_prescaled || nlse, "attn_bwd_bf16: scratch for the negated statistics missing");
     return with_res_variant(N, [&](auto mw, auto mu, int W) {

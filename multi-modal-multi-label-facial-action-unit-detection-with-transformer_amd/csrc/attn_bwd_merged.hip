@@ -12,7 +12,8 @@
 //   sweeps the queries in SLICES of 32 rows (Q and dO slices arrive by LDS-DMA, one slice ahead, one barrier per slice).
 //   Per (slice, key block), key on the lane:
 //     A:  S  = Q K^T - lse2, dP = dO V^T - delta     (the row statistics ride in the C operand; q carries log2(e)/sqrt(dh))
-//     B:  P = exp2(S), dS = P * dP, packed to bf16   (48 VALU instructions per lane)
+//     B:  P = exp2(S), dS = P * dP, packed to bf16   (48 VALU instructions per lane; dS from the fp32 P, both rounded to
+//                                                     nearest even; S, lse2, dP and delta stay fp32)
 //     C:  dV^T += dO^T P,  dK^T += Q^T dS            (the accumulator tiles ARE the B operands)
 //         dS^T goes to a [key][query] image in LDS (8-byte stores of the accumulator rows).
 //   dQ of slice s is computed DURING slice s+1 from the dS^T images of all the key blocks (written by all four waves,
@@ -22,7 +23,7 @@
 //   (A first version summed four per-wave dQ partials: ds_add_f32 into one tile measured 600 cycles per instruction - 55 %
 //   of the kernel -, four fp32 slabs plus a summing pass still 15 %.)
 //   delta = rowsum(dO * O) of the NEXT slice is computed at the bottom of each slice from the dO rows already in LDS
-//   and an O chunk fetched at the top.
+//   and an O chunk fetched at the top (an fp32 sum over the bf16 o the kernel is given).  dq, dk, dv are rounded once, on store.
 // One wave per SIMD: nothing but the wave's own instruction order overlaps VALU and matrix pipe, so the slice body is
 // software-pipelined by hand (see the stages below) and fenced with sched_barrier.  Bitwise deterministic.
 //
@@ -744,6 +745,14 @@ bool attn_bwd_merged_ok(int N, int dh, bool q_prescaled) {
   return allow && q_prescaled && dh == 64 && N <= 512 && N >= min_n;
 }
 
+// key blocks of 32 keys per wave (four waves) for N tokens, and whether the last of them hold rows past N: the instantiation
+// attn_bwd_merged launches and avf_attn_plan reports
+int attn_bwd_merged_kb(int N, bool* ragged) {
+  const int KB = (((N + 31) >> 5) + 3) >> 2;
+  *ragged = N != 4 * KB * 32;
+  return KB;
+}
+
 int attn_bwd_merged(const TimingScope* ts, const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv,
                     int B, int N, int H, hipStream_t s, const void* keep, void* dq_q, void* dq_s) {
   AVF_REQUIRE(!dq_q || (dq_s && !keep && ((uintptr_t)dq_q & 3) == 0 && (3 * H * 64) % 32 == 0),
@@ -751,8 +760,8 @@ int attn_bwd_merged(const TimingScope* ts, const bf16* qkv, const bf16* o, const
   AVF_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)o & 15) == 0 && ((uintptr_t)d_o & 15) == 0 &&
                   ((uintptr_t)dqkv & 15) == 0,
               "attn_bwd_merged: misaligned pointers");
-  const int KB = (((N + 31) >> 5) + 3) >> 2;
-  const bool ragged = N != 4 * KB * 32;
+  bool ragged;
+  const int KB = attn_bwd_merged_kb(N, &ragged);
   return with_key_blocks(KB, N, [&](auto kb) {
     constexpr int K = decltype(kb)::value;
     // token mask: the masked instantiation (which treats padded keys as dropped ones)

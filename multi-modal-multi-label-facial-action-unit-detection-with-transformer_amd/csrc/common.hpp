@@ -687,6 +687,17 @@ bool attn_bwd_emits_mx8(int N, int dh, bool q_prescaled);
 int attn_delta(int dtype, const void* o, const void* d_o, float* delta, int B, int N, int H, int dh, hipStream_t s);
 // merged dQ + dK/dV kernel (attn_bwd_merged.hip): dim_head 64, pre-scaled q, N <= 512
 bool attn_bwd_merged_ok(int N, int dh, bool q_prescaled);
+int attn_bwd_merged_kb(int N, bool* ragged);  // key blocks per wave (1 .. 4) and whether the last ones hold rows past N
+// Which kernels the bf16 attention entry points launch (avf_attn_plan; the values of AVF_ATTN_* in avformer_hip.h).  attn_fwd_bf16
+// and attn_bwd_bf16 switch on attn_fwd_bf16_kind / attn_bwd_bf16_kind themselves, so a launch and the query cannot disagree.
+enum AttnKind {
+  ATTN_RES8 = AVF_ATTN_RES8, ATTN_RES12 = AVF_ATTN_RES12, ATTN_RES_MULTI = AVF_ATTN_RES_MULTI, ATTN_STREAM = AVF_ATTN_STREAM,
+  ATTN_F32 = AVF_ATTN_F32, ATTN_MERGED = AVF_ATTN_MERGED
+};
+int attn_fwd_bf16_kind(int N, int dh);
+int attn_bwd_bf16_kind(int N, int dh, bool q_prescaled, bool masked, int* kb, bool* ragged);  // kb / ragged: ATTN_MERGED only
+// unmasked: avf_attn_fwd[_qs] / avf_attn_bwd[_qs] on bf16; masked: attn_fwd_masked_bf16 / attn_bwd_masked_bf16 (the layer's choice)
+int attn_bf16_plan(int N, int dh, bool q_prescaled, bool masked, int* fwd, int* bwd);
 int attn_bwd_merged(const TimingScope* ts, const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv,
                     int B, int N, int H, hipStream_t s, const void* keep = nullptr, void* dq_q = nullptr, void* dq_s = nullptr);
 

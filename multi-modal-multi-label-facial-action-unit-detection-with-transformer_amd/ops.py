@@ -552,6 +552,24 @@ def attn_bwd(qkv, o, d_o, lse2, batch: int, tokens: int, heads: int, dim_head: i
     return dqkv
 
 
+ATTN_KINDS = {0: "res8", 1: "res12", 2: "res_multi", 3: "stream", 4: "f32"}  # AVF_ATTN_* of avformer_hip.h
+ATTN_MERGED = 8
+
+
+def attn_plan(tokens: int, dim_head: int, q_prescaled: bool = False, masked: bool = False) -> dict:
+    """Which kernels the bf16 attention core launches at this shape (avf_attn_plan, pure host code): attn_fwd / attn_bwd with
+    this ``q_prescaled``, or with ``masked`` attn_fwd_masked / attn_bwd_masked(q_prescaled=True) and the layer itself.
+    dict(fwd = "res8" | "res12" | "res_multi" (head-resident) | "stream" | "f32" (fp32 arithmetic), bwd = the same names or
+    "merged", kb = key blocks per wave of the merged kernel (else 0), ragged = its last key block holds rows past tokens)."""
+    fwd, bwd = C.c_int(-1), C.c_int(-1)
+    _lib.check(_lib.load().avf_attn_plan(int(tokens), int(dim_head), int(bool(q_prescaled)), int(bool(masked)), C.byref(fwd),
+                                         C.byref(bwd)), "attn_plan")
+    if bwd.value >= ATTN_MERGED:
+        code = bwd.value - ATTN_MERGED
+        return dict(fwd=ATTN_KINDS[fwd.value], bwd="merged", kb=code // 2, ragged=bool(code & 1))
+    return dict(fwd=ATTN_KINDS[fwd.value], bwd=ATTN_KINDS[bwd.value], kb=0, ragged=False)
+
+
 def attn_masked_on_mfma(tokens: int, dim_head: int) -> bool:
     """does the masked attention of a bf16 stack (attn_fwd_masked / attn_bwd_masked with q_prescaled=True, and the layer itself)
     run the masked MFMA kernels at this shape (avf_attn_masked_on_mfma), not the fp32-arithmetic ones"""

@@ -6,7 +6,9 @@ mask>; everything else: the fp32-arithmetic kernels of attn_f32.hip on bf16 stor
 carries the named keep pattern, clip 1 a random one with token 0 dropped.  Errors are taken per ROW GROUP (kept tokens, dropped
 tokens; all clips and clip 0 alone): a dropped query's output row is the mean of v and its norm about 1/sqrt(N) of a kept
 row's, so a whole-tensor error cannot see it.  Caps: mask_attn_util (the project's own figures for these kernels; none comes
-from what the kernels produce); tests/test_mask_attn_ref_cpu.py shows that bf16 rounding alone takes under a fifth of each."""
+from what the kernels produce); tests/test_mask_attn_ref_cpu.py shows that bf16 rounding alone takes under a fifth of each.
+The unmasked instantiations of the same kernels: tests/test_gpu_attn_bf16.py (16 x 16 groups against an emulation of the
+rounding points, the backward on reference-made inputs)."""
 import functools
 import math
 

@@ -295,7 +295,9 @@ def test_attention_emits_the_image_of_its_output(ops, B, N, H):
 @pytest.mark.parametrize("B,N,H", [(2, 324, 8), (1, 512, 4), (2, 300, 1), (2, 385, 2)])
 def test_attention_backward_emits_the_image_of_dqkv(ops, B, N, H):
     """round 3: the merged backward kernel writes the MX-FP8 image of dqkv (the A operand of dqkv -> dh1 in the fp8 mode):
-    dqkv itself is bit-equal to the plain call, the image is that of the stored bf16 tensor"""
+    dqkv itself is bit-equal to the plain call, the image is that of the stored bf16 tensor
+    (KB 3 and 4 here; tests/test_gpu_attn_bf16.py::test_backward_merged_mx8_form adds KB 1 and 2, ragged and full, and holds
+    dqkv to the fp64 reference)"""
     import math
     g = torch.Generator().manual_seed(B * 7 + N + H)
     qkv = torch.randn(B * N, 3 * H * 64, generator=g)

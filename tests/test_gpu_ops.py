@@ -409,6 +409,8 @@ def test_attention_f32(ops, f32_arith, B, N, H, dh):
 @pytest.mark.parametrize("B,N,H,dh", [(1, 64, 2, 32), (2, 49, 8, 32), (3, 17, 8, 64), (2, 130, 3, 64), (1, 324, 2, 64),
                                       (2, 12, 8, 32), (1, 512, 2, 64), (1, 200, 1, 32)])
 def test_attention_bf16(ops, B, N, H, dh, qs):
+    """whole-tensor norms, the backward on the device's own o and lse2 (tests/test_gpu_attn_bf16.py holds the same kernels
+    group-wise to an fp64 reference, the backward on reference-made inputs, and asserts which kernel each case runs)"""
     g = torch.Generator().manual_seed(B * 100 + N + dh + 1)
     qkv = torch.randn(B * N, 3 * H * dh, generator=g).to(torch.bfloat16)
     d_o = torch.randn(B * N, H * dh, generator=g).to(torch.bfloat16)
@@ -431,7 +433,8 @@ def test_attention_bf16(ops, B, N, H, dh, qs):
 @pytest.mark.parametrize("qs", [False, True], ids=["raw_q", "prescaled_q"])
 def test_attention_bf16_dh64_lengths(ops, N, qs):
     """dim_head 64 over the sequence lengths where the kernel family changes: one group per wave (N <= 384, 8- and
-    12-wave builds), several groups per wave (385..576), the streaming kernels (> 576); tails of 1..63 rows."""
+    12-wave builds), several groups per wave (385..576), the streaming kernels (> 576); tails of 1..63 rows.
+    (Whole-tensor norms; group-wise and with the kernel of every length asserted: tests/test_gpu_attn_bf16.py.)"""
     B, H, dh = 2, 2, 64
     g = torch.Generator().manual_seed(1000 + N)
     qkv = torch.randn(B * N, 3 * H * dh, generator=g).to(torch.bfloat16)
@@ -460,7 +463,9 @@ def test_attention_bf16_dh64_lengths(ops, N, qs):
 def test_attention_bf16_rescale_paths(ops, mode, qs):
     """lazy rescaling of the head-resident forward: 'ramp' = the row maximum grows by much more than the threshold in
     every key tile (rescale each tile); 'small_steps' = it grows by less than the threshold per tile (stale maximum,
-    probabilities above 1 in the accumulators); 'huge' = scores of magnitude ~1e3 (log2 domain ~1.4e3)."""
+    probabilities above 1 in the accumulators); 'huge' = scores of magnitude ~1e3 (log2 domain ~1.4e3).
+    (tests/test_gpu_attn_bf16.py::test_score_regimes holds the regimes but 'huge' group-wise to the worst case of three bf16
+    roundings; 'huge' stays here: its fp32 score error is not small against that bound.)"""
     B, N, H, dh = 1, 324, 1, 64
     g = torch.Generator().manual_seed(11)
     q = torch.randn(N, dh, generator=g)
