@@ -610,6 +610,23 @@ int avf_clip_gather_autoaugment_normalize(const uint8_t* bank, const int32_t* vi
                                           int C, const int32_t* plan, int k, const float* lut, const uint8_t* flip, void* dst,
                                           int out_dtype, int layout, void* stream);
 
+/* ---- TFormer's tokens from a resident bank of per-frame S-Former features (vformer.py:232-293) ----------------------------------
+ * The frozen S-Former runs per frame, in eval mode: a frame's features do not depend on the clip it sits in.  feat fp32 [F, D]
+ * (rows ldf floats apart) holds them once per frame, black [D] is the feature row of a black frame, and video_db_nr, present
+ * (nullable) and index are exactly what avf_clip_gather takes: all DEVICE pointers, read by the kernel at run time.  The rule is
+ * the one above, applied to feature rows: slot t of sample b is frame a = index[b] - d * (T - 1 - t), and its row is black where
+ * a < 0 or a >= F, where video_db_nr[a] != video_db_nr[index[b]], where present[a] == 0, or where index[b] is outside [0, F) -
+ * then the whole sample is black and nothing of feat, video_db_nr or present is read for it; in every other case it is feat[a].
+ *   out[b, j, :]          = lead[j, :] + pos[j, :]                 j < n_lead   (lead [n_lead, D]; null iff n_lead == 0)
+ *   out[b, n_lead + t, :] = row(b, t)  + pos[n_lead + t, :]        t < T        (pos [n_lead + T, D] or null: no add)
+ * out fp32 [B, n_lead + T, D], contiguous, must not overlap feat.  At most one fp32 add per element: bit for bit what
+ * avf_assemble_tokens gives on the rows gathered first.  D % 4 == 0 and ldf % 4 == 0, ldf >= D; feat, black, lead, pos and out
+ * 16-byte aligned.  ONE launch; sizes and indices are 64-bit; nothing is allocated or synchronised (capturable); every argument
+ * is checked before anything is enqueued, and an error names the argument. */
+int avf_feature_clip_tokens(const float* feat, int64_t ldf, const float* black, const int32_t* video_db_nr, const uint8_t* present,
+                            const int64_t* index, int64_t F, int64_t B, int64_t T, int64_t d, int D, const float* lead, int n_lead,
+                            const float* pos, float* out, void* stream);
+
 /* ---- one transformer layer (heads.py:246-255), forward and backward ------------------------ */
 size_t avf_layer_saved_bytes(const avf_layer_cfg* cfg);     /* activations kept for backward        */
 size_t avf_layer_lowp_bytes(const avf_layer_cfg* cfg);      /* bf16 weight copies (+transposes)     */

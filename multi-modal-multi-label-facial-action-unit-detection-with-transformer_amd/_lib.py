@@ -146,6 +146,7 @@ SIGNATURES = {
     "avf_clip_gather_autoaugment": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "avf_clip_gather_autoaugment_normalize": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp,
                                                      _vp, _int, _int, _vp]),
+    "avf_feature_clip_tokens": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp]),
     "avf_conv_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _int, _vp]),
     "avf_conv2d_nhwc": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "avf_conv_plan": (_int, [_int, _int, _int, _int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

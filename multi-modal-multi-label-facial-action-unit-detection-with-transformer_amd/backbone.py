@@ -345,3 +345,51 @@ class FrozenVideoModel(nn.Module):
     def forward(self, x):
         x = x[:, -self.num_channels:].permute(0, 2, 1, 3, 4)
         return self.t_former(self.s_former(x))
+
+    # ---- whole-video inference: the S-Former once per frame, the clips from its features (frames.FeatureBank) -------------------
+    @torch.no_grad()
+    def frame_features(self, frame_bank, front_end, chunk: int = 256):
+        """``frames.FrameBank`` -> ``frames.FeatureBank``: every frame of the bank once through ``front_end`` (no mirror) and
+        ``s_former``, ``chunk`` frames at a time as one-frame clips [n, 1, C, H, W], into ``features`` fp32 [F, 512].  ``s_former``
+        is frozen and applied per frame (vformer.py:232-268), so these are the rows ``forward`` computes for every clip a frame
+        sits in.  ``black`` is ``s_former`` of one all-zero uint8 frame through the same ``front_end``: black is a byte value and
+        is normalised like any other.  ``video_db_nr`` and ``present`` are carried over; a frame with ``present == 0`` may hold
+        anything, the rule never reads its row.  ``front_end``: a ``ClipFrontEnd(layout="tchw", channels=num_channels)``."""
+        from .clip import ClipFrontEnd
+        from .frames import FeatureBank, FrameBank
+        if not isinstance(frame_bank, FrameBank):
+            raise ValueError(f"frame_bank must be a FrameBank, got {type(frame_bank).__name__}")
+        if not isinstance(front_end, ClipFrontEnd):
+            raise ValueError(f"front_end must be a ClipFrontEnd, got {type(front_end).__name__}")
+        if front_end.layout != "tchw":
+            raise ValueError(f"front_end must write layout='tchw' ([n, 1, C, H, W], what s_former views as frames), got {front_end.layout!r}")
+        if front_end.channels != self.num_channels:
+            raise ValueError(f"front_end keeps {front_end.channels} channels, the model takes the last {self.num_channels}")
+        if frame_bank.frame_shape[-1] != front_end.in_channels:
+            raise ValueError(f"the bank has {frame_bank.frame_shape[-1]} channels, front_end's mean / std have {front_end.in_channels}")
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f"chunk must be an integer of at least 1, got {chunk!r}")
+        frames, F = frame_bank.frames, len(frame_bank)
+        black = self.s_former(front_end(torch.zeros((1, 1) + frame_bank.frame_shape, dtype=torch.uint8, device=frames.device)))
+        features = torch.empty((F, black.shape[1]), dtype=torch.float32, device=frames.device)
+        for i in range(0, F, chunk):
+            features[i:i + chunk] = self.s_former(front_end(frames[i:i + chunk].unsqueeze(1)))
+        return FeatureBank(features, black[0].float().contiguous(), frame_bank.video_db_nr, frame_bank.present)
+
+    def forward_bank(self, feature_bank, index, assembler):
+        """``forward`` on the clips of ``index`` int64 [B], from the features of their frames: the tokens
+        ``cat(cls_token, rows) + pos_embedding`` straight from the bank (``frames.FeatureClipAssembler``), then ``t_former``'s
+        stack -> [B, 512]"""
+        from .frames import FeatureBank, FeatureClipAssembler
+        if not isinstance(feature_bank, FeatureBank):
+            raise ValueError(f"feature_bank must be a FeatureBank, got {type(feature_bank).__name__}")
+        if not isinstance(assembler, FeatureClipAssembler):
+            raise ValueError(f"assembler must be a FeatureClipAssembler, got {type(assembler).__name__}")
+        t = self.t_former
+        if assembler.clip_len != t.num_patches:
+            raise ValueError(f"the assembler builds clips of {assembler.clip_len} frames, t_former takes {t.num_patches}")
+        if feature_bank.dim != t.dim:
+            raise ValueError(f"the bank's features are {feature_bank.dim} wide, t_former takes {t.dim}")
+        if not feature_bank.features.is_cuda:
+            raise RuntimeError("FrozenVideoModel.forward_bank needs its bank on the MI355X; there is no CPU fallback")
+        return t.forward_tokens(assembler.tokens(feature_bank, index, t.cls_token, t.pos_embedding))

@@ -20,6 +20,12 @@ all-black clip - this project's definition: the reference would raise, nothing o
 ``backend="torch"`` (default) is ATen ops on any device: the table of source frames, ``index_select``, ``where``, then the
 existing modules.  ``backend="hip"`` is one launch of csrc/clip_bank.hip per method.  Both give the same bytes and bits.
 
+What holds for bytes over the host link holds for S-Former FLOPs.  The video stream applies ``s_former`` per frame
+(vformer.py:232-268 flattens [b, t] into the batch) and, frozen, in eval mode: a frame's 512 features do not depend on the clip it
+sits in.  ``FeatureBank`` keeps them once per frame (2 KB against 37.6 KB of pixels), with the features of a black frame beside
+them, and ``FeatureClipAssembler`` builds the [B, T + 1, 512] token tensor that ``t_former``'s stack consumes (vformer.py:279-287)
+by the same rule, applied to feature rows: one launch of csrc/feature_bank.hip with ``backend="hip"``.
+
 Parity: unpinned by a reference fixture (the data set class needs lmdb and cv2, which are not importable here); checked bytewise
 against an independent numpy restatement of the cited lines (tests/frames_util.py).
 """
@@ -78,6 +84,20 @@ class FrameBank:
         return FrameBank(self.frames.to(device), self.video_db_nr.to(device), None if self.present is None else self.present.to(device))
 
 
+def _source_table(video_db_nr: torch.Tensor, present: Optional[torch.Tensor], index: torch.Tensor, T: int, d: int) -> torch.Tensor:
+    """int64 [B, T]: the bank entry of every slot of the clips of ``index``, -1 for a black one - the rule of the module docstring,
+    the one copy of it in torch ops (``ClipAssembler`` applies it to frames, ``FeatureClipAssembler`` to feature rows)."""
+    F = video_db_nr.shape[0]
+    label_ok = (index >= 0) & (index < F)
+    a = index[:, None] - d * (T - 1 - torch.arange(T, device=index.device))[None, :]          # aff2compdataset.py:126-127
+    inside = (a >= 0) & (a < F) & label_ok[:, None]
+    a_safe, label_safe = torch.where(inside, a, torch.zeros_like(a)), torch.where(label_ok, index, torch.zeros_like(index))
+    ok = inside & (video_db_nr[a_safe] == video_db_nr[label_safe][:, None])                    # :129
+    if present is not None:
+        ok = ok & (present[a_safe] != 0)                                                       # :142-155
+    return torch.where(ok, a, torch.full_like(a, -1))
+
+
 class ClipAssembler(nn.Module):
     """The clips of ``index`` int64 [B] out of a ``FrameBank``, ``clip_len`` frames each, ``dilation`` frames apart, ending at the
     labelled frame ``index[b]`` (the module docstring states the rule).
@@ -118,15 +138,7 @@ class ClipAssembler(nn.Module):
 
     def source_table(self, bank: FrameBank, index: torch.Tensor) -> torch.Tensor:
         self._check(bank, index, table_only=True)
-        F, T, d = len(bank), self.clip_len, self.dilation
-        label_ok = (index >= 0) & (index < F)
-        a = index[:, None] - d * (T - 1 - torch.arange(T, device=index.device))[None, :]          # aff2compdataset.py:126-127
-        inside = (a >= 0) & (a < F) & label_ok[:, None]
-        a_safe, label_safe = torch.where(inside, a, torch.zeros_like(a)), torch.where(label_ok, index, torch.zeros_like(index))
-        ok = inside & (bank.video_db_nr[a_safe] == bank.video_db_nr[label_safe][:, None])          # :129
-        if bank.present is not None:
-            ok = ok & (bank.present[a_safe] != 0)                                                  # :142-155
-        return torch.where(ok, a, torch.full_like(a, -1))
+        return _source_table(bank.video_db_nr, bank.present, index, self.clip_len, self.dilation)
 
     def _gather(self, bank: FrameBank, index: torch.Tensor) -> torch.Tensor:
         table = self.source_table(bank, index)
@@ -218,3 +230,122 @@ class ClipAssembler(nn.Module):
             return ops.clip_gather_autoaugment_normalize(bank.frames, bank.video_db_nr, bank.present, index.contiguous(), self.clip_len,
                                                          self.dilation, plan.contiguous(), front_end.lut, front_end.channels, flip,
                                                          front_end.layout, front_end.out_dtype)
+
+
+class FeatureBank:
+    """The per-frame features of a data set split on one device: ``features`` fp32 [F, D] (D a multiple of 4), ``black`` fp32 [D]
+    (the features of a black frame: black is a byte value, normalised and run through the S-Former like any other frame),
+    ``video_db_nr`` int32 [F] and ``present`` bool / uint8 [F] or None as ``FrameBank`` takes them.  All contiguous, all on the
+    device of ``features``.  The row of a frame with ``present == 0`` may hold anything: the rule never reads it."""
+
+    def __init__(self, features: torch.Tensor, black: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor] = None):
+        if not torch.is_tensor(features) or features.dtype != torch.float32 or features.dim() != 2:
+            raise ValueError("features must be a float32 tensor [F, D]")
+        F, D = features.shape
+        if F < 1 or D < 4 or D % 4:
+            raise ValueError(f"the bank needs at least one frame and a width that is a positive multiple of 4, got {tuple(features.shape)}")
+        if not torch.is_tensor(black) or black.dtype != torch.float32 or tuple(black.shape) != (D,):
+            raise ValueError(f"black must be a float32 tensor [{D}]")
+        if not torch.is_tensor(video_db_nr) or video_db_nr.dtype != torch.int32 or tuple(video_db_nr.shape) != (F,):
+            raise ValueError(f"video_db_nr must be an int32 tensor [{F}]")
+        if present is not None and (not torch.is_tensor(present) or present.dtype not in (torch.bool, torch.uint8)
+                                    or tuple(present.shape) != (F,)):
+            raise ValueError(f"present must be None or a bool / uint8 tensor [{F}]")
+        for name, t in (("black", black), ("video_db_nr", video_db_nr), ("present", present)):
+            if t is not None and t.device != features.device:
+                raise ValueError(f"{name} is on {t.device}, the features on {features.device}")
+        for name, t in (("features", features), ("black", black), ("video_db_nr", video_db_nr), ("present", present)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        self.features, self.black, self.video_db_nr, self.present = features, black, video_db_nr, present
+
+    def __len__(self) -> int:
+        return self.features.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.features.device
+
+    @property
+    def dim(self) -> int:
+        return self.features.shape[1]
+
+    def to(self, device) -> "FeatureBank":
+        return FeatureBank(self.features.to(device), self.black.to(device), self.video_db_nr.to(device),
+                           None if self.present is None else self.present.to(device))
+
+
+class FeatureClipAssembler(nn.Module):
+    """The token tensor of ``index`` int64 [B] out of a ``FeatureBank``: ``clip_len`` feature rows per sample, ``dilation`` frames
+    apart, ending at the labelled frame ``index[b]`` (the module docstring states the rule; a black slot is ``bank.black``).
+
+    ``source_table(bank, index)`` -> int64 [B, T]: the bank row of every slot, -1 for a black one.  Plain torch, any device.
+    ``tokens(bank, index, lead=None, pos=None)`` -> fp32 [B, n_lead + T, D]: ``cat(lead, rows) + pos[:n_lead + T]``, what
+    ``TFormer.forward`` builds in front of its stack (vformer.py:279-287).  ``lead`` is [n_lead, D] or the parameter shape
+    [1, n_lead, D] (TFormer's ``cls_token`` [1, 1, D]), ``pos`` is [P, D] or [1, P, D] with P >= n_lead + T; None leaves the
+    part out.  Each element is at most one fp32 add.
+
+    ``backend="torch"`` (default) is the definition, on any device: the table of source rows, ``index_select``, ``where`` against
+    ``black``, ``cat`` with ``lead``, ``+ pos``.  ``backend="hip"``: one launch of csrc/feature_bank.hip, the bank must be on the
+    GPU (no CPU fallback), under ``no_grad``; ``index`` is read on the device.  Both give the same bits."""
+
+    def __init__(self, clip_len: int = 16, dilation: int = 3, backend: str = "torch"):
+        super().__init__()
+        if backend not in BACKENDS:
+            raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
+        for name, v in (("clip_len", clip_len), ("dilation", dilation)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer of at least 1, got {v!r}")
+        self.clip_len, self.dilation, self.backend = clip_len, dilation, backend
+
+    def _check(self, bank: FeatureBank, index: torch.Tensor, table_only: bool = False) -> None:
+        if not isinstance(bank, FeatureBank):
+            raise ValueError(f"bank must be a FeatureBank, got {type(bank).__name__}")
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+            raise ValueError("index must be an int64 tensor [B] with B >= 1")
+        if index.device != bank.device:
+            raise ValueError(f"index is on {index.device}, the bank on {bank.device}")
+        if self.backend == "hip" and not table_only and not bank.features.is_cuda:
+            raise RuntimeError("FeatureClipAssembler (HIP) needs its bank on the MI355X; there is no CPU fallback - "
+                               "use backend='torch' on the host")
+
+    def source_table(self, bank: FeatureBank, index: torch.Tensor) -> torch.Tensor:
+        self._check(bank, index, table_only=True)
+        return _source_table(bank.video_db_nr, bank.present, index, self.clip_len, self.dilation)
+
+    def _rows2d(self, name: str, t: Optional[torch.Tensor], bank: FeatureBank, at_least: int) -> Optional[torch.Tensor]:
+        """``lead`` / ``pos`` as [rows, D]: [rows, D] itself or the parameter shape [1, rows, D]"""
+        if t is None:
+            return None
+        D = bank.dim
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in (2, 3) or t.shape[-1] != D or \
+                (t.dim() == 3 and t.shape[0] != 1):
+            raise ValueError(f"{name} must be a float32 tensor [rows, {D}] or [1, rows, {D}]")
+        if t.device != bank.device:
+            raise ValueError(f"{name} is on {t.device}, the bank on {bank.device}")
+        t = t.detach().reshape(-1, D)
+        if t.shape[0] < at_least:
+            raise ValueError(f"{name} has {t.shape[0]} rows, the tokens need {at_least}")
+        return t
+
+    def tokens(self, bank: FeatureBank, index: torch.Tensor, lead: Optional[torch.Tensor] = None,
+               pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check(bank, index)
+        T = self.clip_len
+        lead = self._rows2d("lead", lead, bank, 1)
+        n_lead = 0 if lead is None else lead.shape[0]
+        pos = self._rows2d("pos", pos, bank, n_lead + T)
+        if pos is not None:
+            pos = pos[:n_lead + T]
+        if self.backend == "hip":
+            with torch.no_grad():
+                return ops.feature_clip_tokens(bank.features, bank.black, bank.video_db_nr, bank.present, index.contiguous(), T,
+                                               self.dilation, None if lead is None else lead.contiguous(),
+                                               None if pos is None else pos.contiguous())
+        table = _source_table(bank.video_db_nr, bank.present, index, T, self.dilation)
+        B = table.shape[0]
+        rows = bank.features.index_select(0, table.clamp(min=0).view(-1)).view(B, T, bank.dim)
+        x = torch.where((table < 0).view(B, T, 1), bank.black, rows)
+        if lead is not None:
+            x = torch.cat([lead.expand(B, n_lead, bank.dim), x], dim=1)
+        return x + pos if pos is not None else x

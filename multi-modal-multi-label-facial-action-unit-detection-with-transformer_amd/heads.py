@@ -327,6 +327,14 @@ class TFormer(nn.Module):
         x = self.spatial_transformer(x)
         return x[:, 0]
 
+    def forward_tokens(self, tokens):
+        """the stack and the cls row on an already assembled ``cat(cls_token, x) + pos_embedding`` [B, num_patches + 1, dim]
+        (``frames.FeatureClipAssembler.tokens`` builds it from a feature bank)"""
+        _need_gpu(tokens, "TFormer")
+        if tokens.dim() != 3 or tuple(tokens.shape[1:]) != (self.num_patches + 1, self.dim):
+            raise ValueError(f"tokens must be [B, {self.num_patches + 1}, {self.dim}], got {tuple(tokens.shape)}")
+        return self.spatial_transformer(tokens)[:, 0]
+
 
 class ResFormerTokens(nn.Module):
     """The transformer section in the middle of the reference's ``ResFormer`` (S-Former after ResNet stage 3): the

@@ -77,6 +77,13 @@ class VisualFormer(nn.Module):
     def forward(self, x):
         return self.au_head.tokens(self.video_model(x))  # avformer.py:99
 
+    def forward_bank(self, feature_bank, index, assembler):
+        """``forward`` on the clips of ``index``, from a bank of per-frame S-Former features (``FrozenVideoModel.forward_bank``)"""
+        if not hasattr(self.video_model, "forward_bank"):
+            raise RuntimeError("VisualFormer.forward_bank needs the frozen video model: backbone='resnet18_frozen' or "
+                               f"'resnet18_frozen_fused' (got {type(self.video_model).__name__})")
+        return self.au_head.tokens(self.video_model.forward_bank(feature_bank, index, assembler))
+
 
 # the criteria each task model of the reference owns (loss_EX, loss_AU, VA weights): avformer.py:89-91 and 122, sformer.py:359-363
 # and 420, vformer.py:375-379 and 404, tformer.py:423-427 and 454
@@ -180,7 +187,20 @@ class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
         self.concurrent_streams = True
         self._side_streams = {}
 
+    def _forward_bank(self, x):
+        """``x['clip_bank'] = (feature_bank, index, assembler)`` in place of ``x['clip']``: the video branch from a bank of per-frame
+        S-Former features (whole-video inference, predict.py); one stream"""
+        audio_tok = self.audio_model(x['audio_features'])
+        video_tok = self.video_model.forward_bank(*x['clip_bank'])
+        if self.task == 'AU':
+            return self.au_head.forward_fused(audio_tok, video_tok, pad_to=21)
+        return torch.zeros(audio_tok.shape[0], 21, device=audio_tok.device, dtype=torch.float32)
+
     def forward(self, x):
+        if 'clip_bank' in x:
+            if 'clip' in x:
+                raise ValueError("x holds both 'clip' and 'clip_bank': the video branch takes one of them")
+            return self._forward_bank(x)
         a_in, v_in = x['audio_features'], x['clip']
         if self.concurrent_streams and a_in.is_cuda and torch.cuda.is_current_stream_capturing():
             # the two streams of the model are independent up to the fusion: while a hipGraph is being captured the aural

@@ -1126,6 +1126,36 @@ def clip_gather_autoaugment_normalize(bank: torch.Tensor, video_db_nr: torch.Ten
     return out
 
 
+def feature_clip_tokens(feat: torch.Tensor, black: torch.Tensor, video_db_nr: torch.Tensor, present: Optional[torch.Tensor],
+                        index: torch.Tensor, T: int, d: int, lead: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """avf_feature_clip_tokens, one launch: feat fp32 [F, D] (unit column stride, any row stride that is a multiple of 4) ->
+    fp32 [B, n_lead + T, D] = cat(lead [n_lead, D], the rows of the clips of index int64 [B]) + pos [n_lead + T, D].  Slot t of
+    sample b is row index[b] - d * (T - 1 - t), ``black`` [D] outside the bank, in another video (video_db_nr int32 [F]) or where
+    present (uint8 / bool [F] or None) is 0.  Everything is read on the device (no host synchronisation)."""
+    _need_cuda(feat, black, video_db_nr, present, index, lead, pos, out)
+    assert feat.dim() == 2 and feat.dtype == torch.float32 and feat.stride(1) == 1
+    F, D = feat.shape
+    assert black.dtype == torch.float32 and tuple(black.shape) == (D,) and black.is_contiguous()
+    assert video_db_nr.dtype == torch.int32 and video_db_nr.is_contiguous() and tuple(video_db_nr.shape) == (F,)
+    if present is not None:
+        assert present.dtype in (torch.bool, torch.uint8) and present.is_contiguous() and tuple(present.shape) == (F,)
+    assert index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1 and index.numel() >= 1
+    B, T = index.numel(), int(T)
+    n_lead = 0 if lead is None else lead.shape[0]
+    assert lead is None or (lead.dtype == torch.float32 and lead.is_contiguous() and tuple(lead.shape) == (n_lead, D))
+    assert pos is None or (pos.dtype == torch.float32 and pos.is_contiguous() and tuple(pos.shape) == (n_lead + T, D))
+    for t in (black, video_db_nr, present, index, lead, pos, out):
+        assert t is None or t.device == feat.device
+    if out is None:
+        out = torch.empty((B, n_lead + T, D), dtype=torch.float32, device=feat.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, n_lead + T, D)
+    _lib.check(_lib.load().avf_feature_clip_tokens(_ptr(feat), feat.stride(0), _ptr(black), _ptr(video_db_nr), _ptr(present),
+                                                   _ptr(index), F, B, T, int(d), D, _ptr(lead), n_lead, _ptr(pos), _ptr(out),
+                                                   _stream()), "feature_clip_tokens")
+    return out
+
+
 def fuse_tokens(clip: torch.Tensor, audio: torch.Tensor, pos: Optional[torch.Tensor], out_bf16: bool = False) -> torch.Tensor:
     """[B,Tv,D] ++ [B,Ta,D] on the token axis, + pos[Tv+Ta, D] (nullable): one pass (avf_fuse_tokens); out_bf16: the
     result is written in bf16 (the storage type of a bf16 residual stream, avf_fuse_tokens_bf16)."""
