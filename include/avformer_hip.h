@@ -214,10 +214,21 @@ int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, 
  * C_i[M_i,N_i] (fp32, dense) = A_i[K,M_i]^T * B_i[K,N_i] (bf16, token-major, dense: lda = M_i, ldb = N_i) that share the
  * reduction length K (the B*N token rows); K % 64 == 0, M_i % 8 == 0, N_i % 8 == 0.  Split-K partial slabs live in
  * `workspace` (avf_gemm_tn_group_workspace_bytes) and are folded by a second launch; a group whose tiles fill the chip
- * unsplit needs no workspace (0 bytes) and stores straight to C_i. */
+ * unsplit needs no workspace (0 bytes) and stores straight to C_i.
+ * avf_gemm_tn_group_plan: what that launch decides, by the function the launcher itself acts on (host code only; the
+ * tuning switches AVF_TN_BIG / AVF_TN_WAVES / AVF_TN_XCD / AVF_TN_SPLITS count exactly as in the launch).  out[0] = 1 for the
+ * 256 x 128 tile, 0 for the 128 x 128 one; out[1] = wavefronts per workgroup (4 or 8); out[2] = output tiles of the group;
+ * out[3] = S, the split count; out[4] = reduction rows per split (a multiple of 64; a split that starts past K writes a slab
+ * of zeros); out[5] = the block order of the 256 x 128 kernel (> 0: XCD groups, -1: eighths of the split-major work list,
+ * 0: tile-major; 0 on the 128 x 128 kernel); out[6] = workgroups launched; out[7] = the fold kernel's instantiation (2 .. 8 =
+ * unrolled for that many slabs, 0 = its run-time loop, -1 = no fold: S == 1).  The workspace the launch needs is
+ * S * sum(M_i N_i) * 4 bytes, never more than avf_gemm_tn_group_workspace_bytes.
+ * avf_gemm_tn_plan: the same for avf_gemm(AVF_BF16, transA = 1, transB = 0): out[0] = S (up to 32), out[1] = rows per split. */
 size_t avf_gemm_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N);
 int avf_gemm_tn_group(int count, int64_t K, const void* const* A, const void* const* B, float* const* C, const int64_t* M,
                       const int64_t* N, void* workspace, void* stream);
+int avf_gemm_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out);
+int avf_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int32_t* out);
 
 /* MX-FP8 operands (OCP microscaling: e4m3 elements, one E8M0 scale byte per 32 consecutive elements of a row) for the
  * forward nn.Linear GEMMs (heads.py:191,195,212) on v_mfma_scale_f32_16x16x128_f8f6f4 - BASELINE config 5.

@@ -353,6 +353,23 @@ extern "C" size_t avf_gemm_tn_group_workspace_bytes(int count, int64_t K, const 
   if (fill_tn_group(&g, count, K, nullptr, nullptr, nullptr, M, N)) return 0;
   return gemm_bf16_tn_group_ws(g);
 }
+extern "C" int avf_gemm_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out) {
+  AVF_REQUIRE(out, "gemm_tn_group_plan: null pointer");
+  TnGroupArgs g;
+  AVF_TRY(fill_tn_group(&g, count, K, nullptr, nullptr, nullptr, M, N));
+  AVF_REQUIRE(gemm_bf16_tn_group_ok(g), "gemm_tn_group_plan: unsupported shapes (K%%64, M%%8, N%%8)");
+  const TnGroupPlan pl = gemm_bf16_tn_group_plan_full(g);
+  out[0] = pl.big; out[1] = pl.waves; out[2] = pl.tiles; out[3] = pl.S;
+  out[4] = pl.kchunk; out[5] = pl.xcd_groups; out[6] = pl.blocks; out[7] = pl.fold;
+  return 0;
+}
+extern "C" int avf_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int32_t* out) {
+  AVF_REQUIRE(out && M > 0 && N > 0 && K > 0 && M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "gemm_tn_plan: bad arguments");
+  int S = 1, kchunk = 0;
+  gemm_bf16_tn_plan(M, N, K, &S, &kchunk);
+  out[0] = S; out[1] = kchunk;
+  return 0;
+}
 extern "C" int avf_gemm_tn_group(int count, int64_t K, const void* const* A, const void* const* B, float* const* C,
                                  const int64_t* M, const int64_t* N, void* workspace, void* stream) {
   AVF_REQUIRE(A && B && C, "gemm_tn_group: null pointer");

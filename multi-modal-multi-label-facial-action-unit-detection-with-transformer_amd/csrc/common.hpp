@@ -616,6 +616,20 @@ bool gemm_bf16_tn_group_ok(const TnGroupArgs& a);
 size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a);
 // the tile count of the group on the kernel it would run on, and the workgroup slots of one round of that kernel
 void gemm_bf16_tn_group_plan(const TnGroupArgs& a, int* tiles, int* slots);
+// Everything gemm_bf16_tn_group decides before it launches (shapes, K and the tuning switches only; no pointer is read): the
+// launch acts on exactly this, avf_gemm_tn_group_plan reports it.
+struct TnGroupPlan {
+  int big;         // 1 = the 256 x 128 tile (gemm_bf16_tn_group_big_kernel<3>), 0 = the 128 x 128 one (gemm_bf16_tn_group_kernel)
+  int waves;       // wavefronts per workgroup: 8 on the 256 x 128 tile; 4 (<2>) or 8 (<4>) on the 128 x 128 one
+  int tiles;       // output tiles of the whole group
+  int S, kchunk;   // split count and reduction rows per split (a multiple of 64; a split that starts past K writes zeros)
+  int xcd_groups;  // block -> (tile, split) order of the 256 x 128 kernel (TnGroup::xcd_groups); 0 on the 128 x 128 one
+  int blocks;      // workgroups launched (>= tiles * S: the XCD-aware orders round up to a multiple of 8)
+  int fold;        // fold_group_kernel<SS>: SS = 2 .. 8, 0 = its run-time loop, -1 = no slab fold (S == 1)
+};
+TnGroupPlan gemm_bf16_tn_group_plan_full(const TnGroupArgs& a);
+// the single-problem path (gemm_bf16_tn): split count and reduction rows per split
+void gemm_bf16_tn_plan(int64_t M, int64_t N, int64_t K, int* S, int* kchunk);
 int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extra_folds = nullptr);
 // the same group for fp32 operands in the parity mode's bf16x3 arithmetic (gemm_f32.hip, round 6): one launch + one fold
 bool gemm_f32x3_tn_group_ok(const TnGroupArgs& a);

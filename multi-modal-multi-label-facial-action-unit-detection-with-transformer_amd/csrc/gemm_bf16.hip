@@ -852,10 +852,12 @@ __global__ __launch_bounds__(256) void fold_group_kernel(TnGroup g, int nslab, F
   }
 }
 
-// f(int_c<SS>{}) for fold_group_kernel<SS>: the split counts it is unrolled for (2 .. 8), else 0 = the run-time loop
+// the fold instantiation of a split count (TnGroupPlan::fold): unrolled for 2 .. 8 slabs, 0 = the run-time loop, -1 = no slabs
+int fold_code(int S) { return S <= 1 ? -1 : (S <= 8 ? S : 0); }
+// f(int_c<SS>{}) for fold_group_kernel<SS>, SS = a fold code; without slabs (-1: column folds alone) the run-time form
 template <typename F>
-int with_fold_splits(int S, F&& f) {
-  switch (S) {
+int with_fold_splits(int code, F&& f) {
+  switch (code) {
     case 2: return f(int_c<2>{});
     case 3: return f(int_c<3>{});
     case 4: return f(int_c<4>{});
@@ -870,10 +872,13 @@ int with_fold_splits(int S, F&& f) {
 int tn_group_splits(int total_tiles, int64_t K, int slots = kWorkgroupSlots) {
   const int forced = tuning_int("AVF_TN_SPLITS", 0);  // tuning aid (read per call: a test runs both arms in one process)
   if (forced > 0) return forced;
-  // kWorkgroupSlots (2 per CU at 72 KiB of LDS).  Pick the split count whose total workgroup count fills whole rounds of
-  // them best, charging 5 % per extra slab for the fold's traffic: 128 tiles (d = 512) -> 4 splits = exactly one round;
-  // 288 tiles (d = 768) -> 3 splits = 1.7 rounds (84 % full) instead of 2 splits = 1.125 rounds (56 %): 3.90 -> 3.13 ms per
-  // step at C4 (measured sweep: 3 splits 3.13, 4: 3.22, 5: 3.26, 6: 3.20, 8: 3.17 ms)
+  // `slots` = the workgroups of one round of the kernel that runs: kWorkgroupSlots (2 per CU) on the 128 x 128 tile, half of
+  // them (1 per CU) on the 256 x 128 one.  Pick the split count whose total workgroup count fills whole rounds of them best,
+  // charging 5 % per extra slab for the fold's traffic.  A layer's weight gradients run on the 256 x 128 tile (what
+  // avf_gemm_tn_group_plan reports, pinned in tests/test_gemm_tn_ref_cpu.py): 64 tiles (d = 512, 10 368 token rows) -> 4 splits
+  // = exactly one round of 256; 144 tiles (d = 768, 16 384 token rows) -> 3 splits = 1.7 rounds (84 % full) instead of 2 splits
+  // = 1.125 rounds (56 %): 3.90 -> 3.13 ms per step at C4 (measured sweep: 3 splits 3.13, 4: 3.22, 5: 3.26, 6: 3.20, 8: 3.17 ms).
+  // The same counts in 128 x 128 tiles: 128 and 288 on 512 slots.  d = 768 over fewer than 3072 rows runs unsplit (below).
   // at least 16 K-steps per workgroup - 4 where the unsplit tiles leave more than half of the slots empty (short inputs: ~1 k
   // token rows; each K-step of a lone workgroup is a full memory round trip, so more, shorter workgroups win: real avformer
   // heads 0.671 -> 0.637 ms per step, TFormer at 17 tokens 0.444 -> 0.437)
@@ -910,6 +915,10 @@ size_t gemm_nt_colsum_ws(int64_t M, int64_t N) { return (size_t)(ceil_div(M, 32)
 size_t gemm_bf16_tn_ws(int64_t M, int64_t N, int64_t K) {
   const int s = tn_splits(M, N, K);
   return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
+}
+void gemm_bf16_tn_plan(int64_t M, int64_t N, int64_t K, int* S, int* kchunk) {
+  *S = tn_splits(M, N, K);
+  *kchunk = split_plan(K, *S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
 }
 
 int gemm_bf16_nt(const GemmArgs& a, hipStream_t s) {
@@ -983,26 +992,28 @@ int gemm_bf16_tn(const GemmArgs& a, hipStream_t s) {
   AVF_REQUIRE(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0 && ((uintptr_t)a.C & 15) == 0,
               "gemm_bf16_tn: operands must be 16-byte aligned");
   AVF_REQUIRE(a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31), "gemm_bf16_tn: shape too large");
+  int S = 1, kchunk = 0;
+  gemm_bf16_tn_plan(a.M, a.N, a.K, &S, &kchunk);
+  // both refused BEFORE anything is enqueued: a refused call leaves C as it was
+  AVF_REQUIRE(S == 1 || a.workspace, "gemm_bf16_tn: split-K workspace missing");
+  AVF_REQUIRE(S == 1 || a.ldc == a.N, "gemm_bf16_tn: split-K path needs a dense C (ldc == N)");
   static PerDeviceOnce attr_set;
   if (attr_set.need()) {
     hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_SMEM);
     AVF_REQUIRE(e == hipSuccess, "gemm_bf16_tn: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     attr_set.mark();
   }
-  const int S = tn_splits(a.M, a.N, a.K);
-  AVF_REQUIRE(S == 1 || a.workspace, "gemm_bf16_tn: split-K workspace missing");
   TnParams p;
   TimingScope ts(KC_GEMM_BF16_TN, 2.0 * a.M * a.N * a.K, 2.0 * (a.M * a.K + a.N * a.K) + 4.0 * a.M * a.N, s, /*per_kernel=*/true);
   p.A = (const bf16*)a.A; p.lda = a.lda; p.B = (const bf16*)a.B; p.ldb = a.ldb;
   p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
-  p.kchunk = split_plan(a.K, S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
+  p.kchunk = kchunk;
   if (S > 1) { p.C = (float*)a.workspace; p.ldc = a.N; p.slab = a.M * a.N; }
   else { p.C = (float*)a.C; p.ldc = a.ldc; p.slab = 0; }
   dim3 grid((unsigned)ceil_div(a.N, TB), (unsigned)ceil_div(a.M, TB), (unsigned)S);
   launch_in_scope(&ts, gemm_bf16_tn_kernel, grid, dim3(256), TN_SMEM, s, p);
   AVF_TRY(check_launch("gemm_bf16_tn_kernel"));
   if (S > 1) {
-    AVF_REQUIRE(a.ldc == a.N, "gemm_bf16_tn: split-K path needs a dense C (ldc == N)");
     const int64_t n4 = a.M * a.N / 4;
     int64_t blocks = ceil_div(n4, 256);
     if (blocks > 2048) blocks = 2048;
@@ -1044,6 +1055,35 @@ void gemm_bf16_tn_group_plan(const TnGroupArgs& a, int* tiles, int* slots) {
   *slots = big ? kWorkgroupSlots / 2 : kWorkgroupSlots;
 }
 
+TnGroupPlan gemm_bf16_tn_group_plan_full(const TnGroupArgs& a) {
+  TnGroupPlan pl;
+  int slots = 0;
+  gemm_bf16_tn_group_plan(a, &pl.tiles, &slots);
+  pl.big = slots == kWorkgroupSlots / 2;
+  pl.S = tn_group_splits(pl.tiles, a.K, slots);
+  pl.kchunk = split_plan(a.K, pl.S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
+  pl.fold = fold_code(pl.S);
+  pl.xcd_groups = 0;
+  pl.blocks = pl.tiles * pl.S;
+  static const int tn_waves = tuning_int("AVF_TN_WAVES", 4);  // tuning aid; 8 waves measured 5 % slower here (unlike the NT kernel)
+  pl.waves = (pl.big || tn_waves != 4) ? 8 : 4;
+  if (!pl.big) return pl;
+  static const int xcd_order = tuning_int("AVF_TN_XCD", 1);  // tuning aid: 0 = tile-major block ids
+  if (!xcd_order) return pl;
+  // the XCD-aware orders deal 8 equal runs of block ids: 8 x the longest run of tiles (S | 8) or of (split, tile) items
+  const bool divides = pl.S == 1 || pl.S == 2 || pl.S == 4 || pl.S == 8;
+  pl.xcd_groups = divides ? 8 / pl.S : -1;
+  const int runs = divides ? pl.xcd_groups : 8;
+  const int64_t items = divides ? pl.tiles : (int64_t)pl.tiles * pl.S;
+  int per = 0;
+  for (int r = 0; r < runs; ++r) {
+    const int n = (int)(items * (r + 1) / runs - items * r / runs);
+    per = n > per ? n : per;
+  }
+  pl.blocks = 8 * per;
+  return pl;
+}
+
 size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a) {
   size_t elems = 0;
   for (int i = 0; i < a.count; ++i) elems += (size_t)a.M[i] * a.N[i];
@@ -1056,13 +1096,14 @@ size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a) {
 
 int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extra_folds) {
   AVF_REQUIRE(gemm_bf16_tn_group_ok(a), "gemm_bf16_tn_group: unsupported shapes/alignment (K%%64, M%%8, N%%8, 16-byte alignment)");
+  const TnGroupPlan pl = gemm_bf16_tn_group_plan_full(a);  // every decision of this launch; nothing below decides again
+  const bool big = pl.big != 0;
   TnGroup g;
   memset(&g, 0, sizeof(g));
   g.nprob = a.count;
   g.K = (int)a.K;
   int tiles = 0;
   double flops = 0, bytes = 0;
-  const bool big = tn_group_big(a);
   for (int i = 0; i < a.count; ++i) {
     TnProblem& P = g.p[i];
     P.A = (const bf16*)a.A[i]; P.B = (const bf16*)a.B[i]; P.C = a.C[i];
@@ -1073,9 +1114,11 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
     flops += 2.0 * a.M[i] * a.N[i] * a.K;
     bytes += 2.0 * (a.M[i] + a.N[i]) * a.K + 4.0 * a.M[i] * a.N[i];
   }
-  g.total_tiles = tiles;
-  g.S = tn_group_splits(tiles, a.K, big ? kWorkgroupSlots / 2 : kWorkgroupSlots);
-  g.kchunk = split_plan(a.K, g.S, TR).kchunk;  // (S stays: a split past the end of K writes a slab of zeros)
+  AVF_REQUIRE(tiles == pl.tiles, "gemm_bf16_tn_group: the tile list disagrees with the plan (internal error)");
+  g.total_tiles = pl.tiles;
+  g.S = pl.S;
+  g.kchunk = pl.kchunk;
+  g.xcd_groups = pl.xcd_groups;
   if (g.S > 1) {
     AVF_REQUIRE(a.workspace, "gemm_bf16_tn_group: split-K workspace missing");
     float* w = (float*)a.workspace;
@@ -1088,7 +1131,6 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
   if (shape_log_on())
     shape_log("gemm_bf16_tn,gemm_bf16_tn_group%s,%d,%d,%d,%lld,%d,%.0f,%.0f", big ? "_big_kernel<3>" : "_kernel", tiles * g.S,
               a.count, g.S, (long long)a.K, -1, flops, bytes);
-  static const int tn_waves = tuning_int("AVF_TN_WAVES", 4);  // tuning aid; 8 waves measured 5 % slower here (unlike the NT kernel)
   if (big) {
     static PerDeviceOnce raised3;
     if (raised3.need()) {
@@ -1096,30 +1138,9 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
                                       3 * 48 * 1024) == hipSuccess, "gemm_bf16_tn_group: cannot raise dynamic LDS limit");
       raised3.mark();
     }
-    static const int xcd_order = tuning_int("AVF_TN_XCD", 1);  // tuning aid: 0 = tile-major block ids
-    int nblocks = tiles * g.S;
-    g.xcd_groups = 0;
-    if (xcd_order && (g.S == 1 || g.S == 2 || g.S == 4 || g.S == 8)) {
-      g.xcd_groups = 8 / g.S;
-      int per = 0;  // tiles of the largest group
-      for (int grp = 0; grp < g.xcd_groups; ++grp) {
-        const int n = (int)((int64_t)tiles * (grp + 1) / g.xcd_groups - (int64_t)tiles * grp / g.xcd_groups);
-        per = n > per ? n : per;
-      }
-      nblocks = 8 * per;
-    } else if (xcd_order) {
-      g.xcd_groups = -1;
-      const int W = tiles * g.S;
-      int per = 0;
-      for (int x = 0; x < 8; ++x) {
-        const int n = (int)((int64_t)W * (x + 1) / 8 - (int64_t)W * x / 8);
-        per = n > per ? n : per;
-      }
-      nblocks = 8 * per;
-    }
-    launch_in_scope(&ts, gemm_bf16_tn_group_big_kernel<3>, dim3(nblocks), dim3(512), 3 * 48 * 1024, s, g);
-  } else if (tn_waves == 4) launch_in_scope(&ts, gemm_bf16_tn_group_kernel<2>, dim3(tiles * g.S), dim3(256), 0, s, g);
-  else launch_in_scope(&ts, gemm_bf16_tn_group_kernel<4>, dim3(tiles * g.S), dim3(512), 0, s, g);
+    launch_in_scope(&ts, gemm_bf16_tn_group_big_kernel<3>, dim3(pl.blocks), dim3(512), 3 * 48 * 1024, s, g);
+  } else if (pl.waves == 4) launch_in_scope(&ts, gemm_bf16_tn_group_kernel<2>, dim3(pl.blocks), dim3(256), 0, s, g);
+  else launch_in_scope(&ts, gemm_bf16_tn_group_kernel<4>, dim3(pl.blocks), dim3(512), 0, s, g);
   AVF_TRY(check_launch("gemm_bf16_tn_group_kernel"));
   FoldList fl;
   memset(&fl, 0, sizeof(fl));
@@ -1129,7 +1150,7 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
   if (nslab == 0 && fl.count > 3) return fold_list(fl, s);
   if (nslab + fl.count > 0) {
     dim3 grid(256, nslab + fl.count);
-    with_fold_splits(nslab ? g.S : 0, [&](auto ss) {
+    with_fold_splits(pl.fold, [&](auto ss) {
       launch_in_scope(&ts, fold_group_kernel<decltype(ss)::value>, grid, dim3(256), 0, s, g, nslab, fl);
       return 0;
     });

@@ -390,9 +390,39 @@ def gemm_ws(a: torch.Tensor, w_packed: torch.Tensor, n_out: int, out_dtype=None,
     return res[0] if len(res) == 1 else res
 
 
-def gemm_tn_group(pairs):
+TN_GROUP_PLAN_FIELDS = ("big", "waves", "tiles", "S", "kchunk", "xcd_groups", "blocks", "fold")
+
+
+def gemm_tn_group_plan(shapes, K: int) -> dict:
+    """What ``gemm_tn_group`` decides for problems of the shapes [(M_i, N_i), ...] over K reduction rows
+    (avf_gemm_tn_group_plan: the launcher's own decision, host code only, no device needed): dict(big = 1 for the 256 x 128
+    tile, waves per workgroup, tiles, S = split count, kchunk = rows per split, xcd_groups = block order of the 256 x 128
+    kernel, blocks launched, fold = fold_group_kernel's instantiation: 2 .. 8, 0 = run-time loop, -1 = none; and
+    workspace_bytes = what avf_gemm_tn_group_workspace_bytes promises for the group)."""
+    lib = _lib.load()
+    n = len(shapes)
+    Ms = (C.c_int64 * n)(*[int(m) for m, _ in shapes])
+    Ns = (C.c_int64 * n)(*[int(k) for _, k in shapes])
+    out = (C.c_int32 * 8)()
+    _lib.check(lib.avf_gemm_tn_group_plan(n, int(K), Ms, Ns, out), "gemm_tn_group_plan")
+    plan = dict(zip(TN_GROUP_PLAN_FIELDS, (int(v) for v in out)))
+    plan["workspace_bytes"] = int(lib.avf_gemm_tn_group_workspace_bytes(n, int(K), Ms, Ns))
+    return plan
+
+
+def gemm_tn_plan(M: int, N: int, K: int) -> dict:
+    """What ``gemm(trans_a=True, trans_b=False)`` decides on bf16 operands (avf_gemm_tn_plan): dict(S = split count,
+    kchunk = reduction rows per split)."""
+    out = (C.c_int32 * 2)()
+    _lib.check(_lib.load().avf_gemm_tn_plan(int(M), int(N), int(K), out), "gemm_tn_plan")
+    return dict(S=int(out[0]), kchunk=int(out[1]))
+
+
+def gemm_tn_group(pairs, outs=None, workspace=None):
     """[(A_i [K, M_i] bf16, B_i [K, N_i] bf16), ...] (up to 16, same K) -> [C_i [M_i, N_i] fp32 = A_i^T B_i]: the grouped
-    weight-gradient launch of a layer's backward, or of up to four layers' (avf_gemm_tn_group)."""
+    weight-gradient launch of a layer's backward, or of up to four layers' (avf_gemm_tn_group).  outs: preallocated
+    contiguous fp32 [M_i, N_i] tensors to write into (returned); workspace: a contiguous tensor of at least the bytes the
+    launch needs (gemm_tn_group_plan) to hold the split-K slabs.  Without them both are made here."""
     lib = _lib.load()
     n = len(pairs)
     As = [a.contiguous() for a, _ in pairs]
@@ -402,9 +432,24 @@ def gemm_tn_group(pairs):
     assert all(a.shape[0] == K and b.shape[0] == K and a.dtype == b.dtype == torch.bfloat16 for a, b in zip(As, Bs))
     Ms = (C.c_int64 * n)(*[a.shape[1] for a in As])
     Ns = (C.c_int64 * n)(*[b.shape[1] for b in Bs])
-    Cs = [torch.empty((a.shape[1], b.shape[1]), dtype=torch.float32, device=a.device) for a, b in zip(As, Bs)]
+    if outs is None:
+        Cs = [torch.empty((a.shape[1], b.shape[1]), dtype=torch.float32, device=a.device) for a, b in zip(As, Bs)]
+    else:
+        Cs = list(outs)
+        _need_cuda(*Cs)
+        if len(Cs) != n or not all(c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (a.shape[1], b.shape[1])
+                                   for a, b, c in zip(As, Bs, Cs)):
+            raise ValueError("gemm_tn_group: outs are contiguous fp32 [M_i, N_i] tensors, one per pair")
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    ws = _bytes(lib.avf_gemm_tn_group_workspace_bytes(n, K, Ms, Ns), As[0].device)
+    if workspace is None:
+        ws = _bytes(lib.avf_gemm_tn_group_workspace_bytes(n, K, Ms, Ns), As[0].device)
+    else:
+        ws = workspace
+        _need_cuda(ws)
+        plan = gemm_tn_group_plan([(a.shape[1], b.shape[1]) for a, b in zip(As, Bs)], K)
+        need = 0 if plan["S"] == 1 else 4 * plan["S"] * sum(a.shape[1] * b.shape[1] for a, b in zip(As, Bs))
+        if need and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16):
+            raise ValueError(f"gemm_tn_group: workspace must be contiguous, 16-byte aligned and hold {need} bytes")
     _lib.check(lib.avf_gemm_tn_group(n, K, arr(As), arr(Bs), arr(Cs), Ms, Ns, _ptr(ws), _stream()), "gemm_tn_group")
     return Cs
 

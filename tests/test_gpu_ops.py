@@ -587,12 +587,14 @@ def test_au_loss_on_output_rows_equals_the_sliced_form(ops):
 @pytest.mark.parametrize("K,shapes", [
     (128, [(64, 64)]),                                               # one 128 x 128 tile, two K-steps
     (4096, [(1536, 512), (1024, 512), (512, 1024), (512, 512)]),     # a d=512 layer: the 256 x 128 kernel (64 tiles)
-    (2112, [(2304, 768), (1536, 768), (768, 1536), (768, 768)]),     # d=768 (C4): ragged split-K chunks
+    (2112, [(2304, 768), (1536, 768), (768, 1536), (768, 768)]),     # d=768: 144 tiles of 256 x 128, UNSPLIT at this K (33 K-steps)
     (2048, [(1000, 136), (264, 520), (8, 8)]),                       # ragged tiles in both extents
 ])
 def test_gemm_tn_group(ops, K, shapes):
     """the grouped weight-gradient launch (avf_gemm_tn_group) against fp64 products, through both tile configurations
-    (the host picks 256 x 128 for big groups; AVF_TN_BIG forces one or the other in the A/B tools)"""
+    (the host picks 256 x 128 for big groups; AVF_TN_BIG forces one or the other in the A/B tools).  What each case plans to is
+    what ops.gemm_tn_group_plan reports; tests/test_gpu_gemm_tn.py holds every variant, split count and block order of the
+    family element-wise to fp64."""
     g = torch.Generator().manual_seed(K + len(shapes))
     pairs = [(torch.randn(K, m, generator=g).bfloat16(), torch.randn(K, n, generator=g).bfloat16()) for m, n in shapes]
     outs = ops.gemm_tn_group([(a.cuda(), b.cuda()) for a, b in pairs])
