@@ -827,6 +827,24 @@ int avf_conv2d_nhwc(const void* x, int x_dtype, const void* w_packed, const floa
 int avf_conv_plan(int N, int H, int W, int Cin, int Cout, int k, int stride, int* tile, int* tile_m, int* tile_n);
 int avf_avgpool_nhwc(const void* x, int x_dtype, float* out, int64_t N, int HW, int C, void* stream);
 
+/* ---- the same stages in the parity arithmetic (csrc/conv_f32.hip) ------------------------------------------------------------
+ * fp32 NHWC in, fp32 NHWC out, every fp32 product computed as three bf16 MFMA products ("bf16x3", as avf_gemm's fp32 mode):
+ * v -> hi = bf16(v) (RNE), lo = bf16(v - hi) (the difference is exact in fp32);  x w ~ hi_w lo_x + lo_w hi_x + hi_w hi_x, each
+ * product exact in fp32, accumulated in fp32 in that order (v_mfma_f32_16x16x32_bf16); lo_w lo_x is not computed.  At most
+ * 3 * 2^-16 relative error per product.  This is the convolution's one parity arithmetic: avf_set_f32_arith does not
+ * reach it.
+ *   avf_conv_pack_weight_f32x3: w [Cout, Cin, k, k] fp32 -> w_hi, w_lo [Cout, k, k, Cin] bf16, the split above; scale / shift
+ *     as avf_conv_pack_weight folds them (fp64, stored as fp32 [Cout]).  Once per weight load.
+ *   avf_conv2d_nhwc_f32x3: avf_conv2d_nhwc's operation, shape rules (k = 3 or 1, stride 1 or 2, Cin % 32 == 0, Cout % 16 == 0),
+ *     alignment and overlap rules and tile dispatch (avf_conv_plan names the tile for both); x [N, H, W, Cin], residual (null:
+ *     none) and out [N, Ho, Wo, Cout] all fp32.  x is split as it is staged; the epilogue is fp32. */
+int avf_conv_pack_weight_f32x3(const float* w, const float* gamma, const float* beta, const float* running_mean,
+                               const float* running_var, double eps, void* w_hi, void* w_lo, float* scale, float* shift, int Cout,
+                               int Cin, int k, void* stream);
+int avf_conv2d_nhwc_f32x3(const float* x, const void* w_hi, const void* w_lo, const float* scale, const float* shift,
+                          const float* residual, int relu, int k, int stride, float* out, int N, int H, int W, int Cin, int Cout,
+                          void* stream);
+
 /* ---- frozen ResNet stem, forward only (csrc/stem.hip) -----------------------------------------------------------------------
  * What stands in front of layer1: conv1 (7x7, stride 2, pad 3, bias=False) - bn1 - relu - maxpool (3x3, stride 2, pad 1) of
  * ResFormer.forward (vformer.py:238-241) and of the audio stream's ResNet18 (audio.py:22-39, one input channel), in ONE launch

@@ -151,6 +151,8 @@ SIGNATURES = {
     "avf_feature_clip_tokens": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp]),
     "avf_conv_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _int, _vp]),
     "avf_conv2d_nhwc": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _int, _vp]),
+    "avf_conv_pack_weight_f32x3": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
+    "avf_conv2d_nhwc_f32x3": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _vp]),
     "avf_conv_plan": (_int, [_int, _int, _int, _int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_avgpool_nhwc": (_int, [_vp, _int, _vp, _i64, _int, _int, _vp]),
     "avf_stem_packed_k": (_int, [_int]),

@@ -14,6 +14,12 @@ hip backend runs no map/token permute on either side of ``spatial_transformer``.
 ``conv1`` / ``bn1`` / ReLU / ``maxpool`` as the one launch of csrc/stem.hip, from NCHW planes straight to the NHWC bf16 map
 ``layer1`` reads: no torch compute op and no layout conversion between the front end's planes and the pooled features.
 
+``conv_dtype=`` picks the hip backend's conv arithmetic.  ``"bf16"`` (default) is the throughput form above.  ``"f32"`` is the
+parity form, csrc/conv_f32.hip: every map between launches is fp32 and every fp32 product runs as three bf16 MFMA products
+(bf16x3, the arithmetic of ``compute_dtype="f32"``; ``set_f32_arithmetic`` does not reach the conv).  The stem kernel has no
+parity form: in this mode the stem is the torch definition in fp32, followed by one NCHW -> NHWC fp32 conversion, and
+``stem="hip"`` is refused.
+
 The hip backend computes no gradients: with grad mode on and an input or parameter that requires grad, ``forward`` raises
 instead of silently cutting the graph."""
 from __future__ import annotations
@@ -29,6 +35,7 @@ from .heads import ResFormerTokens
 
 BACKENDS = ("torch", "hip")
 STEMS = ("torch", "hip")
+CONV_DTYPES = ("bf16", "f32")
 _CH = 32  # the conv kernel's channel granule (Cin % 32 == 0): other widths run zero-padded to it
 
 
@@ -46,6 +53,19 @@ def _check_stem(stem, backend):
     return stem
 
 
+def _check_conv_dtype(conv_dtype, stem="torch"):
+    if conv_dtype not in CONV_DTYPES:
+        raise ValueError(f"conv_dtype must be one of {CONV_DTYPES}, got {conv_dtype!r}")
+    if conv_dtype == "f32" and stem == "hip":
+        raise ValueError("stem='hip' with conv_dtype='f32': the stem kernel (csrc/stem.hip) has no parity form - it holds its "
+                         "whole bf16 weight image in registers and a second image does not fit; use stem='torch'")
+    return conv_dtype
+
+
+def _map_dtype(conv_dtype):
+    return torch.float32 if conv_dtype == "f32" else torch.bfloat16
+
+
 def _pad_to(n: int) -> int:
     return -(-n // _CH) * _CH
 
@@ -57,12 +77,12 @@ def _no_grad_or_raise(module: nn.Module, x: torch.Tensor, who: str):
                            "(requires_grad_(False)); backend='torch' differentiates")
 
 
-def to_nhwc(x: torch.Tensor, channels: Optional[int] = None) -> torch.Tensor:
-    """NCHW -> NHWC bf16 (contiguous), zero-padded to ``channels``"""
+def to_nhwc(x: torch.Tensor, channels: Optional[int] = None, dtype=torch.bfloat16) -> torch.Tensor:
+    """NCHW -> NHWC ``dtype`` (bf16 by default; contiguous), zero-padded to ``channels``"""
     x = x.permute(0, 2, 3, 1)
     if channels is not None and channels != x.shape[-1]:
         x = F.pad(x, (0, channels - x.shape[-1]))
-    return x.to(torch.bfloat16).contiguous()
+    return x.to(dtype).contiguous()
 
 
 class FrozenBasicBlock(nn.Module):
@@ -70,10 +90,14 @@ class FrozenBasicBlock(nn.Module):
     are ordinary ``nn.Conv2d`` / ``nn.BatchNorm2d`` children with the reference's state_dict keys and shapes.
     ``forward`` takes and returns NCHW fp32 with either backend; ``forward_nhwc`` is the hip backend's native form (two launches, or
     three with a downsample).  The packed bf16 weights and folded BatchNorm are rebuilt whenever a parameter or buffer changes
-    (version counters, and a ``load_state_dict`` hook); writes through ``.data`` bypass the counters: call ``refresh_weights()``."""
+    (version counters, and a ``load_state_dict`` hook); writes through ``.data`` bypass the counters: call ``refresh_weights()``.
+
+    ``conv_dtype="f32"`` (hip backend) is the parity form (csrc/conv_f32.hip): every map stays fp32 and every fp32 product runs
+    as three bf16 MFMA products (bf16x3), weights packed as a hi and a lo bf16 image.  ``"bf16"`` (default) launches what it
+    always launched."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, backend="torch"):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, backend="torch", conv_dtype="bf16"):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
@@ -82,6 +106,7 @@ class FrozenBasicBlock(nn.Module):
         self.downsample = downsample
         self.stride, self.inplanes, self.planes = stride, inplanes, planes
         self.backend = _check_backend(backend)
+        self.conv_dtype = _check_conv_dtype(conv_dtype)
         self._packed = None
 
     @staticmethod
@@ -103,7 +128,7 @@ class FrozenBasicBlock(nn.Module):
 
     def _state_key(self, device):
         ts = [t for conv, bn in self._pairs() for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        return (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+        return (str(device), self.conv_dtype) + tuple((t.data_ptr(), t._version) for t in ts)
 
     def refresh_weights(self):
         self._packed = None
@@ -112,10 +137,14 @@ class FrozenBasicBlock(nn.Module):
         self._packed = None
         return super()._load_from_state_dict(*args, **kwargs)
 
+    def set_conv_dtype(self, conv_dtype):
+        self.conv_dtype = _check_conv_dtype(conv_dtype)
+        return self
+
     def _pack(self, device):
         key = self._state_key(device)
         if self._packed is None or self._packed[0] != key:
-            packs = []
+            packs, pack = [], ops.conv_pack_weight_f32 if self.conv_dtype == "f32" else ops.conv_pack_weight
             for conv, bn in self._pairs():
                 w, ts = conv.weight.detach(), [t.detach() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
                 if not w.is_cuda:
@@ -125,14 +154,19 @@ class FrozenBasicBlock(nn.Module):
                 if (co, ci) != tuple(w.shape[:2]):  # zero weights, gamma = beta = mean = 0, var = 1: the padded channels stay 0
                     w = F.pad(w, (0, 0, 0, 0, 0, ci - w.shape[1], 0, co - w.shape[0]))
                     ts = [F.pad(t, (0, co - t.numel()), value=float(i == 3)) for i, t in enumerate(ts)]
-                packs.append(ops.conv_pack_weight(w.float(), *[t.float() for t in ts], eps=bn.eps))
+                packs.append(pack(w.float(), *[t.float() for t in ts], eps=bn.eps))
             self._packed = (key, packs)
         return self._packed[1]
 
     def forward_nhwc(self, x, out_dtype=torch.bfloat16):
-        """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(planes)] in ``out_dtype``"""
+        """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(planes)] in ``out_dtype``; with ``conv_dtype="f32"`` x
+        is fp32 and so is every map, the output included (``out_dtype`` does not apply)"""
         _no_grad_or_raise(self, x, "FrozenBasicBlock")
         p = self._pack(x.device)
+        if self.conv_dtype == "f32":
+            h = ops.conv2d_nhwc_f32(x, *p[0], k=3, stride=self.stride, relu=True)
+            identity = x if self.downsample is None else ops.conv2d_nhwc_f32(x, *p[2], k=1, stride=self.stride)
+            return ops.conv2d_nhwc_f32(h, *p[1], k=3, stride=1, residual=identity, relu=True)
         h = ops.conv2d_nhwc(x, *p[0], k=3, stride=self.stride, relu=True)
         identity = x if self.downsample is None else ops.conv2d_nhwc(x, *p[2], k=1, stride=self.stride)
         return ops.conv2d_nhwc(h, *p[1], k=3, stride=1, residual=identity, relu=True, out_dtype=out_dtype)
@@ -141,7 +175,7 @@ class FrozenBasicBlock(nn.Module):
         if self.backend == "torch":
             return self._forward_torch(x)
         ops._need_cuda(x)
-        y = self.forward_nhwc(to_nhwc(x, _pad_to(self.inplanes)), out_dtype=torch.float32)
+        y = self.forward_nhwc(to_nhwc(x, _pad_to(self.inplanes), _map_dtype(self.conv_dtype)), out_dtype=torch.float32)
         return y[..., :self.planes].permute(0, 3, 1, 2).contiguous()
 
 
@@ -201,12 +235,18 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
     writes that NHWC bf16 map (``in_channels`` 1, 3 or 4).  Then ``layer1`` .. ``layer3`` on the conv kernel; the last launch of ``layer3`` writes
     the fp32 tokens, ``pos_embedding`` is added, ``spatial_transformer`` runs, and its output goes straight into ``layer4``;
     ``avgpool`` is the NHWC pool kernel.  The token section is this package's ``Transformer`` with either backend, so the
-    module needs the GPU either way."""
+    module needs the GPU either way.
 
-    def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16", stem="torch"):
+    ``conv_dtype="f32"`` (hip backend): the parity form of the conv stages (csrc/conv_f32.hip, bf16x3 products, fp32 maps
+    throughout); the stem is the torch definition in fp32, followed by one NCHW -> NHWC fp32 conversion (``stem="hip"`` has no
+    parity form and is refused).  With ``compute_dtype="f32"`` the whole module then runs in parity arithmetic."""
+
+    def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16", stem="torch",
+                 conv_dtype="bf16"):
         super().__init__(dropout=dropout, compute_dtype=compute_dtype)
         self.backend = _check_backend(backend)
         self.stem_backend = _check_stem(stem, backend)
+        self.conv_dtype = _check_conv_dtype(conv_dtype, stem)
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -225,26 +265,36 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
         downsample = None
         if stride != 1 or self.inplanes != planes:
             downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes, kernel_size=1, stride=stride, bias=False), nn.BatchNorm2d(planes))
-        stage = [FrozenBasicBlock(self.inplanes, planes, stride, downsample, backend=self.backend)]
+        stage = [FrozenBasicBlock(self.inplanes, planes, stride, downsample, backend=self.backend, conv_dtype=self.conv_dtype)]
         self.inplanes = planes
-        stage += [FrozenBasicBlock(planes, planes, backend=self.backend) for _ in range(1, blocks)]
+        stage += [FrozenBasicBlock(planes, planes, backend=self.backend, conv_dtype=self.conv_dtype) for _ in range(1, blocks)]
         return _Stage(*stage)
 
     def set_backend(self, backend, stem=None):
         """``stem=None`` keeps the stem where it is"""
         stem = _check_stem(self.stem_backend if stem is None else stem, _check_backend(backend))
+        _check_conv_dtype(self.conv_dtype, stem)
         self.backend, self.stem_backend = backend, stem
         for m in self.modules():
             if isinstance(m, FrozenBasicBlock):
                 m.backend = backend
         return self
 
+    def set_conv_dtype(self, conv_dtype):
+        """``"bf16"`` / ``"f32"``: the arithmetic of the hip backend's conv stages; the packed images are rebuilt on the next call"""
+        self.conv_dtype = _check_conv_dtype(conv_dtype, self.stem_backend)
+        for m in self.modules():
+            if isinstance(m, FrozenBasicBlock):
+                m.set_conv_dtype(conv_dtype)
+        return self
+
     def stages_to_tokens(self, x):
         """hip: the stem's NCHW output -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens + pos_embedding, (h, w))"""
-        return self.nhwc_to_tokens(to_nhwc(x))
+        return self.nhwc_to_tokens(to_nhwc(x, dtype=_map_dtype(self.conv_dtype)))
 
     def nhwc_to_tokens(self, x):
-        """hip: the stem's NHWC bf16 map -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens + pos_embedding, (h, w))"""
+        """hip: the stem's NHWC map (bf16; fp32 with ``conv_dtype="f32"``) -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens +
+        pos_embedding, (h, w))"""
         x = self.layer3.forward_nhwc(self.layer2.forward_nhwc(self.layer1.forward_nhwc(x)), out_dtype=torch.float32)
         t = x.view(x.shape[0], x.shape[1] * x.shape[2], x.shape[3])               # NHWC IS [B', tokens, C]: no permute
         return t + self.pos_embedding[:, :t.shape[1]], (x.shape[1], x.shape[2])   # vformer.py:253
@@ -272,9 +322,10 @@ class _FrozenResNet18(_HipStem, nn.Module):
     ``maxpool``, ``layer1`` .. ``layer4``, ``avgpool``, ``fc`` - with torchvision's state_dict keys, written out here because
     torchvision is not a dependency.  ``fc`` is the identity, as avformer.py:50 leaves it."""
 
-    def __init__(self, layers=(2, 2, 2, 2), in_channels=1, backend="torch"):
+    def __init__(self, layers=(2, 2, 2, 2), in_channels=1, backend="torch", conv_dtype="bf16"):
         super().__init__()
         self.backend = backend
+        self.conv_dtype = _check_conv_dtype(conv_dtype)
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -296,7 +347,8 @@ class _FrozenResNet18(_HipStem, nn.Module):
         if self.backend == "torch":
             x = self.layer4(self.layer3(self.layer2(self.layer1(self.stem(x)))))
             return self.fc(torch.flatten(self.avgpool(x), 1))
-        x = self.stem_nhwc(x)
+        # parity form: the stem as the torch definition in fp32 (the stem kernel has no parity form), fp32 maps from there on
+        x = to_nhwc(self.stem(x.float()), dtype=torch.float32) if self.conv_dtype == "f32" else self.stem_nhwc(x)
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
             x = stage.forward_nhwc(x)
         return self.fc(ops.avgpool_nhwc(x))
@@ -309,13 +361,23 @@ class FrozenAudioModel(nn.Module):
     ``strict=False`` load.
 
     ``backend="torch"`` (default) is the definition; ``backend="hip"`` is the stem kernel (csrc/stem.hip), the four stages on
-    the conv kernel and ``ops.avgpool_nhwc``: NCHW planes in, no torch compute op, forward only (``_no_grad_or_raise``)."""
+    the conv kernel and ``ops.avgpool_nhwc``: NCHW planes in, no torch compute op, forward only (``_no_grad_or_raise``).
+    ``conv_dtype="f32"`` (hip backend): the stages in the parity form (csrc/conv_f32.hip, fp32 maps, bf16x3 products) behind
+    the stem as the torch definition in fp32 - the stem kernel has no parity form."""
 
-    def __init__(self, backend="torch", layers=(2, 2, 2, 2)):
+    def __init__(self, backend="torch", layers=(2, 2, 2, 2), conv_dtype="bf16"):
         super().__init__()
         self.backend = _check_backend(backend)
-        self.resnet = _FrozenResNet18(layers, in_channels=1, backend=backend)
+        self.conv_dtype = _check_conv_dtype(conv_dtype)
+        self.resnet = _FrozenResNet18(layers, in_channels=1, backend=backend, conv_dtype=conv_dtype)
         self.modes = ["audio_features"]
+
+    def set_conv_dtype(self, conv_dtype):
+        self.conv_dtype = self.resnet.conv_dtype = _check_conv_dtype(conv_dtype)
+        for m in self.modules():
+            if isinstance(m, FrozenBasicBlock):
+                m.set_conv_dtype(conv_dtype)
+        return self
 
     def set_backend(self, backend):
         self.backend = self.resnet.backend = _check_backend(backend)
@@ -335,12 +397,16 @@ class FrozenVideoModel(nn.Module):
     """``VideoModel`` (vformer.py:295-311) with its fc replaced by the identity, as avformer.py:61-66 uses it: clip [B, C, T, H, W]
     -> the last ``num_channels`` channels -> ``s_former`` -> ``t_former`` -> [B, 512]"""
 
-    def __init__(self, backend="torch", compute_dtype="bf16", stem="torch"):
+    def __init__(self, backend="torch", compute_dtype="bf16", stem="torch", conv_dtype="bf16"):
         super().__init__()
         from .heads import TFormer
-        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype, stem=stem)
+        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype, stem=stem, conv_dtype=conv_dtype)
         self.t_former = TFormer(compute_dtype=compute_dtype)
         self.num_channels = 3
+
+    def set_conv_dtype(self, conv_dtype):
+        self.s_former.set_conv_dtype(conv_dtype)
+        return self
 
     def forward(self, x):
         x = x[:, -self.num_channels:].permute(0, 2, 1, 3, 4)

@@ -57,16 +57,29 @@ class ResFormerShell(ResFormerTokens):
 FROZEN_BACKBONES = ("resnet18_frozen", "resnet18_frozen_fused")
 
 
-def _s_former(backbone, num_channels=3, **kw):
+def _check_backbone_dtype(backbone, backbone_dtype):
+    """``backbone_dtype`` is ``"bf16"`` or ``"f32"``; the fused-stem backbone has no ``"f32"`` form"""
+    from .backbone import _check_conv_dtype
+    _check_conv_dtype(backbone_dtype)
+    if backbone_dtype == "f32" and backbone == "resnet18_frozen_fused":
+        raise ValueError("backbone='resnet18_frozen_fused' with backbone_dtype='f32': that is stem='hip' with conv_dtype='f32', and "
+                         "the stem kernel (csrc/stem.hip) has no parity form; use backbone='resnet18_frozen'")
+    return backbone_dtype
+
+
+def _s_former(backbone, num_channels=3, backbone_dtype="bf16", **kw):
     """the S-Former of a ``*former`` model: ``backbone=None`` or a ``(stem, tail)`` pair -> ``ResFormerShell``;
     ``backbone="resnet18_frozen"`` -> ``backbone.FrozenResFormer`` on the HIP conv kernels (eval-mode stages, forward only), whose
     ``conv1`` takes the ``num_channels`` channels the modality selects (vformer.py:313-331); ``"resnet18_frozen_fused"`` -> the
-    same with the stem on its HIP kernel too"""
+    same with the stem on its HIP kernel too.  ``backbone_dtype``: ``"bf16"`` (default) or ``"f32"``, the frozen module's
+    ``conv_dtype`` - ``"f32"`` runs its conv stages in the parity arithmetic (csrc/conv_f32.hip) and has no fused-stem form"""
+    _check_backbone_dtype(backbone, backbone_dtype)
     if isinstance(backbone, str):
         if backbone not in FROZEN_BACKBONES:
             raise ValueError(f"backbone must be None, a (stem, tail) pair or one of {FROZEN_BACKBONES}, got {backbone!r}")
         from .backbone import FrozenResFormer
-        return FrozenResFormer(backend="hip", in_channels=num_channels, stem="hip" if backbone.endswith("_fused") else "torch", **kw)
+        return FrozenResFormer(backend="hip", in_channels=num_channels, stem="hip" if backbone.endswith("_fused") else "torch",
+                               conv_dtype=backbone_dtype, **kw)
     return ResFormerShell(backbone, **kw)
 
 
@@ -96,11 +109,12 @@ class _FormerTask(nn.Module, _TaskLossMixin):
 class SpatialFormerModel(_FormerTask):
     """registry name ``sformer`` (sformer.py:338-382): per-frame features -> fc head, AU logits from ``AU_former``"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
+                 backbone_dtype="bf16"):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.base_model = _s_former(backbone, self.num_channels, dropout=0.2, compute_dtype=compute_dtype)
+        self.base_model = _s_former(backbone, self.num_channels, backbone_dtype, dropout=0.2, compute_dtype=compute_dtype)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype)
@@ -122,9 +136,9 @@ class SpatialFormerModel(_FormerTask):
 
 
 class _VideoModel(nn.Module):
-    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype, num_channels=3):
+    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype, num_channels=3, backbone_dtype="bf16"):
         super().__init__()
-        self.s_former = _s_former(backbone, num_channels, compute_dtype=compute_dtype)
+        self.s_former = _s_former(backbone, num_channels, backbone_dtype, compute_dtype=compute_dtype)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype) if au_tokens else None
         self.t_former = TFormer(dim=temporal_dim, compute_dtype=compute_dtype)
 
@@ -139,11 +153,12 @@ class _VideoModel(nn.Module):
 class VisualFormerModel(_FormerTask):
     """registry name ``vformer`` (vformer.py:358-387): S-Former frames -> ``TFormer`` over 16 frames -> fc head"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
+                 backbone_dtype="bf16"):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.video_model = _VideoModel(backbone, 512, False, compute_dtype, self.num_channels)
+        self.video_model = _VideoModel(backbone, 512, False, compute_dtype, self.num_channels, backbone_dtype)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vformer'])
@@ -156,11 +171,12 @@ class SpatialTemporalFormerModel(_FormerTask):
     """registry name ``tformer`` (tformer.py:405-436): per-frame AU tokens -> ``TFormer(dim=1536)`` -> fc head, AU logits
     from ``tformer_AU_head`` on the [B, 12, 128] view of the temporal feature"""
 
-    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain"):
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
+                 backbone_dtype="bf16"):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype, self.num_channels)
+        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype, self.num_channels, backbone_dtype)
         self.task, self.modes = task, ["clip"]
         self.au_head = tformer_AU_head(dropout=0.2, compute_dtype=compute_dtype)
         self.fc = _fc_head(128 * 12)

@@ -38,15 +38,17 @@ def load_pretrain(model, weight_path):
 
 
 class AudioFormer(nn.Module):
-    def __init__(self, modality='A', audio_pretrained=False, task='EX', backbone=None, compute_dtype="bf16"):
+    def __init__(self, modality='A', audio_pretrained=False, task='EX', backbone=None, compute_dtype="bf16", backbone_dtype="bf16"):
         super().__init__()
+        from .backbone import _check_conv_dtype
+        _check_conv_dtype(backbone_dtype)  # "f32": the frozen backbone's conv stages in the parity arithmetic (csrc/conv_f32.hip)
         if isinstance(backbone, str):
             # "resnet18_frozen": the reference's AudioModel (audio.py:22-39, fc = identity as in avformer.py:50) on the HIP stem and
             # conv kernels - eval-mode, forward only (backbone.py); consumes mel maps [B, 1, 64, 1001]
             if backbone != "resnet18_frozen":
                 raise ValueError(f"backbone must be None, a module or 'resnet18_frozen', got {backbone!r}")
             from .backbone import FrozenAudioModel
-            backbone = FrozenAudioModel(backend="hip")
+            backbone = FrozenAudioModel(backend="hip", conv_dtype=backbone_dtype)
         self.audio_model = backbone if backbone is not None else nn.Identity()
         self.task = task
         self.modes = ['audio_features']
@@ -58,8 +60,10 @@ class AudioFormer(nn.Module):
 
 class VisualFormer(nn.Module):
     def __init__(self, modality='A;V', video_pretrained=True, task='EX', backbone=None, in_features=512,
-                 compute_dtype="bf16"):
+                 compute_dtype="bf16", backbone_dtype="bf16"):
         super().__init__()
+        from .former_models import _check_backbone_dtype
+        _check_backbone_dtype(backbone, backbone_dtype)  # "f32": the frozen backbone's conv stages in the parity arithmetic
         if isinstance(backbone, str):
             # "resnet18_frozen": the reference's own VideoModel (vformer.py:295-311, fc = identity as in avformer.py:61-66) with
             # its ResNet stages on the HIP conv kernels - eval-mode, forward only (backbone.py); consumes clips [B, C, T, H, W]
@@ -68,7 +72,8 @@ class VisualFormer(nn.Module):
             if backbone not in FROZEN_BACKBONES:
                 raise ValueError(f"backbone must be None, a module or one of {FROZEN_BACKBONES}, got {backbone!r}")
             from .backbone import FrozenVideoModel
-            backbone = FrozenVideoModel(backend="hip", compute_dtype=compute_dtype, stem="hip" if backbone.endswith("_fused") else "torch")
+            backbone = FrozenVideoModel(backend="hip", compute_dtype=compute_dtype, stem="hip" if backbone.endswith("_fused") else "torch",
+                                        conv_dtype=backbone_dtype)
         self.video_model = backbone if backbone is not None else nn.Identity()
         self.task = task
         self.modes = ["clip"]
@@ -166,14 +171,15 @@ class _TaskLossMixin:
 class TwoStreamAuralVisualFormer(nn.Module, _TaskLossMixin):
     def __init__(self, modality='A;V;M', video_pretrained=True, audio_pretrained=True, task='EX',
                  video_weights=None, audio_weights=None, compute_dtype="bf16", task_losses="plain", video_backbone=None,
-                 audio_backbone=None):
+                 audio_backbone=None, backbone_dtype="bf16"):
         super().__init__()
+        # backbone_dtype="f32": both frozen streams run their conv stages in the parity arithmetic (backbone.py, conv_dtype)
         # audio_backbone="resnet18_frozen": the aural stream consumes mel maps [B, 1, 64, 1001] through the frozen ResNet18 on the
         # HIP path (backbone.FrozenAudioModel)
-        self.audio_model = AudioFormer(backbone=audio_backbone, compute_dtype=compute_dtype)
+        self.audio_model = AudioFormer(backbone=audio_backbone, compute_dtype=compute_dtype, backbone_dtype=backbone_dtype)
         # video_backbone="resnet18_frozen" / "resnet18_frozen_fused": the video stream consumes clips through the frozen S-Former on
         # the HIP path (the second with its stem on the HIP kernel too)
-        self.video_model = VisualFormer(backbone=video_backbone, compute_dtype=compute_dtype)
+        self.video_model = VisualFormer(backbone=video_backbone, compute_dtype=compute_dtype, backbone_dtype=backbone_dtype)
         if video_pretrained and load_pretrain(self.video_model, video_weights):
             for p in self.video_model.parameters():
                 p.requires_grad = False

@@ -1297,6 +1297,51 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, sh
     return out
 
 
+# ... in the parity arithmetic (csrc/conv_f32.hip)
+def conv_pack_weight_f32(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                         running_var: torch.Tensor, eps: float = 1e-5):
+    """``conv_pack_weight`` for ``conv2d_nhwc_f32``: -> ((w_hi, w_lo), scale, shift), w_hi = bf16(w) and w_lo = bf16(w - w_hi),
+    each [Cout, k*k*Cin] bf16 tap-major / channel-minor; scale / shift [Cout] fp32 (avf_conv_pack_weight_f32x3)."""
+    _need_cuda(w, gamma, beta, running_mean, running_var)
+    ts = [t.detach().contiguous() for t in (w, gamma, beta, running_mean, running_var)]
+    assert all(t.dtype == torch.float32 for t in ts) and ts[0].dim() == 4 and ts[0].shape[2] == ts[0].shape[3]
+    Cout, Cin, k, _ = ts[0].shape
+    assert all(t.numel() == Cout for t in ts[1:])
+    w_hi = torch.empty((Cout, k * k * Cin), dtype=torch.bfloat16, device=w.device)
+    w_lo = torch.empty_like(w_hi)
+    scale = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    shift = torch.empty(Cout, dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().avf_conv_pack_weight_f32x3(*[_ptr(t) for t in ts], float(eps), _ptr(w_hi), _ptr(w_lo), _ptr(scale),
+                                                      _ptr(shift), Cout, Cin, k, _stream()), "conv_pack_weight_f32")
+    return (w_hi, w_lo), scale, shift
+
+
+def conv2d_nhwc_f32(x: torch.Tensor, w_split, scale: torch.Tensor, shift: torch.Tensor, k: int, stride: int = 1,
+                    residual: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``conv2d_nhwc`` in the parity arithmetic (avf_conv2d_nhwc_f32x3): x [N, H, W, Cin], residual and out [N, Ho, Wo, Cout] all
+    fp32, ``w_split`` = (w_hi, w_lo) / scale / shift from ``conv_pack_weight_f32``.  Every fp32 product runs as three bf16 MFMA
+    products (bf16x3, oracle/bf16x3.py).  That is the convolution's one parity arithmetic: ``set_f32_arithmetic("f32")`` does not
+    reach it.  Same shapes, tiles (``conv_plan``) and errors as ``conv2d_nhwc``.  Forward only."""
+    w_hi, w_lo = w_split
+    _need_cuda(x, w_hi, w_lo, scale, shift, residual, out)
+    N, H, W, Cin = x.shape
+    Cout = w_hi.shape[0]
+    Ho, Wo = conv_out_hw(H, W, k, stride)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    for name, t, shape, dt in (("x", x, (N, H, W, Cin), torch.float32), ("w_hi", w_hi, (Cout, k * k * Cin), torch.bfloat16),
+                               ("w_lo", w_lo, (Cout, k * k * Cin), torch.bfloat16), ("scale", scale, (Cout,), torch.float32),
+                               ("shift", shift, (Cout,), torch.float32), ("residual", residual, (N, Ho, Wo, Cout), torch.float32),
+                               ("out", out, (N, Ho, Wo, Cout), torch.float32)):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != dt):
+            raise ValueError(f"conv2d_nhwc_f32: {name} must be a contiguous {shape} {dt} tensor (got {tuple(t.shape)}, strides "
+                             f"{t.stride()}, {t.dtype})")
+    _lib.check(_lib.load().avf_conv2d_nhwc_f32x3(_ptr(x), _ptr(w_hi), _ptr(w_lo), _ptr(scale), _ptr(shift), _ptr(residual),
+                                                 int(bool(relu)), int(k), int(stride), _ptr(out), N, H, W, Cin, Cout, _stream()),
+               "conv2d_nhwc_f32")
+    return out
+
+
 def avgpool_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[N, ..., C] fp32 or bf16 (NHWC map or [N, HW, C] tokens) -> [N, C] fp32, the mean over the middle axes (avf_avgpool_nhwc)"""
     _need_cuda(x, out)

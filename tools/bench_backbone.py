@@ -27,7 +27,15 @@ frames and the [64, 1, 64, 1001] mel maps of the audio stream, fp32 planes in, t
   whole    FrozenResFormer(backend="hip") with stem="torch" and with stem="hip" (the video shapes), FrozenAudioModel on both backends
            (the mel shape)
 Same windows, alternation and medians.  Per shape the JSON also holds the bytes the stem must move (x in once, out once) and the
-rate arm c reaches on them.  Writes <out-dir>/backbone_stem.json."""
+rate arm c reaches on them.  Writes <out-dir>/backbone_stem.json.
+
+    python tools/bench_backbone.py --conv-dtype f32 [--frames 1024 16] [--groups 7] [--calls 5] [--warmup 2]
+
+The parity form of the conv stages (conv_dtype="f32", csrc/conv_f32.hip: fp32 maps, three bf16 MFMA products per fp32 product)
+against the throughput form (conv_dtype="bf16"), both FrozenResFormer(backend="hip", stem="torch"), in one process, the arms
+alternated: the same three sections, then every distinct conv shape of the stages alone on avf_conv2d_nhwc (bf16 in, bf16 out)
+and on avf_conv2d_nhwc_f32x3, alternated per shape.  The errors are against arm a (backend="torch").  Writes
+<out-dir>/backbone_f32.json."""
 import argparse
 import copy
 import json
@@ -48,15 +56,19 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stem", action="store_true", help="time the stem arms instead (profiles/ab/backbone_stem.json)")
+    ap.add_argument("--conv-dtype", choices=("bf16", "f32"), default="bf16",
+                    help="f32: time the parity form of the conv stages against the bf16 form instead (profiles/ab/backbone_f32.json)")
     ap.add_argument("--name", default=None)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "ab"))
     args = ap.parse_args()
     if args.groups < 5:
         ap.error("--groups must be at least 5 (the result is a median)")
     if args.name is None:
-        args.name = "backbone_stem" if args.stem else "backbone_frozen"
+        args.name = "backbone_stem" if args.stem else "backbone_f32" if args.conv_dtype == "f32" else "backbone_frozen"
     if args.stem:
         return stem_main(args)
+    if args.conv_dtype == "f32":
+        return conv_dtype_main(args)
     import torch
     from torch.nn import functional as F
     import avformer_amd as A
@@ -274,6 +286,111 @@ def stem_main(args):
         json.dump(out, f, indent=1)
     for k, r in result.items():
         print(json.dumps({"shape": k, **{n: r[n] for n in r if n != "ms_per_call"}}))
+
+
+def conv_dtype_main(args):
+    import torch
+    import avformer_amd as A
+    from tools.ab_bench import box_id
+    from tools.bench_mel import shader_clock
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_backbone.py measures on the GPU; no device found")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    m_a = A.FrozenResFormer(backend="torch").to(dev).eval()
+    for p in m_a.parameters():
+        p.requires_grad_(False)
+    m16 = copy.deepcopy(m_a).set_backend("hip")
+    m32 = copy.deepcopy(m_a).set_backend("hip").set_conv_dtype("f32")
+
+    def median_ms(fn, n):
+        t = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) / n)
+        return statistics.median(t)
+
+    clock_before = shader_clock()
+    result = {}
+    with torch.no_grad():
+        for Bp in args.frames:
+            x = torch.randn(Bp, 3, args.size, args.size, device=dev)
+            h = m_a.stem(x)                                              # [B', 64, 28, 28]
+            f3 = m_a.layer3(m_a.layer2(m_a.layer1(h)))                   # [B', 256, 7, 7]
+            tok = f3.permute(0, 2, 3, 1).reshape(Bp, -1, f3.shape[1]).contiguous()
+            hw = tuple(f3.shape[2:])
+            arms = {"bf16_l123": lambda: m16.stages_to_tokens(h), "f32_l123": lambda: m32.stages_to_tokens(h),
+                    "bf16_tail": lambda: m16.tokens_to_features(tok, hw), "f32_tail": lambda: m32.tokens_to_features(tok, hw),
+                    "bf16_whole": lambda: m16(x), "f32_whole": lambda: m32(x)}
+            for fn in arms.values():
+                for _ in range(args.warmup):
+                    fn()
+            torch.cuda.synchronize()
+            want = {"l123": tok + m_a.pos_embedding[:, :tok.shape[1]], "tail": torch.flatten(m_a.avgpool(m_a.layer4(f3)), 1), "whole": m_a(x)}
+            err = {}
+            for k, fn in arms.items():
+                got = fn()
+                got = got[0] if isinstance(got, tuple) else got
+                err[k] = float((got.float() - want[k.split("_")[1]]).norm() / want[k.split("_")[1]].norm())
+            runs = {k: [] for k in arms}
+            for r in range(args.groups):
+                for name, fn in arms.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.calls):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    runs[name].append(round(e0.elapsed_time(e1) / args.calls, 5))
+                print(f"B'={Bp} group {r + 1}: " + "  ".join(f"{k} {v[-1]:.3f}" for k, v in runs.items()) + " ms", flush=True)
+            med = {k: statistics.median(v) for k, v in runs.items()}
+            shapes, seen = [], set()
+            for shp in stage_conv_shapes(m16, Bp, h.shape[2], h.shape[3]):
+                if shp in seen:
+                    continue
+                seen.add(shp)
+                N, H, W, Cin, Cout, k, s = shp
+                xi = torch.randn(N, H, W, Cin, device=dev)
+                xb = xi.bfloat16()
+                w = torch.randn(Cout, k * k * Cin, device=dev)
+                wb, wl = w.bfloat16(), (w - w.bfloat16().float()).bfloat16()
+                sc = torch.ones(Cout, device=dev)
+                o16 = A.ops.conv2d_nhwc(xb, wb, sc, sc, k, s, relu=True)
+                o32 = A.ops.conv2d_nhwc_f32(xi, (wb, wl), sc, sc, k, s, relu=True)
+                n = 20 if Bp <= 64 else 5
+                ms16, ms32 = [], []
+                for _ in range(3):                                       # alternated per shape
+                    ms16.append(median_ms(lambda: A.ops.conv2d_nhwc(xb, wb, sc, sc, k, s, relu=True, out=o16), n))
+                    ms32.append(median_ms(lambda: A.ops.conv2d_nhwc_f32(xi, (wb, wl), sc, sc, k, s, relu=True, out=o32), n))
+                ms16, ms32 = statistics.median(ms16), statistics.median(ms32)
+                flops = 2.0 * o16.numel() * k * k * Cin
+                shapes.append({"x": [N, H, W, Cin], "Cout": Cout, "k": k, "stride": s, "M": o16.numel() // Cout, "K": k * k * Cin,
+                               "tile": A.ops.conv_plan(N, H, W, Cin, Cout, k, s)["tile"], "bf16_ms": round(ms16, 5), "f32_ms": round(ms32, 5),
+                               "f32_over_bf16": round(ms32 / ms16, 3),
+                               "f32_mfma_fraction_of_bf16_peak": round(3 * flops / (ms32 * 1e-3) / PEAK_BF16, 4)})
+                del xi, xb, o16, o32
+            result[str(Bp)] = {"ms_per_call": runs, "median_ms_per_call": med,
+                               "spread_ms_max_minus_min": {k: round(max(v) - min(v), 5) for k, v in runs.items()},
+                               "f32_over_bf16": {s: round(med["f32_" + s] / med["bf16_" + s], 3) for s in ("l123", "tail", "whole")},
+                               "rel_fro_vs_torch_backend": err, "conv_shapes": shapes}
+            del x, h, f3, tok
+    out = {"name": args.name, "frame_counts": args.frames, "size": args.size, "box": box_id(), "clock_before": clock_before,
+           "clock_after": shader_clock(), "device": torch.cuda.get_device_name(0), "alternations": args.groups,
+           "calls_per_group": args.calls, "warmup_calls": args.warmup, "bf16_peak_flops_assumed": PEAK_BF16,
+           "launch": "eager, device events around the calls, inputs already on the device, torch.no_grad()", "frames": result}
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, args.name + ".json"), "w") as f:
+        json.dump(out, f, indent=1)
+    for Bp, r in result.items():
+        print(json.dumps({"frames": Bp, "median_ms_per_call": r["median_ms_per_call"], "f32_over_bf16": r["f32_over_bf16"],
+                          "rel_fro_vs_torch_backend": r["rel_fro_vs_torch_backend"]}))
+        for s in r["conv_shapes"]:
+            print(json.dumps(s))
 
 
 def stage_conv_shapes(model, Bp, H, W):
