@@ -15,8 +15,8 @@ hip backend runs no map/token permute on either side of ``spatial_transformer``.
 ``layer1`` reads: no torch compute op and no layout conversion between the front end's planes and the pooled features.
 
 ``conv_dtype=`` picks the hip backend's conv arithmetic.  ``"bf16"`` (default) is the throughput form above.  ``"f32"`` is the
-parity form, csrc/conv_f32.hip: every map between launches is fp32 and every fp32 product runs as three bf16 MFMA products
-(bf16x3, the arithmetic of ``compute_dtype="f32"``; ``set_f32_arithmetic`` does not reach the conv).  The stem kernel has no
+parity form, csrc/conv_f32.hip (the same kernel template, csrc/conv_kernel.hpp, with two-image operands): every map between
+launches is fp32 and every fp32 product runs as three bf16 MFMA products (bf16x3, the arithmetic of ``compute_dtype="f32"``; ``set_f32_arithmetic`` does not reach the conv).  The stem kernel has no
 parity form: in this mode the stem is the torch definition in fp32, followed by one NCHW -> NHWC fp32 conversion, and
 ``stem="hip"`` is refused.
 
@@ -163,13 +163,11 @@ class FrozenBasicBlock(nn.Module):
         is fp32 and so is every map, the output included (``out_dtype`` does not apply)"""
         _no_grad_or_raise(self, x, "FrozenBasicBlock")
         p = self._pack(x.device)
-        if self.conv_dtype == "f32":
-            h = ops.conv2d_nhwc_f32(x, *p[0], k=3, stride=self.stride, relu=True)
-            identity = x if self.downsample is None else ops.conv2d_nhwc_f32(x, *p[2], k=1, stride=self.stride)
-            return ops.conv2d_nhwc_f32(h, *p[1], k=3, stride=1, residual=identity, relu=True)
-        h = ops.conv2d_nhwc(x, *p[0], k=3, stride=self.stride, relu=True)
-        identity = x if self.downsample is None else ops.conv2d_nhwc(x, *p[2], k=1, stride=self.stride)
-        return ops.conv2d_nhwc(h, *p[1], k=3, stride=1, residual=identity, relu=True, out_dtype=out_dtype)
+        f32 = self.conv_dtype == "f32"
+        conv = ops.conv2d_nhwc_f32 if f32 else ops.conv2d_nhwc
+        h = conv(x, *p[0], k=3, stride=self.stride, relu=True)
+        identity = x if self.downsample is None else conv(x, *p[2], k=1, stride=self.stride)
+        return conv(h, *p[1], k=3, stride=1, residual=identity, relu=True, **({} if f32 else {"out_dtype": out_dtype}))
 
     def forward(self, x):
         if self.backend == "torch":
@@ -184,7 +182,7 @@ class _Stage(nn.Sequential):
 
     def forward_nhwc(self, x, out_dtype=torch.bfloat16):
         for i, blk in enumerate(self):
-            x = blk.forward_nhwc(x, out_dtype if i == len(self) - 1 else torch.bfloat16)
+            x = blk.forward_nhwc(x, out_dtype) if i == len(self) - 1 else blk.forward_nhwc(x)
         return x
 
 

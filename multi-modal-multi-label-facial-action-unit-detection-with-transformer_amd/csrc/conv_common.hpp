@@ -1,6 +1,7 @@
-// conv_common.hpp - what the two NHWC implicit-GEMM convolutions share (conv.hip: bf16 operands; conv_f32.hip: fp32 operands in
-// the bf16x3 parity arithmetic): the argument block, the LDS swizzle, the shape rules, the tile table and its dispatch rule, and
-// the small predicates of the entry points.  Everything has internal linkage: each source gets its own copy.
+// conv_common.hpp - the host side of the NHWC implicit-GEMM convolution (conv_kernel.hpp; conv.hip instantiates it with bf16
+// operands, conv_f32.hip with fp32 operands in the bf16x3 parity arithmetic): the argument block, the LDS swizzle, the shape
+// rules, the tile table and its dispatch rule, the operand checks of the entry points - and what stem.hip shares with them: the
+// small predicates and the BatchNorm fold.  Everything has internal linkage: each source gets its own copy.
 #pragma once
 #include "common.hpp"
 
@@ -12,12 +13,13 @@ constexpr int kConvBK = 32;        // one MFMA deep
 
 struct ConvArgs {
   const void* x;
-  const bf16* w;  // packed [Cout][K]
+  const bf16* w;  // packed [Cout][K]: the one bf16 image, or the hi image of the bf16x3 form
   const float *scale, *shift;
   const void* res;
   void* out;
   int N, H, W, Cin, Cout, k, stride, pad, Ho, Wo, K;
   int64_t M;
+  const bf16* w_lo;  // the lo image, as w (bf16x3 form; else null)
 };
 
 // A tile row is one chunk of one pixel / one output channel: 32 bf16 = four 16-byte pieces, four rows per 256-byte bank row.
@@ -62,7 +64,36 @@ bool apart(const void* p, size_t pn, const void* q, size_t qn) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return a + pn <= b || b + qn <= a;
 }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }  // n: a power of two
+
+// What the two conv entry points check before they launch, in this order: no null operand, the dtypes, the shape (conv_shape
+// fills a's geometry), 16-byte alignment, out apart from every input.  a comes with its pointers set; images = 2 needs w_lo.
+int conv_operands(const char* who, ConvArgs* a, int images, int x_dtype, int res_dtype, int out_dtype, int N, int H, int W, int Cin,
+                  int Cout, int k, int stride) {
+  AVF_REQUIRE(a->x && a->w && (images == 1 || a->w_lo) && a->scale && a->shift && a->out, "%s: null pointer", who);
+  AVF_REQUIRE(is_dtype(x_dtype) && is_dtype(out_dtype) && (!a->res || is_dtype(res_dtype)), "%s: bad dtype (x %d, out %d, residual %d)", who,
+              x_dtype, out_dtype, res_dtype);
+  AVF_TRY(conv_shape(who, N, H, W, Cin, Cout, k, stride, a));
+  const void* in[] = {a->x, a->w, a->w_lo, a->scale, a->shift, a->res};
+  const size_t wn = (size_t)Cout * a->K * 2, cn = (size_t)Cout * 4, on = (size_t)a->M * Cout * elt(out_dtype);
+  const size_t bytes[] = {(size_t)N * H * W * Cin * elt(x_dtype), wn, wn, cn, cn, (size_t)a->M * Cout * elt(res_dtype)};
+  bool al = aligned(a->out, 16), ap = true;
+  for (int i = 0; i < 6; ++i) {
+    al = al && aligned(in[i], 16);
+    ap = ap && (!in[i] || apart(a->out, on, in[i], bytes[i]));
+  }
+  AVF_REQUIRE(al, "%s: every operand must be 16-byte aligned", who);
+  AVF_REQUIRE(ap, "%s: out overlaps an input (a tile reads pixels other tiles write)", who);
+  return 0;
+}
+
+// eval-mode BatchNorm2d of channel c as one (scale, shift) pair: y = x * scale + shift, folded in fp64
+__device__ __forceinline__ void bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, double eps, int64_t c,
+                                        float* scale, float* shift) {
+  const double s = (double)gamma[c] / sqrt((double)var[c] + eps);
+  scale[c] = (float)s;
+  shift[c] = (float)((double)beta[c] - (double)mean[c] * s);
+}
 
 }  // namespace
 }  // namespace avf

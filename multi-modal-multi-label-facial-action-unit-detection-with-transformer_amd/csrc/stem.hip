@@ -21,7 +21,7 @@
 // a monotone rounding commute, so rounding before the max gives the bits of rounding after it - with -inf at the pixels outside
 // the Hc x Wc map, which therefore never win a max.  The pool reads 3 x 3 windows of it, eight channels (16 bytes of bf16) per
 // lane, and stores them: one rounding on the way to memory.
-#include "common.hpp"
+#include "conv_common.hpp"  // the entry points' predicates and the BatchNorm fold
 
 namespace avf {
 namespace {
@@ -236,11 +236,7 @@ __global__ __launch_bounds__(256) void stem_pack_weight_kernel(const float* w, c
   float v = 0.f;
   if (row < Cin * 7 && kx < 7) v = w[(co * Cin * 7 + row) * 7 + kx];
   wp[idx] = from_f32<bf16>(v);
-  if (idx < kStemCout) {
-    const double s = (double)gamma[idx] / sqrt((double)var[idx] + eps);
-    scale[idx] = (float)s;
-    shift[idx] = (float)((double)beta[idx] - (double)mean[idx] * s);
-  }
+  if (idx < kStemCout) bn_fold(gamma, beta, mean, var, eps, idx, scale, shift);
 }
 
 bool stem_cin_ok(int Cin) { return Cin == 1 || Cin == 3 || Cin == 4; }
@@ -285,14 +281,6 @@ int stem_launch_x(const StemArgs& a, int Cin, int out_dtype, hipStream_t s) {
   return out_dtype == AVF_F32 ? stem_launch_out<XT, float>(a, Cin, s) : stem_launch_out<XT, bf16>(a, Cin, s);
 }
 
-bool stem_is_dtype(int d) { return d == AVF_F32 || d == AVF_BF16; }
-size_t stem_elt(int d) { return d == AVF_F32 ? 4 : 2; }
-bool stem_apart(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a + pn <= b || b + qn <= a;
-}
-bool stem_aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 }  // namespace
 }  // namespace avf
 
@@ -323,7 +311,7 @@ extern "C" int avf_stem_pack_weight(const float* w, const float* gamma, const fl
   AVF_REQUIRE(stem_cin_ok(Cin), "stem_pack_weight: Cin=%d: the stem kernel takes 1, 3 or 4 input channels", Cin);
   AVF_REQUIRE(eps >= 0.0, "stem_pack_weight: eps %g", eps);
   const int Kp = stem_kp(Cin);
-  AVF_REQUIRE(stem_apart(w_packed, (size_t)Cout * Kp * 2, w, (size_t)Cout * Cin * 49 * 4) && stem_apart(scale, (size_t)Cout * 4, shift, (size_t)Cout * 4),
+  AVF_REQUIRE(apart(w_packed, (size_t)Cout * Kp * 2, w, (size_t)Cout * Cin * 49 * 4) && apart(scale, (size_t)Cout * 4, shift, (size_t)Cout * 4),
               "stem_pack_weight: an output overlaps an input or another output");
   stem_pack_weight_kernel<<<(unsigned)ceil_div((int64_t)Cout * Kp, 256), 256, 0, (hipStream_t)stream>>>(
       w, gamma, beta, running_mean, running_var, eps, (bf16*)w_packed, scale, shift, Cin, Kp);
@@ -333,15 +321,15 @@ extern "C" int avf_stem_pack_weight(const float* w, const float* gamma, const fl
 extern "C" int avf_stem_nchw(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
                              int out_dtype, int N, int Cin, int H, int W, void* stream) {
   AVF_REQUIRE(x && w_packed && scale && shift && out, "stem_nchw: null pointer");
-  AVF_REQUIRE(stem_is_dtype(x_dtype) && stem_is_dtype(out_dtype), "stem_nchw: bad dtype (x %d, out %d)", x_dtype, out_dtype);
+  AVF_REQUIRE(is_dtype(x_dtype) && is_dtype(out_dtype), "stem_nchw: bad dtype (x %d, out %d)", x_dtype, out_dtype);
   StemArgs a;
   AVF_TRY(stem_shape("stem_nchw", N, Cin, H, W, &a));
-  AVF_REQUIRE(stem_aligned(x, stem_elt(x_dtype)), "stem_nchw: x must be aligned to its element");
-  AVF_REQUIRE(stem_aligned(w_packed, 16) && stem_aligned(scale, 16) && stem_aligned(shift, 16) && stem_aligned(out, 16),
+  AVF_REQUIRE(aligned(x, elt(x_dtype)), "stem_nchw: x must be aligned to its element");
+  AVF_REQUIRE(aligned(w_packed, 16) && aligned(scale, 16) && aligned(shift, 16) && aligned(out, 16),
               "stem_nchw: w_packed, scale, shift and out must be 16-byte aligned");
-  const size_t xn = (size_t)N * Cin * H * W * stem_elt(x_dtype), on = (size_t)N * a.Hp * a.Wp * kStemCout * stem_elt(out_dtype);
-  AVF_REQUIRE(stem_apart(out, on, x, xn) && stem_apart(out, on, w_packed, (size_t)kStemCout * stem_kp(Cin) * 2) &&
-                  stem_apart(out, on, scale, (size_t)kStemCout * 4) && stem_apart(out, on, shift, (size_t)kStemCout * 4),
+  const size_t xn = (size_t)N * Cin * H * W * elt(x_dtype), on = (size_t)N * a.Hp * a.Wp * kStemCout * elt(out_dtype);
+  AVF_REQUIRE(apart(out, on, x, xn) && apart(out, on, w_packed, (size_t)kStemCout * stem_kp(Cin) * 2) &&
+                  apart(out, on, scale, (size_t)kStemCout * 4) && apart(out, on, shift, (size_t)kStemCout * 4),
               "stem_nchw: out overlaps an input (a tile reads pixels other tiles' outputs would cover)");
   a.x = x; a.w = (const bf16*)w_packed; a.scale = scale; a.shift = shift; a.out = out;
   const hipStream_t s = (hipStream_t)stream;

@@ -1242,21 +1242,28 @@ def token_mean_bwd(g: torch.Tensor, tokens: int, want_bf16: bool = False, want_c
     return dy, lo, cs
 
 
-# frozen ResNet stages (csrc/conv.hip) ---------------------------------------------------------------
-def conv_pack_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
-                     running_var: torch.Tensor, eps: float = 1e-5):
-    """nn.Conv2d weight [Cout, Cin, k, k] fp32 + BatchNorm2d's eval-mode statistics -> (w_packed [Cout, k*k*Cin] bf16 ordered
-    tap-major / channel-minor, scale [Cout], shift [Cout] fp32) for ``conv2d_nhwc`` (avf_conv_pack_weight)."""
+# frozen ResNet stages (csrc/conv.hip; csrc/conv_f32.hip: the same kernel, csrc/conv_kernel.hpp, in the parity arithmetic) --------
+def _conv_pack(images: int, w, gamma, beta, running_mean, running_var, eps):
+    """the body of ``conv_pack_weight`` (images = 1) and ``conv_pack_weight_f32`` (2): -> ([image, ...], scale, shift)"""
     _need_cuda(w, gamma, beta, running_mean, running_var)
     ts = [t.detach().contiguous() for t in (w, gamma, beta, running_mean, running_var)]
     assert all(t.dtype == torch.float32 for t in ts) and ts[0].dim() == 4 and ts[0].shape[2] == ts[0].shape[3]
     Cout, Cin, k, _ = ts[0].shape
     assert all(t.numel() == Cout for t in ts[1:])
-    wp = torch.empty((Cout, k * k * Cin), dtype=torch.bfloat16, device=w.device)
+    ws = [torch.empty((Cout, k * k * Cin), dtype=torch.bfloat16, device=w.device) for _ in range(images)]
     scale = torch.empty(Cout, dtype=torch.float32, device=w.device)
     shift = torch.empty(Cout, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().avf_conv_pack_weight(*[_ptr(t) for t in ts], float(eps), _ptr(wp), _ptr(scale), _ptr(shift), Cout, Cin, k,
-                                                _stream()), "conv_pack_weight")
+    fn, name = ((_lib.load().avf_conv_pack_weight, "conv_pack_weight") if images == 1 else
+                (_lib.load().avf_conv_pack_weight_f32x3, "conv_pack_weight_f32"))
+    _lib.check(fn(*[_ptr(t) for t in ts], float(eps), *[_ptr(t) for t in ws], _ptr(scale), _ptr(shift), Cout, Cin, k, _stream()), name)
+    return ws, scale, shift
+
+
+def conv_pack_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                     running_var: torch.Tensor, eps: float = 1e-5):
+    """nn.Conv2d weight [Cout, Cin, k, k] fp32 + BatchNorm2d's eval-mode statistics -> (w_packed [Cout, k*k*Cin] bf16 ordered
+    tap-major / channel-minor, scale [Cout], shift [Cout] fp32) for ``conv2d_nhwc`` (avf_conv_pack_weight)."""
+    (wp,), scale, shift = _conv_pack(1, w, gamma, beta, running_mean, running_var, eps)
     return wp, scale, shift
 
 
@@ -1274,46 +1281,49 @@ def conv_plan(N: int, H: int, W: int, Cin: int, Cout: int, k: int, stride: int =
     return dict(tile=out[0].value, tile_m=out[1].value, tile_n=out[2].value)
 
 
+def _conv2d(name: str, x, ws, scale, shift, k, stride, residual, relu, out, out_dtype):
+    """the body of ``conv2d_nhwc`` (ws = (w_packed,); the maps fp32 or bf16) and ``conv2d_nhwc_f32`` (ws = (w_hi, w_lo); the maps
+    fp32, checked): shapes / contiguity / dtypes, allocation, the call"""
+    f32 = len(ws) == 2
+    _need_cuda(x, *ws, scale, shift, residual, out)
+    N, H, W, Cin = x.shape
+    Cout = ws[0].shape[0]
+    Ho, Wo = conv_out_hw(H, W, k, stride)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), dtype=torch_dtype(out_dtype), device=x.device)
+    wnames = ("w_hi", "w_lo") if f32 else ("w_packed",)
+    for nm, t, shape, dt in ([("x", x, (N, H, W, Cin), torch.float32)] + [(nm, t, (Cout, k * k * Cin), torch.bfloat16) for nm, t in zip(wnames, ws)] +
+                             [("scale", scale, (Cout,), torch.float32), ("shift", shift, (Cout,), torch.float32),
+                              ("residual", residual, (N, Ho, Wo, Cout), torch.float32), ("out", out, (N, Ho, Wo, Cout), torch.float32)]):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or (f32 and t.dtype != dt)):
+            raise ValueError(f"{name}: {nm} must be a contiguous {shape}{f' {dt}' if f32 else ''} tensor (got {tuple(t.shape)}, strides "
+                             f"{t.stride()}, {t.dtype})")
+    assert ws[0].dtype == torch.bfloat16 and scale.dtype == shift.dtype == torch.float32
+    ptrs, geom = [_ptr(t) for t in (*ws, scale, shift, residual)], (N, H, W, Cin, Cout, _stream())
+    if f32:
+        rc = _lib.load().avf_conv2d_nhwc_f32x3(_ptr(x), *ptrs, int(bool(relu)), int(k), int(stride), _ptr(out), *geom)
+    else:
+        rc = _lib.load().avf_conv2d_nhwc(_ptr(x), avf_dtype(x.dtype), *ptrs, avf_dtype(residual.dtype) if residual is not None else F32,
+                                         int(bool(relu)), int(k), int(stride), _ptr(out), avf_dtype(out.dtype), *geom)
+    _lib.check(rc, name)
+    return out
+
+
 def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, k: int, stride: int = 1,
                 residual: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None,
                 out_dtype=torch.bfloat16) -> torch.Tensor:
     """relu?(conv(x, w) * scale + shift (+ residual)) on NHWC activations (avf_conv2d_nhwc): x [N, H, W, Cin] fp32 or bf16,
     w_packed / scale / shift from ``conv_pack_weight``, k = 3 (pad 1) or 1 (pad 0), stride 1 or 2; residual / out
     [N, Ho, Wo, Cout] fp32 or bf16.  Forward only."""
-    _need_cuda(x, w_packed, scale, shift, residual, out)
-    N, H, W, Cin = x.shape
-    Cout = w_packed.shape[0]
-    Ho, Wo = conv_out_hw(H, W, k, stride)
-    if out is None:
-        out = torch.empty((N, Ho, Wo, Cout), dtype=torch_dtype(out_dtype), device=x.device)
-    for name, t, shape in (("x", x, (N, H, W, Cin)), ("w_packed", w_packed, (Cout, k * k * Cin)), ("scale", scale, (Cout,)),
-                           ("shift", shift, (Cout,)), ("residual", residual, (N, Ho, Wo, Cout)), ("out", out, (N, Ho, Wo, Cout))):
-        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
-            raise ValueError(f"conv2d_nhwc: {name} must be a contiguous {shape} tensor (got {tuple(t.shape)}, strides {t.stride()})")
-    assert w_packed.dtype == torch.bfloat16 and scale.dtype == shift.dtype == torch.float32
-    _lib.check(_lib.load().avf_conv2d_nhwc(_ptr(x), avf_dtype(x.dtype), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(residual),
-                                           avf_dtype(residual.dtype) if residual is not None else F32, int(bool(relu)), int(k),
-                                           int(stride), _ptr(out), avf_dtype(out.dtype), N, H, W, Cin, Cout, _stream()), "conv2d_nhwc")
-    return out
+    return _conv2d("conv2d_nhwc", x, (w_packed,), scale, shift, k, stride, residual, relu, out, out_dtype)
 
 
-# ... in the parity arithmetic (csrc/conv_f32.hip)
 def conv_pack_weight_f32(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
                          running_var: torch.Tensor, eps: float = 1e-5):
     """``conv_pack_weight`` for ``conv2d_nhwc_f32``: -> ((w_hi, w_lo), scale, shift), w_hi = bf16(w) and w_lo = bf16(w - w_hi),
     each [Cout, k*k*Cin] bf16 tap-major / channel-minor; scale / shift [Cout] fp32 (avf_conv_pack_weight_f32x3)."""
-    _need_cuda(w, gamma, beta, running_mean, running_var)
-    ts = [t.detach().contiguous() for t in (w, gamma, beta, running_mean, running_var)]
-    assert all(t.dtype == torch.float32 for t in ts) and ts[0].dim() == 4 and ts[0].shape[2] == ts[0].shape[3]
-    Cout, Cin, k, _ = ts[0].shape
-    assert all(t.numel() == Cout for t in ts[1:])
-    w_hi = torch.empty((Cout, k * k * Cin), dtype=torch.bfloat16, device=w.device)
-    w_lo = torch.empty_like(w_hi)
-    scale = torch.empty(Cout, dtype=torch.float32, device=w.device)
-    shift = torch.empty(Cout, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().avf_conv_pack_weight_f32x3(*[_ptr(t) for t in ts], float(eps), _ptr(w_hi), _ptr(w_lo), _ptr(scale),
-                                                      _ptr(shift), Cout, Cin, k, _stream()), "conv_pack_weight_f32")
-    return (w_hi, w_lo), scale, shift
+    ws, scale, shift = _conv_pack(2, w, gamma, beta, running_mean, running_var, eps)
+    return tuple(ws), scale, shift
 
 
 def conv2d_nhwc_f32(x: torch.Tensor, w_split, scale: torch.Tensor, shift: torch.Tensor, k: int, stride: int = 1,
@@ -1323,23 +1333,7 @@ def conv2d_nhwc_f32(x: torch.Tensor, w_split, scale: torch.Tensor, shift: torch.
     products (bf16x3, oracle/bf16x3.py).  That is the convolution's one parity arithmetic: ``set_f32_arithmetic("f32")`` does not
     reach it.  Same shapes, tiles (``conv_plan``) and errors as ``conv2d_nhwc``.  Forward only."""
     w_hi, w_lo = w_split
-    _need_cuda(x, w_hi, w_lo, scale, shift, residual, out)
-    N, H, W, Cin = x.shape
-    Cout = w_hi.shape[0]
-    Ho, Wo = conv_out_hw(H, W, k, stride)
-    if out is None:
-        out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    for name, t, shape, dt in (("x", x, (N, H, W, Cin), torch.float32), ("w_hi", w_hi, (Cout, k * k * Cin), torch.bfloat16),
-                               ("w_lo", w_lo, (Cout, k * k * Cin), torch.bfloat16), ("scale", scale, (Cout,), torch.float32),
-                               ("shift", shift, (Cout,), torch.float32), ("residual", residual, (N, Ho, Wo, Cout), torch.float32),
-                               ("out", out, (N, Ho, Wo, Cout), torch.float32)):
-        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != dt):
-            raise ValueError(f"conv2d_nhwc_f32: {name} must be a contiguous {shape} {dt} tensor (got {tuple(t.shape)}, strides "
-                             f"{t.stride()}, {t.dtype})")
-    _lib.check(_lib.load().avf_conv2d_nhwc_f32x3(_ptr(x), _ptr(w_hi), _ptr(w_lo), _ptr(scale), _ptr(shift), _ptr(residual),
-                                                 int(bool(relu)), int(k), int(stride), _ptr(out), N, H, W, Cin, Cout, _stream()),
-               "conv2d_nhwc_f32")
-    return out
+    return _conv2d("conv2d_nhwc_f32", x, (w_hi, w_lo), scale, shift, k, stride, residual, relu, out, torch.float32)
 
 
 def avgpool_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

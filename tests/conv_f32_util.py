@@ -1,4 +1,4 @@
-"""fp64 references, bounds, cases and mutants for the parity-mode NHWC convolution (csrc/conv_f32.hip: conv_nhwc_f32x3_kernel).
+"""fp64 references, bounds, cases and mutants for the parity-mode NHWC convolution (csrc/conv_f32.hip: conv_nhwc_kernel<ConvBf16x3>).
 CPU only: tests/test_gpu_conv_f32.py feeds it what the device returned, tests/test_conv_f32_ref_cpu.py shows without a device that
 the two checks bite.  Built on tests/conv_util.py: its shapes, its gather (with the staging mutants), out_hw and MUTANTS.
 

@@ -1,6 +1,7 @@
 """fp64 reference, element-wise bounds, cases and mutants for the NHWC implicit-GEMM convolution and the NHWC average pool
-(csrc/conv.hip: conv_nhwc_bf16_kernel, avgpool_nhwc_kernel).  CPU only: tests/test_gpu_conv.py feeds it what the device
-returned, tests/test_conv_ref_cpu.py shows without a device that the bounds bite.
+(csrc/conv_kernel.hpp: conv_nhwc_kernel with bf16 operands; csrc/conv.hip: avgpool_nhwc_kernel).  The reference is CPU only:
+tests/test_gpu_conv.py feeds it what the device returned, tests/test_conv_ref_cpu.py shows without a device that the bounds bite.
+The guarded device views of the GPU tests (conv, parity conv, stem) are at the end.
 
 The operation (x rounded to bf16 first when it is fp32, as the kernel does while staging; w bf16):
     P[m, co] = sum over the taps (ky, kx) IN RANGE and ci of x[n, oy*s - pad + ky, ox*s - pad + kx, ci] * w[co, ky, kx, ci]
@@ -285,3 +286,20 @@ def pool_reference(x):
 def pool_simulate(x, mutant=None):
     HW = x.shape[1]
     return (x.double().sum(1) / (HW + 1 if mutant == "avgpool_wrong_count" else HW)).float()
+
+
+# ---- guarded device operands of the GPU tests -------------------------------------------------------
+SENTINEL = -24576.0  # exact in bf16
+GUARD = 64           # elements either side: keeps every unshifted view 16-byte aligned in both types
+
+
+def _inside(t, fill, shift=0):
+    """a device copy of t as a view into a parent that holds `fill` on both sides, starting `shift` elements further in"""
+    buf = torch.full((t.numel() + 2 * GUARD + shift,), fill, dtype=t.dtype, device="cuda")
+    view = buf[GUARD + shift:GUARD + shift + t.numel()].view(t.shape)
+    view.copy_(t)
+    return buf, view
+
+
+def _intact(what, buf, n):
+    assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all()), what + ": a write outside the output"

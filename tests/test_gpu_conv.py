@@ -17,11 +17,10 @@ import pytest
 import torch
 
 import conv_util as cu
+from conv_util import SENTINEL, _inside, _intact
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -24576.0  # exact in bf16
-GUARD = 64           # elements either side: keeps every view 16-byte aligned in both types
 REACHED = set()
 
 
@@ -30,18 +29,6 @@ def ops():
     import avformer_amd as A
     assert A.ops.device_ok()
     return A.ops
-
-
-def _inside(t, fill):
-    """a device copy of t as a view into a parent that holds `fill` on both sides"""
-    buf = torch.full((t.numel() + 2 * GUARD,), fill, dtype=t.dtype, device="cuda")
-    view = buf[GUARD:GUARD + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
-
-
-def _intact(what, buf, n):
-    assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all()), what + ": a write outside the output"
 
 
 @pytest.mark.parametrize("case", cu.CASES, ids=[c["id"] for c in cu.CASES])

@@ -15,12 +15,11 @@ import torch
 
 import conv_f32_util as fu
 import conv_util as cu
+from conv_util import GUARD, SENTINEL, _inside
 from oracle.bf16x3 import split
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -24576.0
-GUARD = 64           # elements either side: keeps every view 16-byte aligned in both types
 REACHED = set()
 
 
@@ -29,14 +28,6 @@ def ops():
     import avformer_amd as A
     assert A.ops.device_ok()
     return A.ops
-
-
-def _inside(t, fill):
-    """a device copy of t as a view into a parent that holds `fill` on both sides"""
-    buf = torch.full((t.numel() + 2 * GUARD,), fill, dtype=t.dtype, device="cuda")
-    view = buf[GUARD:GUARD + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
 
 
 @pytest.mark.parametrize("case", fu.CASES, ids=[c["id"] for c in fu.CASES])

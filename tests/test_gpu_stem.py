@@ -16,11 +16,10 @@ import pytest
 import torch
 
 import stem_util as su
+from conv_util import GUARD, SENTINEL, _inside
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -24576.0  # exact in bf16
-GUARD = 64           # elements either side: keeps the aligned views 16-byte aligned in both types
 ODD = 3              # x starts this many elements further in
 
 
@@ -29,14 +28,6 @@ def ops():
     import avformer_amd as A
     assert A.ops.device_ok()
     return A.ops
-
-
-def _inside(t, fill, shift=0):
-    """a device copy of t as a view into a parent that holds `fill` on both sides"""
-    buf = torch.full((t.numel() + 2 * GUARD + shift,), fill, dtype=t.dtype, device="cuda")
-    view = buf[GUARD + shift:GUARD + shift + t.numel()].view(t.shape)
-    view.copy_(t)
-    return buf, view
 
 
 def _packed(ops, inp):
