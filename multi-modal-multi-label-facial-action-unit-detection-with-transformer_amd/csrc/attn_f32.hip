@@ -1,5 +1,6 @@
 // attn_f32.hip - parity-mode attention core (fp32 VALU, flash-style: never materialises [B,H,N,N]).
-// (Round 5: fp32 storage without a mask at dim_head 32 / 64 - the parity mode's own calls - runs on attn_f32_mfma.hip instead;
+// (fp32 storage without a mask and with raw q at dim_head 32 / 64 / 128 - the parity mode's own calls - runs on the MFMA kernels of
+//  attn_parity_kernel.hpp instead (attn_f32x3.hip, attn_f32_mfma.hip);
 //  these kernels keep the masked calls, bf16 storage and the other head widths: 8, 16, 32, 64 and 128.)
 //
 // Reference: models/heads.py:222-237 -  dots = q k^T * dh^-0.5 ; softmax(dim=-1) ; out = attn v ;
@@ -335,8 +336,8 @@ int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N,
   TimingScope ts(KC_ATTN_FWD, 4.0 * B * H * (double)N * N * dh, 4.0 * 4.0 * B * N * H * dh, s);
   if (attn_f32x3_ok(dtype, dh, keep, H, qkv, o, q_prescaled))  // round 6: three bf16 products per fp32 product (attn_f32x3.hip)
     return attn_fwd_f32x3((const float*)qkv, (float*)o, lse2, B, N, H, s);
-  if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, o))  // fp32 storage, no mask, dim_head 32 / 64: the fp32 matrix pipe
-    return attn_fwd_f32_mfma((const float*)qkv, (float*)o, lse2, B, N, H, dh, s, q_prescaled);
+  if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, o, q_prescaled))  // fp32 storage, no mask, raw q, dim_head 32 / 64 / 128: the fp32 matrix pipe
+    return attn_fwd_f32_mfma((const float*)qkv, (float*)o, lse2, B, N, H, dh, s);
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
   return with_vec_variant(dh, dtype, kp != nullptr, "attn_fwd_f32", [&](auto d, auto t, auto masked) {
@@ -362,8 +363,8 @@ int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, con
   if (attn_f32x3_ok(dtype, dh, keep, H, qkv, d_o, q_prescaled) && ((uintptr_t)dqkv & 15) == 0 && ((uintptr_t)o & 15) == 0)
     return attn_bwd_f32x3((const float*)qkv, (const float*)o, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, s);
   AVF_TRY(attn_delta(dtype, o, d_o, delta, B, N, H, dh, s));
-  if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, d_o) && ((uintptr_t)dqkv & 15) == 0)
-    return attn_bwd_f32_mfma((const float*)qkv, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, dh, s, q_prescaled);
+  if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, d_o, q_prescaled) && ((uintptr_t)dqkv & 15) == 0)
+    return attn_bwd_f32_mfma((const float*)qkv, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, dh, s);
   const uint8_t* kp = (const uint8_t*)keep;
   const int qs = q_prescaled ? 1 : 0;
   return with_vec_variant(dh, dtype, kp != nullptr, "attn_bwd_f32", [&](auto d, auto t, auto masked) {

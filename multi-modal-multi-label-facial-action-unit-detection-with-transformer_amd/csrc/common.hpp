@@ -638,11 +638,11 @@ int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s);
 
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
 // fp32-arithmetic attention on fp32 / bf16 storage with the optional token mask keep [B, N] (bytes, 1 = kept; heads.py:225-232)
-// parity-mode attention on the fp32 matrix pipe (attn_f32_mfma.hip): fp32 storage, no mask, dim_head 32 / 64
-bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other);
-int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled);
+// parity-mode attention on the fp32 matrix pipe (attn_f32_mfma.hip): fp32 storage, no mask, dim_head 32 / 64 / 128, raw q
+bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
+int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
 int attn_bwd_f32_mfma(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, int B, int N, int H,
-                      int dh, hipStream_t s, bool q_prescaled);
+                      int dh, hipStream_t s);
 // parity-mode attention with three bf16 products per fp32 product (attn_f32x3.hip): fp32 storage, no mask, dim_head 64, raw q
 bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
 int attn_fwd_f32x3(const float* qkv, float* o, float* lse2, int B, int N, int H, hipStream_t s);

@@ -12,6 +12,7 @@
 // 32-deep chunk of one pixel is 32 consecutive channels of ONE tap: in range (two or four 16-byte loads) or padding (zeros
 // written to LDS by index - no load is issued, nothing outside the input is read).
 #pragma once
+#include "bf16x3.hpp"
 #include "conv_common.hpp"
 
 namespace avf {
@@ -49,21 +50,16 @@ struct ConvBf16<float> : ConvRawF8 {
   }
 };
 
-// gemm_f32.hip's split2: two fp32 -> the packed hi pair and the packed lo pair (v - hi is exact in fp32)
-__device__ __forceinline__ void conv_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pack_bf16x2(a, b);
-  lo = pack_bf16x2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
 struct ConvBf16x3 : ConvRawF8 {
   using X = float;
   static constexpr int IMAGES = 2;  // hi, lo
   template <int IM>
   __device__ __forceinline__ uint4 image() const {
     uint32_t h[4], l[4];
-    conv_split2(a.x, a.y, h[0], l[0]);
-    conv_split2(a.z, a.w, h[1], l[1]);
-    conv_split2(b.x, b.y, h[2], l[2]);
-    conv_split2(b.z, b.w, h[3], l[3]);
+    split2(a.x, a.y, h[0], l[0]);
+    split2(a.z, a.w, h[1], l[1]);
+    split2(b.x, b.y, h[2], l[2]);
+    split2(b.z, b.w, h[3], l[3]);
     return IM ? make_uint4(l[0], l[1], l[2], l[3]) : make_uint4(h[0], h[1], h[2], h[3]);
   }
 };

@@ -392,7 +392,9 @@ def _attn_ref(qkv, B, N, H, dh, d_o=None):
 
 
 @pytest.mark.parametrize("B,N,H,dh", [(2, 7, 4, 8), (1, 64, 2, 32), (2, 49, 8, 32), (3, 17, 8, 64), (2, 130, 3, 64),
-                                      (1, 324, 2, 64), (2, 12, 8, 16)])
+                                      (1, 324, 2, 64), (2, 12, 8, 16),
+                                      # the MFMA kernels' 32-row tile edge and 64-row workgroup edge
+                                      (1, 1, 2, 64), (1, 31, 2, 64), (1, 33, 2, 64), (1, 65, 2, 64), (2, 33, 2, 32)])
 def test_attention_f32(ops, f32_arith, B, N, H, dh):
     g = torch.Generator().manual_seed(B * 100 + N + dh)
     qkv = torch.randn(B * N, 3 * H * dh, generator=g)
