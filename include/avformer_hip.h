@@ -863,7 +863,20 @@ int avf_conv2d_nhwc_f32x3(const float* x, const void* w_hi, const void* w_lo, co
  *     w_packed / scale / shift; out may not overlap an input.  bf16 products accumulate in fp32 (v_mfma_f32_16x16x32_bf16); the
  *     epilogue and the max are fp32 arithmetic with one rounding per stored value.  Every global index is 64-bit.
  *   avf_stem_plan: the tile of POOLED outputs (of one image) a workgroup owns for this shape: *tile_h x *tile_w.  It computes the
- *     (2 tile_h + 1) x (2 tile_w + 1) conv pixels the tile needs itself (halo recompute).  Same argument checks as the launch. */
+ *     (2 tile_h + 1) x (2 tile_w + 1) conv pixels the tile needs itself (halo recompute).  Same argument checks as the launch.
+ * The pool has a second geometry, that of the frozen VGGFace2 ResNet-50 (vggformer.py:71: MaxPool2d(3, 2, padding=0,
+ * ceil_mode=True)), picked by pool_mode:
+ *   AVF_STEM_POOL_PAD1 (0)  3x3 / 2 / pad 1, floor: windows start at 2 p - 1, Hp = (Hc - 1) / 2 + 1.  What avf_stem_nchw runs.
+ *   AVF_STEM_POOL_CEIL (1)  3x3 / 2 / pad 0, ceil_mode: windows start at 2 p, Hp = (Hc - 2) / 2 + 1 (torch's max_pool2d rule); a
+ *     window that hangs over the bottom / right edge of the conv map takes the max over the pixels inside the map.  torch has no
+ *     output for a conv map smaller than 2 x 2: H < 3 or W < 3 is an error that says so.
+ *   avf_stem_nchw_pool: avf_stem_nchw with the pool geometry as an argument (a template parameter of the same kernel: the tile,
+ *     the packed image and every other contract above are unchanged; mode 0 IS avf_stem_nchw, bit for bit).  Any other pool_mode
+ *     is an error that names the two.
+ *   avf_stem_out_hw: host only, no device call: the shape rule the launch itself acts on - *Hc x *Wc the conv map, *Hp x *Wp the
+ *     pooled map of an H x W image under pool_mode.  Same errors as the launch for the mode and the sizes. */
+#define AVF_STEM_POOL_PAD1 0
+#define AVF_STEM_POOL_CEIL 1
 int avf_stem_packed_k(int Cin);
 int avf_stem_pack_weight(const float* w, const float* gamma, const float* beta, const float* running_mean,
                          const float* running_var, double eps, void* w_packed, float* scale, float* shift, int Cout, int Cin,
@@ -871,6 +884,9 @@ int avf_stem_pack_weight(const float* w, const float* gamma, const float* beta, 
 int avf_stem_nchw(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
                   int out_dtype, int N, int Cin, int H, int W, void* stream);
 int avf_stem_plan(int N, int Cin, int H, int W, int* tile_h, int* tile_w);
+int avf_stem_nchw_pool(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
+                       int out_dtype, int N, int Cin, int H, int W, int pool_mode, void* stream);
+int avf_stem_out_hw(int H, int W, int pool_mode, int* Hc, int* Wc, int* Hp, int* Wp);
 
 /* test aid: the keep/(1-p) factors (0 or 1/(1-p_eff)) dropout site `site` (0 after to_out, 1 after GELU, 2 after
  * net.3) of layer `layer_index` applies to a [rows, cols] activation, as fp32 [rows, cols] (cols % 4 == 0). */

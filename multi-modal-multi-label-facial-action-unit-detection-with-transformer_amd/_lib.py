@@ -16,6 +16,7 @@ F32, BF16 = 0, 1
 EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
 CLIP_CTHW, CLIP_TCHW = 0, 1
 WAVE_F32, WAVE_I16 = 0, 1
+STEM_POOL_PAD1, STEM_POOL_CEIL = 0, 1
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -159,6 +160,8 @@ SIGNATURES = {
     "avf_stem_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _vp]),
     "avf_stem_nchw": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _vp]),
     "avf_stem_plan": (_int, [_int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "avf_stem_nchw_pool": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
+    "avf_stem_out_hw": (_int, [_int, _int, _int] + [C.POINTER(C.c_int)] * 4),
     "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
     "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

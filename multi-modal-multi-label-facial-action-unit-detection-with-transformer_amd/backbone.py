@@ -85,26 +85,17 @@ def to_nhwc(x: torch.Tensor, channels: Optional[int] = None, dtype=torch.bfloat1
     return x.to(dtype).contiguous()
 
 
-class FrozenBasicBlock(nn.Module):
-    """``BasicBlock`` (vformer.py:128-166) in eval mode: ``conv1``, ``bn1``, ``conv2``, ``bn2``, ``downsample.0``, ``downsample.1``
-    are ordinary ``nn.Conv2d`` / ``nn.BatchNorm2d`` children with the reference's state_dict keys and shapes.
-    ``forward`` takes and returns NCHW fp32 with either backend; ``forward_nhwc`` is the hip backend's native form (two launches, or
-    three with a downsample).  The packed bf16 weights and folded BatchNorm are rebuilt whenever a parameter or buffer changes
-    (version counters, and a ``load_state_dict`` hook); writes through ``.data`` bypass the counters: call ``refresh_weights()``.
-
-    ``conv_dtype="f32"`` (hip backend) is the parity form (csrc/conv_f32.hip): every map stays fp32 and every fp32 product runs
-    as three bf16 MFMA products (bf16x3), weights packed as a hi and a lo bf16 image.  ``"bf16"`` (default) launches what it
-    always launched."""
+class _FrozenBlock(nn.Module):
+    """What the frozen residual blocks share (``FrozenBasicBlock`` here, ``vggface2.FrozenBottleneck``): eval-mode BatchNorm, the
+    packed conv images of the hip backend - one (weights, scale, shift) per (conv, bn) pair of ``_pairs()``, channels
+    zero-padded to 32, in the arithmetic ``conv_dtype`` names - their cache (version counters, a ``load_state_dict`` hook,
+    ``refresh_weights``), ``set_conv_dtype``, the forward-only guard and the NCHW fp32 ``forward`` around ``forward_nhwc``.  A
+    subclass sets ``inplanes`` / ``planes`` / ``stride`` / ``downsample`` and defines ``_pairs``, ``_forward_torch`` and
+    ``_forward_convs``."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, backend="torch", conv_dtype="bf16"):
+    def __init__(self, backend="torch", conv_dtype="bf16"):
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.downsample = downsample
-        self.stride, self.inplanes, self.planes = stride, inplanes, planes
         self.backend = _check_backend(backend)
         self.conv_dtype = _check_conv_dtype(conv_dtype)
         self._packed = None
@@ -112,19 +103,6 @@ class FrozenBasicBlock(nn.Module):
     @staticmethod
     def _bn(x, bn):
         return F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
-
-    def _forward_torch(self, x):
-        out = F.relu(self._bn(self.conv1(x), self.bn1))
-        out = self._bn(self.conv2(out), self.bn2)
-        identity = x if self.downsample is None else self._bn(self.downsample[0](x), self.downsample[1])
-        return F.relu(out + identity)
-
-    # ---- hip ------------------------------------------------------------------------------------
-    def _pairs(self):
-        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)]
-        if self.downsample is not None:
-            pairs.append((self.downsample[0], self.downsample[1]))
-        return pairs
 
     def _state_key(self, device):
         ts = [t for conv, bn in self._pairs() for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
@@ -148,7 +126,7 @@ class FrozenBasicBlock(nn.Module):
             for conv, bn in self._pairs():
                 w, ts = conv.weight.detach(), [t.detach() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
                 if not w.is_cuda:
-                    raise RuntimeError("FrozenBasicBlock(backend='hip'): parameters must be on the MI355X (module.to('cuda')); "
+                    raise RuntimeError(f"{type(self).__name__}(backend='hip'): parameters must be on the MI355X (module.to('cuda')); "
                                        "there is no CPU fallback")
                 co, ci = _pad_to(w.shape[0]), _pad_to(w.shape[1])
                 if (co, ci) != tuple(w.shape[:2]):  # zero weights, gamma = beta = mean = 0, var = 1: the padded channels stay 0
@@ -159,22 +137,59 @@ class FrozenBasicBlock(nn.Module):
         return self._packed[1]
 
     def forward_nhwc(self, x, out_dtype=torch.bfloat16):
-        """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(planes)] in ``out_dtype``; with ``conv_dtype="f32"`` x
-        is fp32 and so is every map, the output included (``out_dtype`` does not apply)"""
-        _no_grad_or_raise(self, x, "FrozenBasicBlock")
-        p = self._pack(x.device)
+        """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(expansion * planes)] in ``out_dtype``; with
+        ``conv_dtype="f32"`` x is fp32 and so is every map, the output included (``out_dtype`` does not apply)"""
+        _no_grad_or_raise(self, x, type(self).__name__)
         f32 = self.conv_dtype == "f32"
-        conv = ops.conv2d_nhwc_f32 if f32 else ops.conv2d_nhwc
-        h = conv(x, *p[0], k=3, stride=self.stride, relu=True)
-        identity = x if self.downsample is None else conv(x, *p[2], k=1, stride=self.stride)
-        return conv(h, *p[1], k=3, stride=1, residual=identity, relu=True, **({} if f32 else {"out_dtype": out_dtype}))
+        return self._forward_convs(x, self._pack(x.device), ops.conv2d_nhwc_f32 if f32 else ops.conv2d_nhwc,
+                                   {} if f32 else {"out_dtype": out_dtype})
 
     def forward(self, x):
         if self.backend == "torch":
             return self._forward_torch(x)
         ops._need_cuda(x)
         y = self.forward_nhwc(to_nhwc(x, _pad_to(self.inplanes), _map_dtype(self.conv_dtype)), out_dtype=torch.float32)
-        return y[..., :self.planes].permute(0, 3, 1, 2).contiguous()
+        return y[..., :self.expansion * self.planes].permute(0, 3, 1, 2).contiguous()
+
+
+class FrozenBasicBlock(_FrozenBlock):
+    """``BasicBlock`` (vformer.py:128-166) in eval mode: ``conv1``, ``bn1``, ``conv2``, ``bn2``, ``downsample.0``, ``downsample.1``
+    are ordinary ``nn.Conv2d`` / ``nn.BatchNorm2d`` children with the reference's state_dict keys and shapes.
+    ``forward`` takes and returns NCHW fp32 with either backend; ``forward_nhwc`` is the hip backend's native form (two launches, or
+    three with a downsample).  The packed bf16 weights and folded BatchNorm are rebuilt whenever a parameter or buffer changes
+    (version counters, and a ``load_state_dict`` hook); writes through ``.data`` bypass the counters: call ``refresh_weights()``.
+
+    ``conv_dtype="f32"`` (hip backend) is the parity form (csrc/conv_f32.hip): every map stays fp32 and every fp32 product runs
+    as three bf16 MFMA products (bf16x3), weights packed as a hi and a lo bf16 image.  ``"bf16"`` (default) launches what it
+    always launched."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, backend="torch", conv_dtype="bf16"):
+        super().__init__(backend, conv_dtype)
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride, self.inplanes, self.planes = stride, inplanes, planes
+
+    def _forward_torch(self, x):
+        out = F.relu(self._bn(self.conv1(x), self.bn1))
+        out = self._bn(self.conv2(out), self.bn2)
+        identity = x if self.downsample is None else self._bn(self.downsample[0](x), self.downsample[1])
+        return F.relu(out + identity)
+
+    # ---- hip ------------------------------------------------------------------------------------
+    def _pairs(self):
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)]
+        if self.downsample is not None:
+            pairs.append((self.downsample[0], self.downsample[1]))
+        return pairs
+
+    def _forward_convs(self, x, p, conv, last):
+        h = conv(x, *p[0], k=3, stride=self.stride, relu=True)
+        identity = x if self.downsample is None else conv(x, *p[2], k=1, stride=self.stride)
+        return conv(h, *p[1], k=3, stride=1, residual=identity, relu=True, **last)
 
 
 class _Stage(nn.Sequential):
@@ -190,8 +205,11 @@ class _HipStem:
     """``conv1`` - ``bn1`` - relu - ``maxpool`` of a ResNet (children ``conv1`` 7x7 / 2 / pad 3 with 1, 3 or 4 input channels,
     ``bn1``, ``maxpool`` 3x3 / 2 / pad 1) in both forms: ``stem`` is the definition in torch ops, ``stem_nhwc`` the one launch of
     csrc/stem.hip.  The packed stem image follows ``conv1`` / ``bn1`` as ``FrozenBasicBlock._pack`` follows its pairs: version
-    counters, and a ``load_state_dict`` hook; writes through ``.data`` bypass the counters: call ``refresh_weights()``."""
+    counters, and a ``load_state_dict`` hook; writes through ``.data`` bypass the counters: call ``refresh_weights()``.
+    ``_stem_pool`` names the geometry of ``maxpool`` for the kernel (``ops.stem_nchw``'s ``pool``): ``"pad1"`` here, ``"ceil"``
+    for the pad 0 / ceil_mode pool of ``vggface2.FrozenVGGFace2``."""
     _stem_packed = None
+    _stem_pool = "pad1"
 
     def stem(self, x):
         """conv1 - bn1 - relu - maxpool (vformer.py:238-241), eval-mode BatchNorm, torch ops: NCHW fp32 in and out"""
@@ -200,7 +218,7 @@ class _HipStem:
     def refresh_weights(self):
         self._stem_packed = None
         for m in self.modules():
-            if isinstance(m, FrozenBasicBlock):
+            if isinstance(m, _FrozenBlock):
                 m.refresh_weights()
 
     def _load_from_state_dict(self, *args, **kwargs):
@@ -220,7 +238,7 @@ class _HipStem:
     def stem_nhwc(self, x):
         """x [N, Cin, H, W] fp32 or bf16 planes -> [N, Hp, Wp, 64] NHWC bf16, what ``layer1.forward_nhwc`` reads (ops.stem_nchw)"""
         ops._need_cuda(x)
-        return ops.stem_nchw(x.contiguous(), *self._stem_pack(x.device))
+        return ops.stem_nchw(x.contiguous(), *self._stem_pack(x.device), pool=self._stem_pool)
 
 
 class FrozenResFormer(_HipStem, ResFormerTokens):
@@ -274,7 +292,7 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
         _check_conv_dtype(self.conv_dtype, stem)
         self.backend, self.stem_backend = backend, stem
         for m in self.modules():
-            if isinstance(m, FrozenBasicBlock):
+            if isinstance(m, _FrozenBlock):
                 m.backend = backend
         return self
 
@@ -282,7 +300,7 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
         """``"bf16"`` / ``"f32"``: the arithmetic of the hip backend's conv stages; the packed images are rebuilt on the next call"""
         self.conv_dtype = _check_conv_dtype(conv_dtype, self.stem_backend)
         for m in self.modules():
-            if isinstance(m, FrozenBasicBlock):
+            if isinstance(m, _FrozenBlock):
                 m.set_conv_dtype(conv_dtype)
         return self
 
@@ -373,14 +391,14 @@ class FrozenAudioModel(nn.Module):
     def set_conv_dtype(self, conv_dtype):
         self.conv_dtype = self.resnet.conv_dtype = _check_conv_dtype(conv_dtype)
         for m in self.modules():
-            if isinstance(m, FrozenBasicBlock):
+            if isinstance(m, _FrozenBlock):
                 m.set_conv_dtype(conv_dtype)
         return self
 
     def set_backend(self, backend):
         self.backend = self.resnet.backend = _check_backend(backend)
         for m in self.modules():
-            if isinstance(m, FrozenBasicBlock):
+            if isinstance(m, _FrozenBlock):
                 m.backend = backend
         return self
 

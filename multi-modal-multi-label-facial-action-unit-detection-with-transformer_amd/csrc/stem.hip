@@ -1,13 +1,17 @@
 // stem.hip - the frozen ResNet stem in front of layer1 (vformer.py:238-241; audio.py:22-39 with one input channel), forward only:
-//   stem_nchw_kernel         conv 7x7 / stride 2 / pad 3 -> folded eval-mode BatchNorm -> ReLU -> maxpool 3x3 / stride 2 / pad 1 in
-//                            one launch: NCHW planes (fp32 or bf16, Cin = 1 / 3 / 4) in, NHWC [N, Hp, Wp, 64] out - what layer1 reads
+//   stem_nchw_kernel         conv 7x7 / stride 2 / pad 3 -> folded eval-mode BatchNorm -> ReLU -> maxpool 3x3 / stride 2 in one
+//                            launch: NCHW planes (fp32 or bf16, Cin = 1 / 3 / 4) in, NHWC [N, Hp, Wp, 64] out - what layer1 reads.
+//                            The pool is pad 1 / floor (AVF_STEM_POOL_PAD1: vformer.py:241, torchvision's ResNet) or pad 0 /
+//                            ceil_mode (AVF_STEM_POOL_CEIL: VGGFace2's ResNet-50, vggformer.py:71)
 //   stem_pack_weight_kernel  nn.Conv2d's [64, Cin, 7, 7] fp32 weight -> the [64, Kp] bf16 image below, BatchNorm2d's running
 //                            statistics -> one (scale, shift) pair per channel
 //
 // A workgroup owns a 7 x 7 tile of POOLED outputs of one image (28 x 28 pooled pixels of a 112 x 112 frame are 4 x 4 tiles).
-// The tile needs the 15 x 15 conv pixels (2 * py0 - 1 .. 2 * py0 + 13) and those the 35 x 35 input pixels from 4 * py0 - 5 on,
-// of every channel: the patch is staged in LDS as bf16, zero where it leaves the image (no load is issued there).  The halo
-// conv pixels are recomputed by the neighbouring tiles (225 / 196 = 1.15 x the convolution) so that no tile reads another's.
+// The tile needs the 15 x 15 conv pixels (2 * py0 - pad .. 2 * py0 - pad + 14, pad the pool's padding: 1 or 0) and those the
+// 35 x 35 input pixels from 4 * py0 - 2 * pad - 3 on (-5 or -3 at the image corner), of every channel: only these two origins
+// depend on the pool geometry, a template parameter of the kernel (PAD; the pad-1 instantiation is the kernel as it was).  The
+// patch is staged in LDS as bf16, zero where it leaves the image (no load is issued there).  The halo conv pixels are recomputed
+// by the neighbouring tiles (225 / 196 = 1.15 x the convolution) so that no tile reads another's.
 //
 // GEMM view of the convolution: rows = the 64 channels (the MFMA's A operand), columns = the tile's 225 conv pixels in 15
 // fragments of 16 (the B operand), reduction ordered (ci, ky, kx padded to 8): the eight k-values of a lane are eight
@@ -46,6 +50,7 @@ struct StemArgs {
   const float *scale, *shift;
   void* out;
   int N, H, W, Hc, Wc, Hp, Wp, tiles_y, tiles_x;
+  int pad;        // the pool's padding: 1 (AVF_STEM_POOL_PAD1) or 0 (AVF_STEM_POOL_CEIL), the kernel's PAD; Hp, Wp follow the mode's size rule
   int64_t tiles;  // N * tiles_y * tiles_x
 };
 
@@ -74,8 +79,9 @@ struct MapIO<float> {
   }
 };
 
-template <typename XT, typename OT, int CIN>
+template <typename XT, typename OT, int CIN, int PAD>
 __global__ __launch_bounds__(kStemThreads) __attribute__((amdgpu_waves_per_eu(2))) void stem_nchw_kernel(const StemArgs a) {
+  static_assert(PAD == 0 || PAD == 1, "the pool's padding");
   constexpr int KP = stem_kp(CIN), NS = KP / 32, ROWS = CIN * 7;  // k-steps; the (ci, ky) rows that exist
   constexpr int MAPW = kStemCout + kStemMapPad;
   constexpr int PLANE = kStemPH * kStemPW;
@@ -119,7 +125,7 @@ __global__ __launch_bounds__(kStemThreads) __attribute__((amdgpu_waves_per_eu(2)
     const int64_t n = t / (a.tiles_y * a.tiles_x);
     const int tr = (int)(t - n * (a.tiles_y * a.tiles_x));
     const int ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-    const int iy0 = 4 * ty * kStemTH - 5, ix0 = 4 * tx * kStemTW - 5;  // the first input pixel: 2 * (2 * py0 - 1) - 3
+    const int iy0 = 4 * ty * kStemTH - 2 * PAD - 3, ix0 = 4 * tx * kStemTW - 2 * PAD - 3;  // the first input pixel: 2 * (2 * py0 - PAD) - 3
 #pragma unroll
     for (int i = 0; i < TURNS; ++i) {
       const int q = tid + i * kStemThreads;
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(kStemThreads) __attribute__((amdgpu_waves_per_eu(2)
     const int tr = (int)(t - n * (a.tiles_y * a.tiles_x));
     const int ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
     const int py0 = ty * kStemTH, px0 = tx * kStemTW;
-    const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;      // the tile's first conv pixel
+    const int cy0 = 2 * py0 - PAD, cx0 = 2 * px0 - PAD;      // the tile's first conv pixel
 
     if (!PREFETCH) fetch(t);
     stash();
@@ -201,7 +207,9 @@ __global__ __launch_bounds__(kStemThreads) __attribute__((amdgpu_waves_per_eu(2)
     }
     __syncthreads();
 
-    // ---- the pool: a lane takes eight channels of one pooled pixel; window rows 2 py - 1 .. 2 py + 1 are map rows 2 ply .. + 2
+    // ---- the pool: a lane takes eight channels of one pooled pixel; window rows 2 py - PAD .. + 2 are map rows 2 ply .. + 2 in
+    // either geometry.  A ceil-mode window that hangs over the bottom / right edge of the conv map reads the -inf written above
+    // at cy >= Hc / cx >= Wc, as the pad-1 window does at cy = -1: the max is over the pixels inside the map
     for (int q = tid; q < kStemTH * kStemTW * 8; q += kStemThreads) {
       const int pp = q >> 3, c8 = (q & 7) * 8;
       const int ply = pp / kStemTW, plx = pp - ply * kStemTW;
@@ -241,12 +249,31 @@ __global__ __launch_bounds__(256) void stem_pack_weight_kernel(const float* w, c
 
 bool stem_cin_ok(int Cin) { return Cin == 1 || Cin == 3 || Cin == 4; }
 
-int stem_shape(const char* who, int N, int Cin, int H, int W, StemArgs* a) {
+// The shape rule of both pool geometries, torch's max_pool2d output size: conv map L -> floor((L + 2 - 3) / 2) + 1 with pad 1;
+// ceil((L - 3) / 2) + 1 = (L - 2) / 2 + 1 with pad 0 and ceil_mode (L >= 2; the last window starts at 2 * ((L - 2) / 2) <= L - 2,
+// inside the map, so torch's "last window must start inside the input" correction never applies).
+int stem_out_hw(const char* who, int H, int W, int pool_mode, int* Hc, int* Wc, int* Hp, int* Wp) {
+  AVF_REQUIRE(pool_mode == AVF_STEM_POOL_PAD1 || pool_mode == AVF_STEM_POOL_CEIL,
+              "%s: pool_mode=%d: the stem pool is AVF_STEM_POOL_PAD1 (0: 3x3 / 2 / pad 1, floor) or AVF_STEM_POOL_CEIL (1: 3x3 / 2 / pad 0, "
+              "ceil_mode)", who, pool_mode);
+  AVF_REQUIRE(H > 0 && W > 0, "%s: empty shape (H=%d W=%d)", who, H, W);
+  *Hc = (H - 1) / 2 + 1; *Wc = (W - 1) / 2 + 1;
+  if (pool_mode == AVF_STEM_POOL_CEIL) {
+    AVF_REQUIRE(H >= 3 && W >= 3, "%s: H=%d W=%d with AVF_STEM_POOL_CEIL: the conv map %d x %d is smaller than 2 x 2, for which "
+                "max_pool2d(3, 2, padding=0, ceil_mode=True) has no output; H and W must be at least 3", who, H, W, *Hc, *Wc);
+    *Hp = (*Hc - 2) / 2 + 1; *Wp = (*Wc - 2) / 2 + 1;
+  } else {
+    *Hp = (*Hc - 1) / 2 + 1; *Wp = (*Wc - 1) / 2 + 1;
+  }
+  return 0;
+}
+
+int stem_shape(const char* who, int N, int Cin, int H, int W, int pool_mode, StemArgs* a) {
   AVF_REQUIRE(N > 0 && H > 0 && W > 0, "%s: empty shape (N=%d H=%d W=%d)", who, N, H, W);
   AVF_REQUIRE(stem_cin_ok(Cin), "%s: Cin=%d: the stem kernel takes 1, 3 or 4 input channels (and writes 64)", who, Cin);
   a->N = N; a->H = H; a->W = W;
-  a->Hc = (H - 1) / 2 + 1; a->Wc = (W - 1) / 2 + 1;
-  a->Hp = (a->Hc - 1) / 2 + 1; a->Wp = (a->Wc - 1) / 2 + 1;
+  AVF_TRY(stem_out_hw(who, H, W, pool_mode, &a->Hc, &a->Wc, &a->Hp, &a->Wp));
+  a->pad = pool_mode == AVF_STEM_POOL_CEIL ? 0 : 1;
   a->tiles_y = (int)ceil_div(a->Hp, kStemTH);
   a->tiles_x = (int)ceil_div(a->Wp, kStemTW);
   AVF_REQUIRE((int64_t)a->tiles_y * a->tiles_x < (1ll << 31), "%s: too many tiles per image", who);
@@ -254,21 +281,25 @@ int stem_shape(const char* who, int N, int Cin, int H, int W, StemArgs* a) {
   return 0;
 }
 
-template <typename XT, typename OT, int CIN>
-int stem_launch_cin(const StemArgs& a, hipStream_t s) {
+template <typename XT, typename OT, int CIN, int PAD>
+int stem_launch_pad(const StemArgs& a, hipStream_t s) {
   constexpr size_t lds = stem_lds_bytes(CIN, sizeof(OT));
   static_assert(lds <= 80 * 1024, "two workgroups per CU");
   static PerDeviceOnce raised;
   if (lds > 64 * 1024 && raised.need()) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem_nchw_kernel<XT, OT, CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)stem_nchw_kernel<XT, OT, CIN, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     AVF_REQUIRE(e == hipSuccess, "stem_nchw: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     raised.mark();
   }
   // persistent: as many workgroups as stay resident - two per CU by registers, four for one channel and a bf16 map
   constexpr int64_t slots = (CIN == 1 && sizeof(OT) == 2) ? 2 * kWorkgroupSlots : kWorkgroupSlots;
   const unsigned grid = (unsigned)(a.tiles < slots ? a.tiles : slots);
-  stem_nchw_kernel<XT, OT, CIN><<<grid, kStemThreads, lds, s>>>(a);
+  stem_nchw_kernel<XT, OT, CIN, PAD><<<grid, kStemThreads, lds, s>>>(a);
   return check_launch("stem_nchw");
+}
+template <typename XT, typename OT, int CIN>
+int stem_launch_cin(const StemArgs& a, hipStream_t s) {
+  return a.pad ? stem_launch_pad<XT, OT, CIN, 1>(a, s) : stem_launch_pad<XT, OT, CIN, 0>(a, s);
 }
 template <typename XT, typename OT>
 int stem_launch_out(const StemArgs& a, int Cin, hipStream_t s) {
@@ -297,7 +328,7 @@ extern "C" int avf_stem_packed_k(int Cin) {
 extern "C" int avf_stem_plan(int N, int Cin, int H, int W, int* tile_h, int* tile_w) {
   AVF_REQUIRE(tile_h && tile_w, "stem_plan: null pointer");
   StemArgs a;
-  AVF_TRY(stem_shape("stem_plan", N, Cin, H, W, &a));
+  AVF_TRY(stem_shape("stem_plan", N, Cin, H, W, AVF_STEM_POOL_PAD1, &a));
   *tile_h = kStemTH;
   *tile_w = kStemTW;
   return 0;
@@ -318,12 +349,22 @@ extern "C" int avf_stem_pack_weight(const float* w, const float* gamma, const fl
   return check_launch("stem_pack_weight");
 }
 
+extern "C" int avf_stem_out_hw(int H, int W, int pool_mode, int* Hc, int* Wc, int* Hp, int* Wp) {
+  AVF_REQUIRE(Hc && Wc && Hp && Wp, "stem_out_hw: null pointer");
+  return stem_out_hw("stem_out_hw", H, W, pool_mode, Hc, Wc, Hp, Wp);
+}
+
 extern "C" int avf_stem_nchw(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
                              int out_dtype, int N, int Cin, int H, int W, void* stream) {
+  return avf_stem_nchw_pool(x, x_dtype, w_packed, scale, shift, out, out_dtype, N, Cin, H, W, AVF_STEM_POOL_PAD1, stream);
+}
+
+extern "C" int avf_stem_nchw_pool(const void* x, int x_dtype, const void* w_packed, const float* scale, const float* shift, void* out,
+                                  int out_dtype, int N, int Cin, int H, int W, int pool_mode, void* stream) {
   AVF_REQUIRE(x && w_packed && scale && shift && out, "stem_nchw: null pointer");
   AVF_REQUIRE(is_dtype(x_dtype) && is_dtype(out_dtype), "stem_nchw: bad dtype (x %d, out %d)", x_dtype, out_dtype);
   StemArgs a;
-  AVF_TRY(stem_shape("stem_nchw", N, Cin, H, W, &a));
+  AVF_TRY(stem_shape("stem_nchw", N, Cin, H, W, pool_mode, &a));
   AVF_REQUIRE(aligned(x, elt(x_dtype)), "stem_nchw: x must be aligned to its element");
   AVF_REQUIRE(aligned(w_packed, 16) && aligned(scale, 16) && aligned(shift, 16) && aligned(out, 16),
               "stem_nchw: w_packed, scale, shift and out must be 16-byte aligned");

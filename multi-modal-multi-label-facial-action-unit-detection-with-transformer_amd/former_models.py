@@ -11,7 +11,11 @@ does.  Without a backbone the models consume what the backbone would produce (a 
 average pool + a fixed channel tiling to 512 features), which is enough to drive the token path, the heads and the
 [B, 21] output contract.  ``backbone="resnet18_frozen"`` builds the stages themselves: ``backbone.FrozenResFormer``, the reference's whole
 ``ResFormer`` in eval mode on the HIP conv kernels, forward only (csrc/conv.hip).  Module / parameter names follow the reference so that its checkpoints load with strict=False.
-The small ``fc`` heads (BatchNorm1d / Linear) are plain PyTorch modules - plumbing either side of the hot path."""
+The small ``fc`` heads (BatchNorm1d / Linear) are plain PyTorch modules - plumbing either side of the hot path.
+
+``vggformer`` (VGGVisualFormer, vggformer.py:323-421) is the fifth entry: ``VGGVisualFormerModel`` owns its backbone - the frozen
+VGGFace2 ResNet-50 of ``vggface2.VGGFormer`` on the HIP conv path - and, because everything trainable sits behind that backbone's
+last convolution, trains there."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -162,6 +166,49 @@ class VisualFormerModel(_FormerTask):
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vformer'])
+
+    def forward(self, x):
+        return self.fc(self.video_model(self._select(x)))
+
+
+class _VGGVideoModel(nn.Module):
+    """``VideoModel`` of vggformer.py:323-342 with its fc replaced by the identity (vggformer.py:390): ``s_former`` is a
+    ``VGGFormer``, ``t_former`` a ``TFormer`` over 16 frames"""
+
+    def __init__(self, num_channels, backend, stem, backbone_dtype, compute_dtype):
+        super().__init__()
+        from .vggface2 import VGGFormer
+        self.s_former = VGGFormer(backend=backend, stem=stem, conv_dtype=backbone_dtype, compute_dtype=compute_dtype,
+                                  in_channels=num_channels)
+        self.t_former = TFormer(num_patches=16, dim=512, compute_dtype=compute_dtype)
+
+    def forward(self, x):
+        return self.t_former(self.s_former(x))                 # [B, T, C, H, W] -> [B*16, 512] -> cls token [B, 512]
+
+
+class VGGVisualFormerModel(_FormerTask):
+    """registry name ``vggformer`` (vggformer.py:364-421): ``VGGFormer`` frames (the frozen VGGFace2 ResNet-50, a trainable 1x1
+    conv and one transformer layer over its map) -> ``TFormer`` over 16 frames -> fc head ``Linear(512, 256) - BatchNorm1d -
+    ReLU - Linear(256, 21)`` (vggformer.py:384-389), plain torch like the other fc heads.
+
+    ``backend="hip"`` (default) runs the extractor on the HIP conv path and ``stem="hip"`` (default) its stem on the stem kernel;
+    the model trains there, since nothing in front of the extractor's last convolution has a gradient.  ``backbone_dtype="f32"`` is
+    the parity arithmetic of the extractor and needs ``stem="torch"`` (the stem kernel has no parity form).  The VGGFace2
+    weights are not loaded here (the reference reads a fixed path, vggformer.py:328): call
+    ``video_model.s_former.load_pretrain_vgg(path)``; ``video_pretrained`` is accepted for the signature."""
+    has_backbone = True
+
+    def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', compute_dtype="bf16", task_losses="plain",
+                 backbone_dtype="bf16", backend="hip", stem="hip"):
+        super().__init__()
+        # The reference's config_modality (vggformer.py:344-362) reads self.s_former.conv1, which VGGFormer does not have, and
+        # raises for every modality with a mask.  What it means is what sformer / vformer / tformer do: the extractor's first
+        # convolution, VGG_model.conv1, takes the 4 (RGB + mask) or 1 (mask only) channels the modality selects.
+        self._config(modality, task)
+        self.video_model = _VGGVideoModel(self.num_channels, backend, stem, backbone_dtype, compute_dtype)
+        self.task, self.modes = task, ["clip"]
+        self.fc = nn.Sequential(nn.Linear(512, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Linear(256, 12 + 7 + 2))
+        self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vggformer'])
 
     def forward(self, x):
         return self.fc(self.video_model(self._select(x)))

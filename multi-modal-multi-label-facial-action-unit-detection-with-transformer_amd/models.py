@@ -97,6 +97,7 @@ REFERENCE_TASK_LOSSES = {
     'sformer': ('ce', 'dice', (1.0, 1.0)),
     'vformer': ('ce', 'bce', (2.0, 1.0)),
     'tformer': ('ce', 'bce', (2.0, 1.0)),
+    'vggformer': ('ce', 'bce', (2.0, 1.0)),   # vggformer.py:391-395 and 420: cross-entropy ignoring 7, AULoss, CCC 2 v + a
 }
 
 
@@ -303,10 +304,11 @@ MODEL_REGISTRY = {
 
 
 def _register_former_models():
-    # sformer / vformer / tformer (train.py:292-303): the token sections on the HIP path around a caller's CNN backbone
+    # sformer / vformer / tformer (train.py:292-303): the token sections on the HIP path around a caller's CNN backbone;
+    # vggformer (train.py:296-299): the frozen VGGFace2 ResNet-50 on the HIP conv path under a trainable token section
     from . import former_models as fm
     MODEL_REGISTRY.update({'sformer': fm.SpatialFormerModel, 'vformer': fm.VisualFormerModel,
-                           'tformer': fm.SpatialTemporalFormerModel})
+                           'tformer': fm.SpatialTemporalFormerModel, 'vggformer': fm.VGGVisualFormerModel})
 
 
 def build_model(model_name: str, modality: str = 'A;V;M', task: str = 'AU', **kw) -> nn.Module:
@@ -314,7 +316,7 @@ def build_model(model_name: str, modality: str = 'A;V;M', task: str = 'AU', **kw
         _register_former_models()
     if model_name not in MODEL_REGISTRY:
         raise KeyError(f"model {model_name!r} is not provided by the MI355X hot-path build; available: "
-                       f"{sorted(MODEL_REGISTRY)} (the CNN-only models of the reference are out of scope)")
+                       f"{sorted(MODEL_REGISTRY)} (the reference's models that train a CNN end to end are out of scope)")
     cls = MODEL_REGISTRY[model_name]
     if cls is SyntheticAVFormer:
         return cls(task=task, **kw)

@@ -5,6 +5,7 @@ All tensors must live on a CUDA(HIP) device; nothing here falls back to PyTorch 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -1362,10 +1363,27 @@ def stem_packed_k(Cin: int) -> int:
     return kp
 
 
-def stem_out_hw(H: int, W: int) -> Tuple[int, int]:
-    """(Hp, Wp) of conv 7x7 / 2 / pad 3 followed by maxpool 3x3 / 2 / pad 1"""
-    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+STEM_POOLS = {"pad1": _lib.STEM_POOL_PAD1, "ceil": _lib.STEM_POOL_CEIL}
+
+
+def _stem_pool(pool) -> int:
+    if pool not in STEM_POOLS:
+        raise ValueError(f"pool must be one of {tuple(STEM_POOLS)}, got {pool!r}")
+    return STEM_POOLS[pool]
+
+
+@functools.lru_cache(maxsize=256)
+def _stem_out_hw(H: int, W: int, mode: int) -> Tuple[int, int]:
+    out = [C.c_int(-1) for _ in range(4)]
+    _lib.check(_lib.load().avf_stem_out_hw(H, W, mode, *[C.byref(o) for o in out]), "stem_out_hw")
+    return out[2].value, out[3].value
+
+
+def stem_out_hw(H: int, W: int, pool: str = "pad1") -> Tuple[int, int]:
+    """(Hp, Wp) of conv 7x7 / 2 / pad 3 followed by the stem's maxpool: ``pool="pad1"`` 3x3 / 2 / pad 1 (floor), ``pool="ceil"``
+    3x3 / 2 / pad 0 with ceil_mode (VGGFace2's ResNet-50; H, W >= 3).  The rule the launch itself acts on (avf_stem_out_hw; the
+    answer per (H, W, pool) is kept, so a launch-bound caller pays the host call once)."""
+    return _stem_out_hw(int(H), int(W), _stem_pool(pool))
 
 
 def stem_plan(N: int, Cin: int, H: int, W: int) -> dict:
@@ -1398,15 +1416,18 @@ def stem_pack_weight(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, r
 
 
 def stem_nchw(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, out: Optional[torch.Tensor] = None,
-              out_dtype=torch.bfloat16) -> torch.Tensor:
-    """maxpool3x3/2(relu(conv7x7/2(x, w) * scale + shift)) in one launch (avf_stem_nchw): x [N, Cin, H, W] contiguous planes, fp32
-    or bf16, Cin in {1, 3, 4}, any H, W >= 1; w_packed / scale / shift from ``stem_pack_weight``; -> out [N, Hp, Wp, 64] NHWC,
-    fp32 or bf16.  x may start at any element (a view into a larger buffer); out must be 16-byte aligned.  Forward only."""
+              out_dtype=torch.bfloat16, pool: str = "pad1") -> torch.Tensor:
+    """maxpool3x3/2(relu(conv7x7/2(x, w) * scale + shift)) in one launch (avf_stem_nchw_pool): x [N, Cin, H, W] contiguous planes,
+    fp32 or bf16, Cin in {1, 3, 4}, any H, W >= 1; w_packed / scale / shift from ``stem_pack_weight``; -> out [N, Hp, Wp, 64] NHWC,
+    fp32 or bf16.  ``pool``: ``"pad1"`` (default) pools with padding 1, floor mode; ``"ceil"`` with padding 0 and ceil_mode
+    (H, W >= 3), see ``stem_out_hw``.  x may start at any element (a view into a larger buffer); out must be 16-byte aligned.
+    Forward only."""
+    mode = _stem_pool(pool)
     _need_cuda(x, w_packed, scale, shift, out)
     if x.dim() != 4 or not x.is_contiguous():
         raise ValueError(f"stem_nchw: x must be a contiguous [N, Cin, H, W] tensor (got {tuple(x.shape)}, strides {x.stride()})")
     N, Cin, H, W = x.shape
-    Hp, Wp = stem_out_hw(H, W)
+    Hp, Wp = _stem_out_hw(H, W, mode)
     if out is None:
         out = torch.empty((N, Hp, Wp, STEM_COUT), dtype=torch_dtype(out_dtype), device=x.device)
     if tuple(out.shape) != (N, Hp, Wp, STEM_COUT) or not out.is_contiguous():
@@ -1421,8 +1442,8 @@ def stem_nchw(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, shif
             raise ValueError(f"stem_nchw: {name} must be a contiguous fp32 [{STEM_COUT}] tensor")
     if w_packed.dtype != torch.bfloat16:
         raise ValueError("stem_nchw: w_packed must be bf16")
-    _lib.check(lib.avf_stem_nchw(_ptr(x), avf_dtype(x.dtype), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out), avf_dtype(out.dtype),
-                                 N, Cin, H, W, _stream()), "stem_nchw")
+    _lib.check(lib.avf_stem_nchw_pool(_ptr(x), avf_dtype(x.dtype), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out),
+                                      avf_dtype(out.dtype), N, Cin, H, W, mode, _stream()), "stem_nchw")
     return out
 
 
