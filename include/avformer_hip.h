@@ -305,6 +305,21 @@ int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float
 #define AVF_ATTN_F32 4
 #define AVF_ATTN_MERGED 8
 int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int masked, int* fwd, int* bwd);
+/* Which kernel family the fp32-arithmetic attention (avf_attn_fwd / avf_attn_bwd on AVF_F32, and the masked / bf16-storage
+ * calls that share its dispatch) takes under the arithmetic avf_get_f32_arith() reports now - host code only, read-only,
+ * answered by the predicates the dispatch itself switches on:
+ *   AVF_ATTN_PARITY_VEC     the one-lane-per-query kernels (a mask, bf16 storage, pre-scaled q, another dim_head, or a tensor
+ *                           that does not start on a 16-byte boundary)
+ *   AVF_ATTN_PARITY_F32MFMA the f32-input MFMA kernels (dim_head 32 / 64 / 128)
+ *   AVF_ATTN_PARITY_BF16X3  three bf16 products per fp32 product (dim_head 64, arithmetic 1)
+ * aligned16 = 1: every tensor of the call (qkv, o, d_o, dqkv) starts on a 16-byte boundary.  aligned16 = 0: qkv itself does
+ * not - both families refuse such a call, forward and backward.  A call whose qkv is aligned and another tensor is not lies
+ * outside this query: the forward then looks at o, the backward at d_o and dqkv, and its bf16x3 kernels also at o (a
+ * misaligned o alone sends that backward to the f32-input MFMA kernels). */
+#define AVF_ATTN_PARITY_VEC 0
+#define AVF_ATTN_PARITY_F32MFMA 1
+#define AVF_ATTN_PARITY_BF16X3 2
+int avf_attn_parity_plan(int dtype, int dim_head, int masked, int q_prescaled, int aligned16, int heads);
 /* ... with the token mask of heads.py:225-232 (keep: device bytes [batch, tokens], 1 = kept - ANY pattern, token 0 and
  * whole clips included): the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8
  * stack - one internal helper picks the kernels for the layer and for these calls.  avf_attn_masked_on_mfma(tokens,

@@ -105,6 +105,7 @@ SIGNATURES = {
     "avf_attn_fwd_qs": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_bwd_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_plan": (_int, [_int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "avf_attn_parity_plan": (_int, [_int, _int, _int, _int, _int, _int]),
     "avf_attn_masked_on_mfma": (_int, [_int, _int]),
     "avf_attn_fwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_bwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),

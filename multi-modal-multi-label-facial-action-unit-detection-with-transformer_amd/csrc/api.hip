@@ -486,6 +486,12 @@ extern "C" int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int mask
   return attn_bf16_plan(tokens, dim_head, q_prescaled != 0, masked != 0, fwd, bwd);
 }
 
+// which family avf_attn_fwd / avf_attn_bwd take in the parity mode, under the arithmetic set now: host code only, answered by
+// the predicates attn_fwd_vec / attn_bwd_vec switch on
+extern "C" int avf_attn_parity_plan(int dtype, int dim_head, int masked, int q_prescaled, int aligned16, int heads) {
+  return attn_parity_plan(dtype, dim_head, masked != 0, q_prescaled != 0, aligned16 != 0, heads);
+}
+
 // ... with the token mask: the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8 stack
 // (attn_fwd_masked_bf16 / attn_bwd_masked_bf16 choose the kernels for both).  workspace: 2 * avf_attn_bwd_workspace_bytes.
 extern "C" int avf_attn_masked_on_mfma(int tokens, int dim_head) { return attn_masked_bf16_ok(tokens, dim_head, true) ? 1 : 0; }

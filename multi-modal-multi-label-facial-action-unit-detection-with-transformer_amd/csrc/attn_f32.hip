@@ -323,6 +323,15 @@ static int with_vec_variant(int dh, int dtype, bool masked, const char* who, F&&
   });
 }
 
+// which family attn_fwd_vec / attn_bwd_vec take, from the predicates they switch on and in their order.  aligned16 = true speaks
+// for every tensor of the call, false for a misaligned qkv; the backward asks dqkv (and, for bf16x3, o) besides the predicate's
+// pair, so a call with only one of those off the grid is not what this answers (avformer_hip.h says so)
+int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H) {
+  if (attn_f32x3_takes(dtype, dh, masked, H, aligned16, q_prescaled)) return 2;
+  if (attn_f32_mfma_takes(dtype, dh, masked, H, aligned16, q_prescaled)) return 1;
+  return 0;
+}
+
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s) {
   return attn_fwd_vec(AVF_F32, qkv, o, lse2, B, N, H, dh, s, nullptr, false);
 }

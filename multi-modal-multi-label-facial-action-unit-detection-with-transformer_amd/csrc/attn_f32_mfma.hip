@@ -102,9 +102,11 @@ struct ParityF32Mfma {
 }  // namespace
 
 // shapes these kernels take: fp32 storage, no token mask, q not pre-scaled, dim_head 32, 64 or 128, 16-byte aligned rows
+bool attn_f32_mfma_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled) {
+  return dtype == AVF_F32 && !masked && !q_prescaled && (dh == 32 || dh == 64 || dh == 128) && aligned16 && ((H * dh) % 4) == 0;
+}
 bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled) {
-  return dtype == AVF_F32 && !keep && !q_prescaled && (dh == 32 || dh == 64 || dh == 128) && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)other & 15) == 0 &&
-         ((H * dh) % 4) == 0;
+  return attn_f32_mfma_takes(dtype, dh, keep != nullptr, H, attn_aligned16(qkv, other), q_prescaled);
 }
 
 int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s) {

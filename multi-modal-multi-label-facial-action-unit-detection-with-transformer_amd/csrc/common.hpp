@@ -638,12 +638,22 @@ int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s);
 
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
 // fp32-arithmetic attention on fp32 / bf16 storage with the optional token mask keep [B, N] (bytes, 1 = kept; heads.py:225-232)
+// The two predicates of the parity-mode dispatch (attn_fwd_vec / attn_bwd_vec), each in two forms sharing one body: *_ok looks at
+// the call's pointers (keep for null-ness; qkv and the other tensor a kernel touches with 16-byte accesses for alignment), *_takes
+// is told the same facts - what avf_attn_parity_plan answers from.
+inline bool attn_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+// 0 = the one-lane-per-query kernels of attn_f32.hip, 1 = attn_f32_mfma.hip, 2 = attn_f32x3.hip: the order of the dispatch.
+// aligned16: every tensor of the call starts on a 16-byte boundary; false stands for a misaligned qkv (refused by both, in both
+// passes) - which of o, d_o, dqkv each pass asks besides is in avformer_hip.h.
+int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H);
 // parity-mode attention on the fp32 matrix pipe (attn_f32_mfma.hip): fp32 storage, no mask, dim_head 32 / 64 / 128, raw q
+bool attn_f32_mfma_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled);
 bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
 int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
 int attn_bwd_f32_mfma(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, int B, int N, int H,
                       int dh, hipStream_t s);
 // parity-mode attention with three bf16 products per fp32 product (attn_f32x3.hip): fp32 storage, no mask, dim_head 64, raw q
+bool attn_f32x3_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled);
 bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
 int attn_fwd_f32x3(const float* qkv, float* o, float* lse2, int B, int N, int H, hipStream_t s);
 int attn_bwd_f32x3(const float* qkv, const float* o, const float* d_o, const float* lse2, float* delta, float* dqkv, int B, int N,

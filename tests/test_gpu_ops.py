@@ -396,6 +396,8 @@ def _attn_ref(qkv, B, N, H, dh, d_o=None):
                                       # the MFMA kernels' 32-row tile edge and 64-row workgroup edge
                                       (1, 1, 2, 64), (1, 31, 2, 64), (1, 33, 2, 64), (1, 65, 2, 64), (2, 33, 2, 32)])
 def test_attention_f32(ops, f32_arith, B, N, H, dh):
+    """whole-tensor allclose, the backward on the device's own o and lse2 (tests/test_gpu_attn_parity.py holds the same kernels
+    group-wise to an fp64 reference, the backward on reference-made inputs, and asserts which kernel family each case runs)"""
     g = torch.Generator().manual_seed(B * 100 + N + dh)
     qkv = torch.randn(B * N, 3 * H * dh, generator=g)
     d_o = torch.randn(B * N, H * dh, generator=g)
