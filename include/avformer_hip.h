@@ -285,7 +285,7 @@ int avf_attn_bwd(int dtype, const void* qkv, const void* o, const void* d_o, con
  * the scores leave the MFMA in the log2 domain and the subtraction of the running maximum / of lse2 rides in the MFMA's
  * C operand (no per-score multiply-add).  This is what avf_layer_fwd / avf_layer_bwd run - they fold the factor into the
  * query rows of the bf16 copy of to_qkv.weight (heads.py:212) - and dq, dk, dv are still the gradients with respect to
- * the UNSCALED q, k, v.  workspace >= 2 * avf_attn_bwd_workspace_bytes(...). */
+ * the UNSCALED q, k, v.  workspace >= avf_attn_bwd_workspace_bytes(...). */
 int avf_attn_fwd_qs(const void* qkv, void* o, float* lse2, int batch, int tokens, int heads, int dim_head, void* stream);
 int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, void* workspace,
                     int batch, int tokens, int heads, int dim_head, void* stream);
@@ -294,7 +294,7 @@ int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float
  * avf_attn_bwd_qs (q_prescaled = 1); masked = 1: avf_attn_fwd_masked_qs / avf_attn_bwd_masked_qs and the layer.
  *   *fwd: AVF_ATTN_RES8 | RES12 | RES_MULTI - the head-resident kernel with up to 8 / 12 waves in one pass, or 8 waves in
  *         several; AVF_ATTN_STREAM - the streaming kernel; AVF_ATTN_F32 - the fp32-arithmetic kernel (masked = 1 only).
- *   *bwd: the same values for the two head-resident kernels, delta + the two streaming kernels, the fp32-arithmetic ones;
+ *   *bwd: AVF_ATTN_STREAM - delta + the two streaming kernels; AVF_ATTN_F32 - the fp32-arithmetic ones (masked = 1 only);
  *         or AVF_ATTN_MERGED + 2 * KB + ragged - the merged kernel with KB = 1 .. 4 key blocks per wave, ragged = 1 when
  *         the last key block holds rows past `tokens` (always under a mask).
  * The tuning switches of the library (AVF_TUNING=1) move the answers exactly as they move the launches. */
@@ -325,7 +325,7 @@ int avf_attn_parity_plan(int dtype, int dim_head, int masked, int q_prescaled, i
  * stack - one internal helper picks the kernels for the layer and for these calls.  avf_attn_masked_on_mfma(tokens,
  * dim_head) = 1: the masked head-resident MFMA forward and the masked merged backward (dim_head 64, tokens <= 512);
  * 0: the fp32-arithmetic kernels on bf16 storage with pre-scaled q.  lse2 of a dropped query: log2(tokens) on the MFMA
- * kernels, unspecified (finite) otherwise.  workspace >= 2 * avf_attn_bwd_workspace_bytes(...). */
+ * kernels, unspecified (finite) otherwise.  workspace >= avf_attn_bwd_workspace_bytes(...). */
 int avf_attn_masked_on_mfma(int tokens, int dim_head);
 int avf_attn_fwd_masked_qs(const void* qkv, void* o, float* lse2, const void* keep, int batch, int tokens, int heads,
                            int dim_head, void* stream);

@@ -421,7 +421,7 @@ extern "C" int avf_attn_bwd_mx8(const void* qkv, const void* o, const void* d_o,
   AVF_REQUIRE(attn_bwd_emits_mx8(tokens, dim_head, true),
               "attn_bwd_mx8: only the merged backward kernel writes the image (tokens=%d dim_head=%d)", tokens, dim_head);
   return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, nullptr, batch, tokens, heads,
-                       dim_head, (hipStream_t)stream, true, nullptr, nullptr, dqkv_q, dqkv_scales);
+                       dim_head, (hipStream_t)stream, true, nullptr, dqkv_q, dqkv_scales);
 }
 extern "C" int avf_quant_mx8(int dtype, const void* x, int64_t rows, int64_t cols, void* q, void* scales, void* stream) {
   AVF_REQUIRE(x && q && scales, "quant_mx8: null pointer");
@@ -465,7 +465,7 @@ extern "C" int avf_attn_bwd(int dtype, const void* qkv, const void* o, const voi
 }
 
 // bf16 attention on a projection whose q columns already carry log2(e)/sqrt(dim_head) - what avf_layer_fwd/bwd run
-// (the factor is folded into the query rows of the bf16 Wqkv image).  workspace: 2 * avf_attn_bwd_workspace_bytes.
+// (the factor is folded into the query rows of the bf16 Wqkv image).  workspace: avf_attn_bwd_workspace_bytes.
 extern "C" int avf_attn_fwd_qs(const void* qkv, void* o, float* lse2, int batch, int tokens, int heads, int dim_head,
                                void* stream) {
   AVF_REQUIRE(qkv && o && lse2, "attn_fwd_qs: null pointer");
@@ -474,9 +474,8 @@ extern "C" int avf_attn_fwd_qs(const void* qkv, void* o, float* lse2, int batch,
 extern "C" int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv,
                                void* workspace, int batch, int tokens, int heads, int dim_head, void* stream) {
   AVF_REQUIRE(qkv && o && d_o && lse2 && dqkv && workspace, "attn_bwd_qs: null pointer");
-  float* w = (float*)workspace;
-  return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, w, batch, tokens, heads,
-                       dim_head, (hipStream_t)stream, true, w + (size_t)batch * tokens * heads);
+  return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, (float*)workspace, batch, tokens,
+                       heads, dim_head, (hipStream_t)stream, true);
 }
 
 // which kernels those calls launch (masked = 0) and the masked ones below (masked = 1): host code only, answered by the
@@ -493,7 +492,7 @@ extern "C" int avf_attn_parity_plan(int dtype, int dim_head, int masked, int q_p
 }
 
 // ... with the token mask: the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8 stack
-// (attn_fwd_masked_bf16 / attn_bwd_masked_bf16 choose the kernels for both).  workspace: 2 * avf_attn_bwd_workspace_bytes.
+// (attn_fwd_masked_bf16 / attn_bwd_masked_bf16 choose the kernels for both).  workspace: avf_attn_bwd_workspace_bytes.
 extern "C" int avf_attn_masked_on_mfma(int tokens, int dim_head) { return attn_masked_bf16_ok(tokens, dim_head, true) ? 1 : 0; }
 extern "C" int avf_attn_fwd_masked_qs(const void* qkv, void* o, float* lse2, const void* keep, int batch, int tokens, int heads,
                                       int dim_head, void* stream) {
@@ -504,9 +503,8 @@ extern "C" int avf_attn_bwd_masked_qs(const void* qkv, const void* o, const void
                                       void* workspace, const void* keep, int batch, int tokens, int heads, int dim_head,
                                       void* stream) {
   AVF_REQUIRE(qkv && o && d_o && lse2 && dqkv && workspace && keep, "attn_bwd_masked_qs: null pointer");
-  float* w = (float*)workspace;
-  return attn_bwd_masked_bf16(qkv, o, d_o, lse2, dqkv, w, w + (size_t)batch * tokens * heads, keep, batch, tokens, heads, dim_head,
-                              (hipStream_t)stream, true);
+  return attn_bwd_masked_bf16(qkv, o, d_o, lse2, dqkv, (float*)workspace, keep, batch, tokens, heads, dim_head, (hipStream_t)stream,
+                              true);
 }
 
 // After a FAILED stream capture (an operation that cannot be recorded was issued while capturing): end a capture that is still

@@ -314,12 +314,13 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf
 }
 
 // =============================================================================================
-// head-resident variants (dim_head 64, N <= RES_MAX_N): ONE workgroup per (batch, head) keeps the head's whole K and
-// V (or Q and dO) in LDS - 128 B per row, N rounded up to 32 rows - so nothing is staged twice, there is no ring and
-// no per-tile barrier.  The N rows are cut into V = ceil(N/32) groups of 32 query (key) rows; the workgroup has
+// head-resident forward (dim_head 64, N <= RES_MAX_N): ONE workgroup per (batch, head) keeps the head's whole K and
+// V in LDS - 128 B per row, N rounded up to 32 rows - so nothing is staged twice, there is no ring and
+// no per-tile barrier.  The N rows are cut into V = ceil(N/32) groups of 32 query rows; the workgroup has
 // W = ceil(V / passes) wavefronts (passes = ceil(V/12): at most 12 waves, three per SIMD at <= 168 VGPRs) and wave w
-// takes groups w, w+W, ...  After the load phase the waves free-run over the key (query) tiles, which lets the MFMA
-// phase of one wave overlap the softmax VALU phase of another on the same SIMD.
+// takes groups w, w+W, ...  After the load phase the waves free-run over the key tiles, which lets the MFMA
+// phase of one wave overlap the softmax VALU phase of another on the same SIMD.  (The backward has no head-resident
+// form: the merged kernel of attn_bwd_merged.hip or the streaming pair below.)
 //
 // LDS image: written by LDS-DMA (global_load_lds_dwordx4, 64 lanes x 16 B = 8 rows per instruction, no staging
 // VGPRs), so it is lane-linear per instruction; bank conflicts are avoided by permuting the SOURCE chunk instead:
@@ -333,8 +334,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf
 // probabilities stay <= 2^RES_TAU; the row sums come from the MFMA (a ones fragment as a 65th value row), the
 // cross-lane maximum from v_permlane{16,32}_swap instead of LDS permutes.  lse2 = m + log2(l) is exact whatever m is.
 // =============================================================================================
-constexpr int RES_MAX_N = 576;    // (N rounded to 32) * 256 B + the dK/dV kernel's statistics <= 160 KB
-constexpr int RES_A = 1;          // tiles whose DMA is issued before any compute (1 vs 2: -2 % backward, same forward)
+constexpr int RES_MAX_N = 576;    // (N rounded to 32) * 256 B of K and V images = 144 KB of the 160 KB
+constexpr int RES_A = 1;          // tiles whose DMA is issued before any compute (2 gave the same forward time)
 constexpr float RES_TAU = 6.0f;   // log2 of the largest probability kept before a rescale
 
 __device__ __forceinline__ void glds16(const void* g, char* l) {
@@ -366,26 +367,7 @@ __device__ __forceinline__ void glds16_res(const void* g, char* l) {
 #endif
 }
 
-__device__ __forceinline__ void glds4(const void* g, char* l) {
-  typedef __attribute__((address_space(1))) const void gptr_t;
-  typedef __attribute__((address_space(3))) void lptr_t;
-  __builtin_amdgcn_global_load_lds((gptr_t*)g, (lptr_t*)l, 4, 0, 0);
-}
-
 __device__ __forceinline__ void wait_all_loads() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// dot product of two 8-element bf16 fragments, fp32
-__device__ __forceinline__ float dot8(const bf16x8_t& x, const bf16x8_t& y) {
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-  const u32x4_t a = __builtin_bit_cast(u32x4_t, x), b = __builtin_bit_cast(u32x4_t, y);
-  float acc = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    acc = fmaf(__uint_as_float(a[i] << 16), __uint_as_float(b[i] << 16), acc);
-    acc = fmaf(__uint_as_float(a[i] & 0xffff0000u), __uint_as_float(b[i] & 0xffff0000u), acc);
-  }
-  return acc;
-}
 
 __device__ __forceinline__ bf16x8_t ones_frag() {
   typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
@@ -452,7 +434,7 @@ struct ResOffsets {
   }
 };
 
-// Tile schedule shared by the three kernels: pass 0 of every wave gates on the two arrival barriers and feeds the
+// Tile schedule of the head-resident forward: pass 0 of every wave gates on the two arrival barriers and feeds the
 // remaining DMA from its first tile; later passes (more 32-row groups than waves) run without any synchronisation.
 template <bool MULTI, typename TileFn, typename SyncFn>
 __device__ __forceinline__ void res_sweep(int N, bool first, TileFn&& tile, SyncFn&& sync) {
@@ -488,7 +470,7 @@ __device__ __forceinline__ void tr4x4(uint32_t (&a)[4]) {
 
 // MULTI: more 32-row groups than waves (each wave loops over its groups); otherwise exactly one group per wave.
 // QS: the q columns already carry log2(e)/sqrt(dh) (layer path) - the scores leave the MFMA in the log2 domain, and the
-// subtraction of the running maximum (forward) / of lse2 (backward) rides in the MFMA's C operand: no per-score FMA.
+// subtraction of the running maximum rides in the MFMA's C operand: no per-score FMA.
 // MASKED (QS only): the token mask of heads.py:225-232 - keep[b][n] != 0 keeps token n.  A pair (query, key) with either
 // token dropped scores -FLT_MAX in the reference: a kept query gives dropped keys zero weight (score -inf here), a dropped
 // query's row is one constant, i.e. uniform attention over ALL its keys (score 0 here: lse2 = log2 N exactly, which the
@@ -781,304 +763,6 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
           *reinterpret_cast<uint4*>(oq + row * I + h * DH + lg * 16) = make_uint4(qw[0], qw[1], qw[2], qw[3]);
           if (lg == 0) *reinterpret_cast<uint16_t*>(osc + row * (I >> 5) + h * 2) = (uint16_t)(sb[0] | (sb[1] << 8));
         }
-      }
-    }
-    AVF_PHASE_MARK(7);
-  } while (MULTI && (grp += W) < V);
-  AVF_PHASE_FLUSH();
-}
-
-// ---------------------------------------------------------------------------------------------
-// head-resident dQ: K and V images as in the forward; 32 query rows per group.  Also produces
-// delta[q] = sum_d O[q,d] dO[q,d] for its rows (from the dO fragments it holds anyway) and writes it for the
-// dK/dV kernel that follows on the stream - no separate delta launch on this path.
-// ---------------------------------------------------------------------------------------------
-// MULTI: more 32-row groups than waves (each wave loops over its groups); otherwise exactly one group per wave.
-// QS: the q columns already carry log2(e)/sqrt(dh) (layer path) - the scores leave the MFMA in the log2 domain, and the
-// subtraction of the running maximum (forward) / of lse2 (backward) rides in the MFMA's C operand: no per-score FMA.
-template <int MAXW, bool MULTI, bool QS>
-__global__ __launch_bounds__(MAXW * 64) void attn_dq_res_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
-                                                               const bf16* __restrict__ d_o,
-                                                               const float* __restrict__ lse2, float* __restrict__ delta,
-                                                               float* __restrict__ nlse, bf16* __restrict__ dqkv, int N,
-                                                               int H) {
-  constexpr int DH = 64, KS = 2, DB = 4;
-  extern __shared__ __attribute__((aligned(16))) char res_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), W = blockDim.x >> 6;
-  const int li = lane & 15, lg = lane >> 4;
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-  const int I = H * DH;
-  const int64_t ld = 3 * (int64_t)I;
-  const bf16* qbase = qkv + (int64_t)b * N * ld + h * DH;
-  const bf16* kbase = qbase + I;
-  const bf16* vbase = qbase + 2 * I;
-  const bf16* gbase = d_o + (int64_t)b * N * I + h * DH;
-  const bf16* obase = o + (int64_t)b * N * I + h * DH;
-  const int NP = (N + 31) & ~31, V = NP >> 5;
-  char* ksm = res_smem;
-  char* vsm = res_smem + NP * 128;
-  const float scale = 1.0f / sqrtf((float)DH);
-  const float c = LOG2E * scale;
-  ResLoader loader;
-  loader.init(kbase, ld, ksm, vbase, ld, vsm, NP, N, wave, W, lane);
-  ResOffsets off;
-  off.init(li, lg);
-
-  int grp = wave;
-  do {
-    const bool first_pass = !MULTI || grp == wave;
-    const int q0 = grp * 32;
-    bf16x8_t fq[2][KS], fg[2][KS];
-    float L[2], dl[2];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      const int q = q0 + qb * 16 + li;
-      const bool ok = q < N;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        fq[qb][ks] = load_frag_global(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, ok);
-        fg[qb][ks] = load_frag_global(gbase + (int64_t)q * I + ks * 32 + 8 * lg, ok);
-      }
-      L[qb] = ok ? lse2[(int64_t)bh * N + q] : 0.f;
-      float part = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        part += dot8(load_frag_global(obase + (int64_t)q * I + ks * 32 + 8 * lg, ok), fg[qb][ks]);
-      dl[qb] = colsum4(part);
-      if (ok && lg == 0) {
-        delta[(int64_t)bh * N + q] = -dl[qb];        // NEGATED: the dK/dV kernel feeds it to its dP MFMAs as the C operand
-        if (QS) nlse[(int64_t)bh * N + q] = -L[qb];  // likewise for the score MFMAs
-      }
-    }
-    const f32x4_t linit[2] = {{-L[0], -L[0], -L[0], -L[0]}, {-L[1], -L[1], -L[1], -L[1]}};
-    // dP - delta leaves the MFMA directly: -delta of the lane's query row rides in the C operand (no per-score subtract)
-    const f32x4_t dinit[2] = {{-dl[0], -dl[0], -dl[0], -dl[0]}, {-dl[1], -dl[1], -dl[1], -dl[1]}};
-    if (first_pass) loader.issue_until(16 * RES_A);
-
-    f32x4_t dqt[DB][2];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) dqt[d][qb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    auto tile = [&](int t, auto tail_tag, auto feed_tag) {
-      constexpr bool TAIL = decltype(tail_tag)::value;
-      constexpr bool FEED = decltype(feed_tag)::value;
-      const int nkb = TAIL ? (N - t * 64 + 15) / 16 : 4;
-      const char* kt = ksm + t * 8192;
-      const char* vt = vsm + t * 8192;
-      f32x4_t ds[4][2];
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        ds[kb][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        ds[kb][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (!TAIL || kb < nkb) {
-          const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
-          f32x4_t p0 = dinit[0], p1 = dinit[1];
-          f32x4_t s0 = QS ? linit[0] : zero, s1 = QS ? linit[1] : zero;  // QS: the MFMA returns log2-score - lse2
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8_t fk = lds_row_frag(kt + kb * 2048 + off.row[ks]);
-            const bf16x8_t fv = lds_row_frag(vt + kb * 2048 + off.row[ks]);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[0][ks], s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[1][ks], s1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, fg[0][ks], p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, fg[1][ks], p1, 0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const bool dead = TAIL && (t * 64 + kb * 16 + 4 * lg + r >= N);
-            const float e0 = dead ? 0.f : __builtin_amdgcn_exp2f(QS ? s0[r] : fmaf(s0[r], c, -L[0]));
-            const float e1 = dead ? 0.f : __builtin_amdgcn_exp2f(QS ? s1[r] : fmaf(s1[r], c, -L[1]));
-            ds[kb][0][r] = e0 * p0[r];
-            ds[kb][1][r] = e1 * p1[r];
-          }
-        }
-        if (FEED) loader.issue_one();
-      }
-      // dQ^T[d][q] += K^T dS^T
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        if (TAIL && 2 * s2 >= nkb) continue;
-        const bf16x8_t a0 = pack_pair(ds[2 * s2][0], ds[2 * s2 + 1][0]);
-        const bf16x8_t a1 = pack_pair(ds[2 * s2][1], ds[2 * s2 + 1][1]);
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          const bf16x8_t fkt = lds_tr_frag(kt + s2 * 4096 + off.tr[d]);
-          dqt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fkt, a0, dqt[d][0], 0, 0, 0);
-          dqt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fkt, a1, dqt[d][1], 0, 0, 0);
-        }
-        if (FEED) loader.issue_one();
-      }
-      if (FEED) loader.issue_until(1 << 30);
-    };
-    res_sweep<MULTI>(N, first_pass, tile, [&] {
-      wait_all_loads();
-      __builtin_amdgcn_s_barrier();
-    });
-
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      const int q = q0 + qb * 16 + li;
-      if (q < N) {
-        bf16* out = dqkv + ((int64_t)b * N + q) * ld + h * DH;
-store_row_pairs<DB>(out, lg, [&](int d) { return dqt[d][qb] * scale; });
-      }
-    }
-   } while (MULTI && (grp += W) < V);
-}
-
-// ---------------------------------------------------------------------------------------------
-// head-resident dK, dV: Q and dO images (+ the head's lse2 / delta rows, by 4-byte LDS-DMA) in LDS; 32 key rows per
-// group.  Query rows past N are copies of row N-1: their probabilities are zeroed in the tail tile.
-// ---------------------------------------------------------------------------------------------
-// MULTI: more 32-row groups than waves (each wave loops over its groups); otherwise exactly one group per wave.
-// QS: the q columns already carry log2(e)/sqrt(dh) (layer path) - the scores leave the MFMA in the log2 domain, and the
-// subtraction of the running maximum (forward) / of lse2 (backward) rides in the MFMA's C operand: no per-score FMA.
-template <int MAXW, bool MULTI, bool QS>
-__global__ __launch_bounds__(MAXW * 64) void attn_dkv_res_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
-                                                                const float* __restrict__ lse2,
-                                                                const float* __restrict__ delta, bf16* __restrict__ dqkv,
-                                                                int N, int H) {
-  constexpr int DH = 64, KS = 2, DB = 4;
-  extern __shared__ __attribute__((aligned(16))) char res_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), W = blockDim.x >> 6;
-  const int li = lane & 15, lg = lane >> 4;
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-  const int I = H * DH;
-  const int64_t ld = 3 * (int64_t)I;
-  const bf16* qbase = qkv + (int64_t)b * N * ld + h * DH;
-  const bf16* kbase = qbase + I;
-  const bf16* vbase = qbase + 2 * I;
-  const bf16* gbase = d_o + (int64_t)b * N * I + h * DH;
-  const int NP = (N + 31) & ~31, V = NP >> 5;
-  const int NP64 = (N + 63) & ~63;
-  char* qsm = res_smem;
-  char* gsm = res_smem + NP * 128;
-  float* Ls = reinterpret_cast<float*>(res_smem + 2 * NP * 128);
-  float* Ds = Ls + NP64;
-  const float scale = 1.0f / sqrtf((float)DH);
-  const float c = LOG2E * scale;
-  const float kscale = QS ? 1.0f / LOG2E : scale;  // dK = scale dS^T q = dS^T q' / log2(e)
-  AVF_PHASE_INIT();
-  // QS: `lse2` points at the NEGATED statistics the dQ kernel wrote (they become the C operand of the score MFMAs)
-  // the softmax statistics of the head's query rows: 64 floats per DMA piece, lse2 pieces then delta pieces
-  for (int j = wave; j < NP64 / 32; j += W) {
-    const int blk = j >> 1;
-    int row = blk * 64 + lane;
-    row = row < N ? row : N - 1;
-    const float* src = (j & 1) ? delta : lse2;
-    glds4(src + (int64_t)bh * N + row, reinterpret_cast<char*>(((j & 1) ? Ds : Ls) + blk * 64));
-  }
-  ResLoader loader;
-  loader.init(qbase, ld, qsm, gbase, I, gsm, NP, N, wave, W, lane);
-  ResOffsets off;
-  off.init(li, lg);
-
-  int grp = wave;
-  do {
-    const bool first_pass = !MULTI || grp == wave;
-    const int k0 = grp * 32;
-    bf16x8_t fk[2][KS], fv[2][KS];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int key = k0 + kb * 16 + li;
-        fk[kb][ks] = load_frag_global(kbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
-        fv[kb][ks] = load_frag_global(vbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
-      }
-    if (first_pass) loader.issue_until(16 * RES_A);
-
-    f32x4_t dvt[DB][2], dkt[DB][2];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        dvt[d][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        dkt[d][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      }
-
-    auto tile = [&](int t, auto tail_tag, auto feed_tag) {
-      constexpr bool TAIL = decltype(tail_tag)::value;
-      constexpr bool FEED = decltype(feed_tag)::value;
-      const int nqb = TAIL ? (N - t * 64 + 15) / 16 : 4;  // 16-query blocks with valid rows
-      const char* qt = qsm + t * 8192;
-      const char* gt = gsm + t * 8192;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        if (TAIL && 2 * s2 >= nqb) continue;
-        f32x4_t pm[2][2], dsm[2][2];  // P and dS, [q-block of the pair][key-block]
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          const int qb = 2 * s2 + h2;
-          pm[h2][0] = pm[h2][1] = dsm[h2][0] = dsm[h2][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-          if (!TAIL || qb < nqb) {
-            const float4 l4 = *reinterpret_cast<const float4*>(Ls + t * 64 + qb * 16 + 4 * lg);
-            const float4 d4 = *reinterpret_cast<const float4*>(Ds + t * 64 + qb * 16 + 4 * lg);
-            const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
-            f32x4_t p0 = {d4.x, d4.y, d4.z, d4.w}, p1 = p0;  // Ds holds -delta (written negated by the dQ kernel)
-            f32x4_t s0 = QS ? f32x4_t{l4.x, l4.y, l4.z, l4.w} : zero, s1 = s0;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-              const bf16x8_t fqr = lds_row_frag(qt + qb * 2048 + off.row[ks]);
-              const bf16x8_t fgr = lds_row_frag(gt + qb * 2048 + off.row[ks]);
-              s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqr, fk[0][ks], s0, 0, 0, 0);
-              s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqr, fk[1][ks], s1, 0, 0, 0);
-              p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgr, fv[0][ks], p0, 0, 0, 0);
-              p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgr, fv[1][ks], p1, 0, 0, 0);
-            }
-            const float lv[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const bool dead = TAIL && (t * 64 + qb * 16 + 4 * lg + r >= N);
-              const float e0 = dead ? 0.f : __builtin_amdgcn_exp2f(QS ? s0[r] : fmaf(s0[r], c, -lv[r]));
-              const float e1 = dead ? 0.f : __builtin_amdgcn_exp2f(QS ? s1[r] : fmaf(s1[r], c, -lv[r]));
-              pm[h2][0][r] = e0;
-              pm[h2][1][r] = e1;
-              dsm[h2][0][r] = e0 * p0[r];
-              dsm[h2][1][r] = e1 * p1[r];
-            }
-          }
-          if (FEED) loader.issue_one();
-        }
-        AVF_PHASE_MARK(2);
-        // dV^T[d][key] += dO^T P ; dK^T[d][key] += Q^T dS
-        const bf16x8_t pa0 = pack_pair(pm[0][0], pm[1][0]);
-        const bf16x8_t pa1 = pack_pair(pm[0][1], pm[1][1]);
-        const bf16x8_t da0 = pack_pair(dsm[0][0], dsm[1][0]);
-        const bf16x8_t da1 = pack_pair(dsm[0][1], dsm[1][1]);
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          const bf16x8_t fgt = lds_tr_frag(gt + s2 * 4096 + off.tr[d]);
-          const bf16x8_t fqt = lds_tr_frag(qt + s2 * 4096 + off.tr[d]);
-          dvt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgt, pa0, dvt[d][0], 0, 0, 0);
-          dvt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fgt, pa1, dvt[d][1], 0, 0, 0);
-          dkt[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqt, da0, dkt[d][0], 0, 0, 0);
-          dkt[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fqt, da1, dkt[d][1], 0, 0, 0);
-        }
-        if (FEED) loader.issue_one();
-        AVF_PHASE_MARK(4);
-      }
-      if (FEED) loader.issue_until(1 << 30);
-    };
-    AVF_PHASE_MARK(1);
-    res_sweep<MULTI>(N, first_pass, tile, [&] {
-      wait_all_loads();
-      __builtin_amdgcn_s_barrier();
-      AVF_PHASE_MARK(0);
-    });
-
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const int key = k0 + kb * 16 + li;
-      if (key < N) {
-        bf16* outk = dqkv + ((int64_t)b * N + key) * ld + I + h * DH;
-        bf16* outv = outk + I;
-store_row_pairs<DB>(outk, lg, [&](int d) { return dkt[d][kb] * kscale; });
-        store_row_pairs<DB>(outv, lg, [&](int d) { return dvt[d][kb]; });
       }
     }
     AVF_PHASE_MARK(7);
@@ -1471,8 +1155,8 @@ int attn_fwd_bf16_kind(int N, int dh) {
   int W = 0;
   return use_resident(N, dh) ? res_variant(N, &W) : ATTN_STREAM;
 }
-// ... and attn_bwd_bf16: the merged kernel (under a token mask always: its masked instantiation is a ragged one), the two
-// head-resident kernels, or delta + the two streaming kernels
+// ... and attn_bwd_bf16: the merged kernel (under a token mask always: its masked instantiation is a ragged one), or delta +
+// the two streaming kernels
 int attn_bwd_bf16_kind(int N, int dh, bool q_prescaled, bool masked, int* kb, bool* ragged) {
   *kb = 0;
   *ragged = false;
@@ -1481,7 +1165,7 @@ int attn_bwd_bf16_kind(int N, int dh, bool q_prescaled, bool masked, int* kb, bo
     if (masked) *ragged = true;
     return ATTN_MERGED;
   }
-  return attn_fwd_bf16_kind(N, dh);  // (the same split: use_resident and the row groups of N)
+  return ATTN_STREAM;
 }
 
 int attn_bf16_plan(int N, int dh, bool q_prescaled, bool masked, int* fwd, int* bwd) {
@@ -1546,7 +1230,7 @@ int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep
 bool attn_bwd_emits_mx8(int N, int dh, bool q_prescaled) { return attn_bwd_merged_ok(N, dh, q_prescaled); }
 
 int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv, float* delta, int B,
-                  int N, int H, int dh, hipStream_t s, bool q_prescaled, float* nlse, const void* keep, void* dq_q, void* dq_s) {
+                  int N, int H, int dh, hipStream_t s, bool q_prescaled, const void* keep, void* dq_q, void* dq_s) {
   AVF_REQUIRE(!dq_q || (attn_bwd_emits_mx8(N, dh, q_prescaled) && !keep),
               "attn_bwd_bf16: the MX-FP8 image of dqkv exists on the merged kernel only (N=%d dh=%d)", N, dh);
   AVF_REQUIRE(!keep || attn_masked_bf16_ok(N, dh, q_prescaled),
@@ -1564,20 +1248,6 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
   const int kind = attn_bwd_bf16_kind(N, dh, q_prescaled, keep != nullptr, &kb, &ragged);
   // (under a mask the merged kernel at every N <= 512; no fp8 image then: checked above)
   if (kind == ATTN_MERGED) return attn_bwd_merged(&ts, qkv, o, d_o, lse2, dqkv, B, N, H, s, keep, dq_q, dq_s);
-  if (kind != ATTN_STREAM) {  // head-resident: delta comes out of the dQ kernel
-    const size_t smem = (size_t)((N + 31) & ~31) * 128 * 2, smem_kv = smem + (size_t)((N + 63) & ~63) * 8;
-    AVF_REQUIRE(!q_prescaled || nlse, "attn_bwd_bf16: scratch for the negated statistics missing");
-    return with_res_variant(N, [&](auto mw, auto mu, int W) {
-      return with_bool(q_prescaled, [&](auto q) {
-        constexpr int MW = decltype(mw)::value;
-        constexpr bool MU = decltype(mu)::value, Q = decltype(q)::value;
-        AVF_TRY((res_launch<attn_dq_res_kernel<MW, MU, Q>>(&ts, "attn_dq_res", res_tag<MW, MU, Q>(), B * H, W, smem, s, qkv, o, d_o,
-                                                           lse2, delta, nlse, dqkv, N, H)));
-        return res_launch<attn_dkv_res_kernel<MW, MU, Q>>(&ts, "attn_dkv_res", res_tag<MW, MU, Q>(), B * H, W, smem_kv, s, qkv, d_o,
-                                                          Q ? (const float*)nlse : lse2, (const float*)delta, dqkv, N, H);
-      });
-    });
-  }
   AVF_TRY(attn_delta(AVF_BF16, o, d_o, delta, B, N, H, dh, s));
   const unsigned grid = (unsigned)(ceil_div(N, 128) * B * H);
   const int qs = q_prescaled ? 1 : 0;
@@ -1589,12 +1259,11 @@ int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* 
   });
 }
 
-int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta, float* nlse,
+int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta,
                          const void* keep, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled) {
   AVF_REQUIRE(keep, "attn_bwd_masked_bf16: no mask");
   if (attn_masked_bf16_ok(N, dh, q_prescaled))  // (as the forward chose)
-    return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, delta, B, N, H, dh, s, true, nlse,
-                         keep);
+    return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, delta, B, N, H, dh, s, true, keep);
   return attn_bwd_vec(AVF_BF16, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, keep, q_prescaled);
 }
 

@@ -3,8 +3,8 @@
 //
 // Reference: autograd of models/heads.py:222-237 (dots = q k^T * dh^-0.5, softmax over keys, out = attn v).
 //
-// The two head-resident kernels of attn_bf16.hip (dQ with the query on the lane, dK/dV with the key on the lane) each
-// recompute S = q k^T and dP = dO v^T: 14 matrix products for 10 nominal.  Here every (query, key) tile is visited once:
+// A dQ kernel and a dK/dV kernel (attn_bf16.hip's streaming pair: dQ with the query on the lane, dK/dV with the key on the
+// lane) each recompute S = q k^T and dP = dO v^T: 14 matrix products for 10 nominal.  Here every (query, key) tile is visited once:
 //
 //   one workgroup = 4 wavefronts (one per SIMD, the whole 512-register file each) = one (clip, head), N <= 512, dim_head 64;
 //   wave w OWNS key blocks [w KB, (w+1) KB) of 32 keys: dK^T and dV^T of its keys stay in 64 KB accumulators for the whole
@@ -732,18 +732,10 @@ int with_key_blocks(int KB, int N, F&& f) {
 
 }  // namespace
 
-// merged backward: dim_head 64, pre-scaled q, N <= 512 - the default at every such N since its epilogue stores went to 16 bytes
-// (back to back, B = 32: N = 128 11.6 us against 18.9 for the two head-resident kernels, 196: 23.1 / 24.2, 256: 26.3 / 29.3; TFormer's
-// 17 tokens: 0.438 -> 0.428 ms per step).  History of the threshold (AVF_ATTN_MERGED_MIN_N), from three key blocks per wave up (N >= 257):
-// back to back in the harness it wins at N = 512 (B = 32 / 64: 77.3 / 155 us against 80.1 / 160.2 us) and loses at N = 324
-// (46.2 against 44.2 us), but IN THE STEP the single launch - which reads q, k, v, dO once, not twice - is the faster one there
-// too: C2 (N = 324) 2.107 / 2.113 ms per step against 2.141 / 2.129 with the two kernels (same box, alternating runs).
-// AVF_ATTN_MERGED=0 turns it off, AVF_ATTN_MERGED_MIN_N moves the threshold.
-bool attn_bwd_merged_ok(int N, int dh, bool q_prescaled) {
-  static const int allow = tuning_int("AVF_ATTN_MERGED", 1);
-  static const int min_n = tuning_int("AVF_ATTN_MERGED_MIN_N", 1);
-  return allow && q_prescaled && dh == 64 && N <= 512 && N >= min_n;
-}
+// merged backward: dim_head 64, pre-scaled q, N <= 512 - the one kernel at every such N: a single launch that reads q, k, v
+// and dO once, where a dQ kernel followed by a dK/dV kernel reads them twice (the measurements that settled it:
+// DESIGN_HISTORY.md, "Head-resident attention backward retired").
+bool attn_bwd_merged_ok(int N, int dh, bool q_prescaled) { return q_prescaled && dh == 64 && N <= 512; }
 
 // key blocks of 32 keys per wave (four waves) for N tokens, and whether the last of them hold rows past N: the instantiation
 // attn_bwd_merged launches and avf_attn_plan reports

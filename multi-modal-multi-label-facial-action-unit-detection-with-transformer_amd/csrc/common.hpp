@@ -22,7 +22,7 @@ int check_launch(const char* what);
 // <file> - tools/shape_table.py joins it with a rocprofv3 kernel trace into the per-shape table under profiles/.
 bool shape_log_on();
 void shape_log(const char* fmt, ...);
-// Every tuning / A-B switch of the library (AVF_NT_WS, AVF_NT_TILE, AVF_ATTN_MERGED, ...: INTEGRATION.md lists them) is read
+// Every tuning / A-B switch of the library (AVF_NT_WS, AVF_NT_TILE, AVF_ATTN_RESIDENT, ...: INTEGRATION.md lists them) is read
 // through this: unless the process was started with AVF_TUNING=1 the switches do not exist - a product process runs ONE
 // dispatch, the one the parity tests exercised, whatever else is in its environment.
 inline const char* tuning_env(const char* name) {
@@ -665,8 +665,7 @@ int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, con
 int attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, float* dqkv, float* delta,
                  int B, int N, int H, int dh, hipStream_t s);
 // q_prescaled: the q columns of qkv already hold q * log2(e)/sqrt(dh) (the layer path: folded into the bf16 copy of
-// Wqkv's query rows, attn_q_prescale); the operator-level C entry points pass false.  nlse (backward, q_prescaled
-// only): B*H*N floats of scratch next to delta.
+// Wqkv's query rows, attn_q_prescale); the operator-level C entry points pass false.
 // single-launch forward of one layer for short sequences (layer_small.hip)
 bool small_layer_ok(int dtype, int tokens, int dim, int heads, int dim_head, int mlp_dim);
 int layer_fwd_small(int B, int N, int D, int H, int M, float eps, float score_scale, const avf_layer_params* p,
@@ -697,14 +696,14 @@ int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, in
 bool attn_masked_bf16_ok(int N, int dh, bool q_prescaled);  // head-resident forward + merged backward: dh 64, N <= 512, pre-scaled q
 // the masked attention core of a bf16, non-fp8 stack - the ONE place that picks its kernels (avf_layer_fwd / avf_layer_bwd and
 // the per-operator entry points avf_attn_fwd_masked_qs / avf_attn_bwd_masked_qs call it): the MFMA kernels where
-// attn_masked_bf16_ok holds, else the fp32-arithmetic ones on bf16 storage.  nlse: the B*H*N floats behind delta.
+// attn_masked_bf16_ok holds, else the fp32-arithmetic ones on bf16 storage.
 int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep, int B, int N, int H, int dh, hipStream_t s,
                          bool q_prescaled);
-int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta, float* nlse,
+int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta,
                          const void* keep, int B, int N, int H, int dh, hipStream_t s, bool q_prescaled);
 bool attn_fwd_emits_mx8(int N, int dh);  // mx_q / mx_s: MX-FP8 image of o, written by the head-resident kernel only
 int attn_bwd_bf16(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse2, bf16* dqkv, float* delta,
-                  int B, int N, int H, int dh, hipStream_t s, bool q_prescaled = false, float* nlse = nullptr,
+                  int B, int N, int H, int dh, hipStream_t s, bool q_prescaled = false,
                   const void* keep = nullptr, void* dq_q = nullptr, void* dq_s = nullptr);
 // dq_q / dq_s: MX-FP8 image of dqkv ([B N][3 I] e4m3 + [B N][3 I / 32] E8M0), written by the merged kernel only
 bool attn_bwd_emits_mx8(int N, int dh, bool q_prescaled);

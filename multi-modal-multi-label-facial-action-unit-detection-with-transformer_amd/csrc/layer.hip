@@ -238,7 +238,7 @@ size_t carve_work(const Dims& d, void* base, Work* w) {
   t.dx_mid = (float*)c.take(d.R * d.D * 4);
   t.dx_mid_lo = c.take(d.dt == AVF_BF16 ? d.R * d.D * 2 : 0);
   t.dx_out_lo = c.take(d.dt == AVF_BF16 ? d.R * d.D * 2 : 0);
-  t.delta = (float*)c.take((size_t)d.B * d.H * d.N * 4 * 2);  // delta, then the negated lse2 rows (bf16 backward)
+  t.delta = (float*)c.take((size_t)d.B * d.H * d.N * 4);
   t.ln_ws = c.take(layernorm_bwd_ws(d.R, d.D));
   t.ln_ws1 = c.take(layernorm_bwd_ws(d.R, d.D, d.N));  // LN1 partials (its fold may be deferred past LN2's; token-major: one row per token)
   t.cs_ws = c.take(work_colsum_bytes(d));
@@ -744,7 +744,7 @@ int LayerBwd::small() {
   const bool fuse_att = small_att_fused(d);
   if (!fuse_att)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
-                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), w.delta + (size_t)d.B * d.H * d.N));
+                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on()));
   SmallBwdBHost hb;
   hb.attention = fuse_att ? 1 : 0;
   hb.qkv = sv.qkv; hb.o = sv.o; hb.d_o = w.d_o; hb.lse2 = sv.lse2; hb.H = d.H;
@@ -805,7 +805,6 @@ int LayerBwd::mlp_half() {
 
 // ---- attention half: dWo, d_o, the attention backward (dqkv), the parity mode's grouped dW, dh1 -------------------------------
 int LayerBwd::attn_half() {
-  float* nlse = w.delta + (size_t)d.B * d.H * d.N;
   if (f32_drop0) AVF_TRY(mask_copy_f32(w.dx_mid, w.gm_m, d.R * d.D, s, dr.site0));  // to_out sees dx_mid through its site-0 mask
   if (!dw_grouped()) AVF_TRY(linear_dw(d, W.lin[kOut], gm, sv.o, g->w_out, w.gemm_ws, s));
   AVF_TRY(linear_dx(d, W.lin[kOut], Act{gm, w.mq, w.ms}, w.d_o, GemmArgs{}, s));
@@ -817,14 +816,14 @@ int LayerBwd::attn_half() {
   const bool dq_mx = d.mxb && dq_mx_on && !d.keep && (3 * d.I) % 128 == 0 && d.D % 128 == 0 &&
                      attn_bwd_emits_mx8(d.N, d.dh, attn_q_prescale_on());
   if (d.keep && lo && !d.mx)  // (attn_bwd_masked_bf16 chooses as the forward's attn_fwd_masked_bf16 did)
-    AVF_TRY(attn_bwd_masked_bf16(sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, nlse, d.keep, d.B, d.N, d.H, d.dh, s,
+    AVF_TRY(attn_bwd_masked_bf16(sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, d.keep, d.B, d.N, d.H, d.dh, s,
                                  attn_q_prescale_on()));
   else if (d.keep)
     AVF_TRY(attn_bwd_vec(d.dt, sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, d.B, d.N, d.H, d.dh, s, d.keep,
                          lo && attn_q_prescale_on()));
   else if (lo)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
-                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), nlse, nullptr, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr));
+                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), nullptr, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr));
   else
     AVF_TRY(attn_bwd_f32((const float*)sv.qkv, (const float*)sv.o, (const float*)w.d_o, sv.lse2, (float*)w.dqkv,
                          w.delta, d.B, d.N, d.H, d.dh, s));

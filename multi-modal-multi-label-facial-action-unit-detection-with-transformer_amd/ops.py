@@ -587,7 +587,7 @@ def attn_bwd(qkv, o, d_o, lse2, batch: int, tokens: int, heads: int, dim_head: i
     lib = _lib.load()
     qkv, o, d_o = qkv.contiguous(), o.contiguous(), d_o.contiguous()
     dqkv = torch.empty_like(qkv)
-    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head) * (2 if q_prescaled else 1), qkv.device)
+    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head), qkv.device)
     if q_prescaled:
         assert qkv.dtype == torch.bfloat16
         _lib.check(lib.avf_attn_bwd_qs(_ptr(qkv), _ptr(o), _ptr(d_o), _ptr(lse2), _ptr(dqkv), _ptr(ws), batch, tokens, heads,
@@ -605,7 +605,7 @@ ATTN_MERGED = 8
 def attn_plan(tokens: int, dim_head: int, q_prescaled: bool = False, masked: bool = False) -> dict:
     """Which kernels the bf16 attention core launches at this shape (avf_attn_plan, pure host code): attn_fwd / attn_bwd with
     this ``q_prescaled``, or with ``masked`` attn_fwd_masked / attn_bwd_masked(q_prescaled=True) and the layer itself.
-    dict(fwd = "res8" | "res12" | "res_multi" (head-resident) | "stream" | "f32" (fp32 arithmetic), bwd = the same names or
+    dict(fwd = "res8" | "res12" | "res_multi" (head-resident) | "stream" | "f32" (fp32 arithmetic), bwd = "stream" | "f32" |
     "merged", kb = key blocks per wave of the merged kernel (else 0), ragged = its last key block holds rows past tokens)."""
     fwd, bwd = C.c_int(-1), C.c_int(-1)
     _lib.check(_lib.load().avf_attn_plan(int(tokens), int(dim_head), int(bool(q_prescaled)), int(bool(masked)), C.byref(fwd),
@@ -663,7 +663,7 @@ def attn_bwd_masked(qkv, o, d_o, lse2, keep, batch: int, tokens: int, heads: int
     keep = keep.to(torch.uint8).contiguous()
     assert keep.shape == (batch, tokens)
     dqkv = torch.empty_like(qkv)
-    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head) * (2 if q_prescaled else 1), qkv.device)
+    ws = _bytes(lib.avf_attn_bwd_workspace_bytes(batch, tokens, heads, dim_head), qkv.device)
     if q_prescaled:
         assert qkv.dtype == torch.bfloat16
         _lib.check(lib.avf_attn_bwd_masked_qs(_ptr(qkv), _ptr(o), _ptr(d_o), _ptr(lse2), _ptr(dqkv), _ptr(ws), _ptr(keep), batch,

@@ -54,7 +54,7 @@ Bounds, per group g, || . || the Frobenius norm over g, U = 2^-24, K = max(N, dh
 
 Mutants, applied to the emulation (check() must refuse each): the table MUTANTS below and the emulate_* functions.
 
-The two run_* functions at the end are the only device code: the launches of the GPU file and of its child process, on
+The two run_* functions at the end are the only device code: the launches of the GPU file, on
 NaN-filled outputs, twice, compared bit for bit.
 
 ATTNSTAT maxima on an MI355X - the worst error / bound of each kernel family by part, with the case and the group (clip, head,
@@ -375,12 +375,13 @@ FWD_RAW = ((64, 33, "res8"), (64, 256, "res8"), (64, 324, "res12"), (64, 385, "r
            (64, 577, "stream"), (32, 200, "stream"), (128, 129, "stream"))      # (dim_head, N, kernel), qs = 0
 BWD_MERGED = {1: (1, 31, 32, 33, 97, 127, 128), 2: (129, 255, 256), 3: (257, 324, 383, 384), 4: (385, 500, 511, 512)}
 MXO_LENGTHS = (128, 129, 256, 384)
-BWD_RES_QS = ((513, "res_multi"), (575, "res_multi"), (576, "res_multi"))
-BWD_RES_RAW = ((33, "res8"), (256, "res8"), (257, "res12"), (384, "res12"), (385, "res_multi"), (576, "res_multi"))
-BWD_STREAM = tuple((64, N, qs) for N in (577, 640, 641) for qs in (1, 0)) + tuple((dh, N, 1) for dh, N in FWD_DH)
+# dim_head 64 on the streaming backward where the forward is still head-resident: past the merged kernel's 512 tokens with
+# pre-scaled q (qs = 1), and with raw q (qs = 0) from a single ragged 64-row tile (33) to the last resident length (576)
+BWD_STREAM64_RES_FWD = {1: (513, 575, 576), 0: (33, 256, 257, 384, 385, 576)}
+BWD_STREAM = (tuple((64, N, qs) for N in (577, 640, 641) for qs in (1, 0)) + tuple((dh, N, 1) for dh, N in FWD_DH) +
+              tuple((64, N, qs) for qs in (1, 0) for N in BWD_STREAM64_RES_FWD[qs]))
 # ... and `very_negative` at two ragged multi-pass lengths: the only operands that show an unmasked padded key past N = 129
 REGIME_CASES = tuple((r, N) for r in REGIME_NAMES for N in (324, 512)) + (("very_negative", 511), ("very_negative", 575))
-CHILD_LENGTHS = ((33, "res8"), (256, "res8"), (324, "res12"), (384, "res12"), (512, "res_multi"))  # AVF_ATTN_MERGED=0, qs = 1
 
 
 def all_cases():
@@ -393,8 +394,6 @@ def all_cases():
     for ns in BWD_MERGED.values():
         out |= {(N, 64, 1, None) for N in ns}
     out |= {(N, 64, 1, None) for N in MXO_LENGTHS}
-    out |= {(N, 64, 1, None) for N, _ in BWD_RES_QS + CHILD_LENGTHS}
-    out |= {(N, 64, 0, None) for N, _ in BWD_RES_RAW}
     out |= {(N, dh, qs, None) for dh, N, qs in BWD_STREAM}
     out |= {(N, 64, 1, r) for r, N in REGIME_CASES}
     return sorted(out, key=lambda c: (c[3] or "", c[1], c[2], c[0]))
@@ -474,7 +473,7 @@ def run_backward(A, qkv, o_in, lse2_in, d_o, B, N, H, dh, qs, mx8=False, tag="bw
     ops, lib = A.ops, A._lib.load()
     q, g, o, L = qkv.cuda().contiguous(), d_o.cuda().contiguous(), packed(o_in).cuda().contiguous(), lse2_in.cuda().contiguous()
     I = H * dh
-    ws = ops._bytes(lib.avf_attn_bwd_workspace_bytes(B, N, H, dh) * 2, q.device)
+    ws = ops._bytes(lib.avf_attn_bwd_workspace_bytes(B, N, H, dh), q.device)
 
     def outputs():
         out = (torch.full((B * N, 3 * I), float("nan"), dtype=torch.bfloat16, device="cuda"),)
@@ -519,11 +518,8 @@ ATTNSTAT_MAXIMA = {
     "bwd_merged_kb3": {"dq": (0.4809, 257, None, (0, 1, 7, 0)), "dk": (0.4818, 257, None, (0, 1, 10, 0)), "dv": (0.4845, 257, None, (1, 1, 13, 2))},
     "bwd_merged_kb4": {"dq": (0.4624, 385, None, (1, 1, 10, 3)), "dk": (0.4620, 385, None, (1, 1, 21, 3)), "dv": (0.4645, 385, None, (1, 1, 21, 3))},
     "bwd_merged_mx8": {"dq": (0.4923, 129, None, (1, 0, 5, 3)), "dk": (0.4911, 128, None, (1, 2, 1, 1)), "dv": (0.4934, 128, None, (1, 2, 4, 1))},
-    "bwd_res_qs": {"dq": (0.4499, 513, None, (1, 2, 8, 0)), "dk": (0.4507, 513, None, (1, 0, 10, 3)), "dv": (0.4996, 513, None, (0, 1, 23, 1))},
-    "bwd_res_qs_child": {"dq": (0.4953, 33, None, (1, 1, 1, 0)), "dk": (0.4954, 33, None, (1, 1, 0, 0)), "dv": (0.4977, 33, None, (1, 1, 0, 2))},
-    "bwd_res_raw": {"dq": (0.4955, 33, None, (1, 2, 0, 0)), "dk": (0.4952, 33, None, (0, 0, 0, 3)), "dv": (0.4977, 33, None, (1, 2, 0, 0))},
-    "bwd_stream64": {"dq": (0.4453, 577, None, (0, 1, 17, 3)), "dk": (0.4493, 577, None, (0, 1, 8, 0)), "dv": (0.4528, 577, None, (1, 0, 24, 2))},
-    "bwd_stream64_raw": {"dq": (0.4383, 640, None, (0, 0, 9, 0)), "dk": (0.4384, 577, None, (0, 1, 35, 2)), "dv": (0.4434, 640, None, (1, 2, 1, 2))},
+    "bwd_stream64": {"dq": (0.4499, 513, None, (1, 2, 8, 0)), "dk": (0.4507, 513, None, (1, 0, 10, 3)), "dv": (0.4544, 513, None, (0, 0, 11, 2))},
+    "bwd_stream64_raw": {"dq": (0.4955, 33, None, (1, 2, 0, 0)), "dk": (0.4952, 33, None, (0, 0, 0, 3)), "dv": (0.4977, 33, None, (1, 2, 0, 0))},
     "bwd_stream32": {"dq": (0.4986, 12, None, (1, 2, 0, 0)), "dk": (0.4985, 12, None, (1, 2, 0, 1)), "dv": (0.4993, 12, None, (0, 2, 0, 1))},
     "bwd_stream128": {"dq": (0.4882, 17, None, (1, 1, 0, 7)), "dk": (0.4905, 17, None, (1, 1, 0, 6)), "dv": (0.5133, 129, None, (1, 1, 3, 5))},
     "masked_f32": {"o": (0.3974, 40, None, (1, 0, 2, 0)), "lse2": (0.0172, 40, None, (1, 1, 24)), "dq": (0.4466, 40, None, (0, 0, 2, 0)),

@@ -103,8 +103,8 @@ FAMILIES_FWD = {
 }
 FAMILIES_BWD = {
     **{f"bwd_merged_kb{kb}": (64, 1, ns) for kb, ns in K.BWD_MERGED.items()},
-    "bwd_res_qs": (64, 1, tuple(N for N, _ in K.BWD_RES_QS)),
-    "bwd_res_raw": (64, 0, tuple(N for N, _ in K.BWD_RES_RAW)),
+    "bwd_stream64_qs_res_fwd": (64, 1, K.BWD_STREAM64_RES_FWD[1]),
+    "bwd_stream64_raw_res_fwd": (64, 0, K.BWD_STREAM64_RES_FWD[0]),
     "bwd_stream64_qs": (64, 1, (577, 640, 641)), "bwd_stream64_raw": (64, 0, (577, 640, 641)),
     "bwd_stream32": (32, 1, tuple(N for dh, N in K.FWD_DH if dh == 32)),
     "bwd_stream128": (128, 1, tuple(N for dh, N in K.FWD_DH if dh == 128)),
@@ -192,10 +192,6 @@ def test_plan_query_names_the_kernel_of_every_case():
             assert (p["bwd"], p["kb"], p["ragged"]) == ("merged", kb, N != 128 * kb), (kb, N, p)
     for N in K.MXO_LENGTHS:
         assert plan(N, 64, True)["bwd"] == "merged" and A._lib.load().avf_attn_bwd_emits_mx8(N, 64) == 1
-    for N, kind in K.BWD_RES_QS:
-        assert plan(N, 64, True)["bwd"] == kind, (N, kind)
-    for N, kind in K.BWD_RES_RAW:
-        assert plan(N, 64, False)["bwd"] == kind, (N, kind)
     for dh, N, qs in K.BWD_STREAM:
         assert plan(N, dh, bool(qs))["bwd"] == "stream", (dh, N, qs)
     # under a mask: what avf_attn_masked_on_mfma says, the merged kernel's masked (ragged) instantiation

@@ -1,5 +1,8 @@
 """CPU (no GPU needed): the sizes and the byte layout of a layer's buffers are pinned, as literal numbers recorded
-from the build BEFORE the layer orchestration was regrouped around one description per Linear.
+from the build BEFORE the layer orchestration was regrouped around one description per Linear.  One change since: the
+workspace's `delta` block holds B*H*N floats, not twice that (its second half was scratch of the retired head-resident
+attention backward), so every workspace size and every workspace offset behind `delta` went down by
+align256(8 B H N) - align256(4 B H N), and nothing else moved.
 
 - The size queries (host code) for one configuration per layer mode: a changed alignment, piece size or workspace
   maximum shows here.  They cannot see equal-sized pieces changing places.
@@ -57,22 +60,22 @@ QUERIES = ("avf_layer_saved_bytes", "avf_layer_lowp_bytes", "avf_layer_workspace
 
 # (saved, lowp, workspace, grad_stream, dw_block, layers_dw_workspace of 1 layer, ... of 4 layers)
 EXPECTED = {
-    "f32": (1132288, 0, 1057024, 51200, 0, 0, 0),
-    "f32_drop": (1132288, 0, 1261824, 51200, 0, 0, 0),
-    "bf16_gs16": (620288, 524288, 812288, 51200, 604160, 0, 0),
-    "bf16_drop_f32stream": (620288, 524288, 812288, 51200, 0, 0, 0),
-    "bf16_resid16": (569088, 524288, 812288, 51200, 604160, 0, 0),
-    "bf16_resid16_drop": (569088, 524288, 914688, 102400, 0, 0, 0),
-    "mx8_fwd": (1579008, 17432576, 2359296, 131072, 0, 0, 0),
-    "mx8": (1579008, 17432576, 2832384, 198656, 0, 0, 0),
-    "mask_bf16": (620288, 524288, 812288, 51200, 0, 0, 0),
-    "mask_bf16_4x32": (621824, 524288, 815360, 51200, 0, 0, 0),
-    "small_n12": (75264, 524288, 113408, 6144, 0, 0, 0),
-    "deferred_128rows": (363520, 524288, 522240, 32768, 389120, 0, 0),
-    "deferred_16384rows": (185335808, 13107200, 234913792, 16777216, 132153344, 33554432, 0),
-    "identity_to_out": (414720, 196608, 465152, 25600, 0, 0, 0),
-    "identity_to_out_f32": (773120, 0, 735488, 25600, 0, 0, 0),
-    "ws_k512": (1447936, 13107200, 2088960, 131072, 1556480, 0, 0),
+    "f32": (1132288, 0, 1055488, 51200, 0, 0, 0),
+    "f32_drop": (1132288, 0, 1260288, 51200, 0, 0, 0),
+    "bf16_gs16": (620288, 524288, 810752, 51200, 604160, 0, 0),
+    "bf16_drop_f32stream": (620288, 524288, 810752, 51200, 0, 0, 0),
+    "bf16_resid16": (569088, 524288, 810752, 51200, 604160, 0, 0),
+    "bf16_resid16_drop": (569088, 524288, 913152, 102400, 0, 0, 0),
+    "mx8_fwd": (1579008, 17432576, 2355200, 131072, 0, 0, 0),
+    "mx8": (1579008, 17432576, 2828288, 198656, 0, 0, 0),
+    "mask_bf16": (620288, 524288, 810752, 51200, 0, 0, 0),
+    "mask_bf16_4x32": (621824, 524288, 812288, 51200, 0, 0, 0),
+    "small_n12": (75264, 524288, 113152, 6144, 0, 0, 0),
+    "deferred_128rows": (363520, 524288, 521216, 32768, 389120, 0, 0),
+    "deferred_16384rows": (185335808, 13107200, 234389504, 16777216, 132153344, 33554432, 0),
+    "identity_to_out": (414720, 196608, 464384, 25600, 0, 0, 0),
+    "identity_to_out_f32": (773120, 0, 734720, 25600, 0, 0, 0),
+    "ws_k512": (1447936, 13107200, 2084864, 131072, 1556480, 0, 0),
 }
 
 
