@@ -4,6 +4,7 @@
 #include <stdarg.h>
 
 #include "common.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 
@@ -115,21 +116,18 @@ __global__ void selftest_mfma_f32_kernel(const float* a, const float* b, float* 
   for (int r = 0; r < 4; ++r) c[(4 * lg + r) * 16 + li] = acc[r];
 }
 
-// ds_read_b64_tr_b16 on a [32 rows][16 cols] bf16 tile (32-byte rows): lane l (i=l&15, g=l>>4) issues two
-// reads with row blocks 4g.. (h=0) and 16+4g.. (h=1), address = &T[blk + (i>>2)][4*(i&3)], and stores
-// its 8 received values: out[l][h*4 + e].  Expected (kernels' assumption): out[l][h*4+e] = T[16h+4g+e][i].
+// The kernels' transposed fragment (tr_frag, mfma_frag.hpp) on a [32 rows][16 cols] bf16 tile (32-byte rows): lane l
+// (i=l&15, g=l>>4) issues two ds_read_b64_tr_b16 with row blocks 4g.. (h=0) and 16+4g.. (h=1), address =
+// &T[blk + (i>>2)][4*(i&3)], and stores its 8 received values: out[l][h*4 + e].  Expected (the k-slot map the kernels
+// assume): out[l][h*4+e] = T[16h+4g+e][i].
 __global__ void selftest_tr16_kernel(const bf16* tile, bf16* out) {
   __shared__ __attribute__((aligned(16))) bf16 T[32 * 16];
   const int l = threadIdx.x, li = l & 15, lg = l >> 4;
   for (int i = l; i < 32 * 16; i += 64) T[i] = tile[i];
   __syncthreads();
+  const s16x8_t v = __builtin_bit_cast(s16x8_t, tr_frag<32>((const lds_char*)T, 0, 0, li, lg));
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const bf16* src = &T[(16 * h + 4 * lg + (li >> 2)) * 16 + 4 * (li & 3)];
-    s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)src);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) out[l * 8 + h * 4 + e].x = (uint16_t)v[e];
-  }
+  for (int j = 0; j < 8; ++j) out[l * 8 + j].x = (uint16_t)v[j];
 }
 
 }  // namespace avf

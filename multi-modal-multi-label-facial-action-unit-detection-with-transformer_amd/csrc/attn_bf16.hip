@@ -11,8 +11,7 @@
 //                  B operand of  O^T = V^T P^T  /  dQ^T = K^T dS^T ; V^T / K^T fragments come from
 //                  ds_read_b64_tr_b16 on the row-major tile.
 //   dK / dV      : S = Q K^T      -> lane owns a key column;  dV^T = dO^T P,  dK^T = Q^T dS.
-// k-slot map of a packed accumulator pair / transposed fragment (32 reduction rows per k-step):
-//   slot j of lane group g  <->  row 16*(j>>2) + 4*g + (j&3).
+// (k-slot map of a packed accumulator pair / transposed fragment: mfma_frag.hpp)
 // Streaming kernels (attn_{fwd,dq,dkv}_bf16_kernel<DH, NW>): a workgroup owns 128 query (key) rows as NW waves of 128/NW.
 // dim_head 32 / 64: NW = 4 (32 rows per wave, two 16-row blocks).  dim_head 128: NW = 8 (16 rows per wave) - with two blocks
 // per wave the dK/dV kernel's accumulators alone take 128 registers and all three kernels spill at 256; with one they need
@@ -26,58 +25,18 @@
 #include <type_traits>
 
 #include "attn_dispatch.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 
 namespace {
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-// Phase stamps for tools/diag/attn_phases.hip (that file defines these and includes this one); nothing in the product.
-#ifndef AVF_PHASE_MARK
-#define AVF_PHASE_INIT()
-#define AVF_PHASE_MARK(slot)
-#define AVF_PHASE_FLUSH()
-#endif
-
-// 1-D grid of nblk * B*H blocks.  Hardware deals consecutive block ids round-robin over the 8 XCDs; this
-// bijection hands each XCD a CONTIGUOUS range of logical ids, so the row blocks of one (batch, head) - which
+// 1-D grid of nblk * B*H blocks in the per-XCD order (xcd_remap), so the row blocks of one (batch, head) - which
 // share that head's K/V (or Q/dO) - run on one XCD and hit in its L2 instead of re-fetching from HBM.
 __device__ __forceinline__ void block_coords(int nblk, int& blk, int& bh) {
-  const int nwg = gridDim.x, id = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, x = id & 7;
-  const int lid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   bh = lid / nblk;
   blk = lid - bh * nblk;
-}
-
-template <int LD>
-__device__ __forceinline__ bf16x8_t tr_frag(const lds_char* tile, int row_base, int col_base, int li, int lg) {
-  const lds_char* p0 = tile + (row_base + 4 * lg + (li >> 2)) * LD + (col_base + 4 * (li & 3)) * 2;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * LD));
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-template <int LD>
-__device__ __forceinline__ bf16x8_t row_frag(const char* tile, int row, int col) {
-  return *reinterpret_cast<const bf16x8_t*>(tile + row * LD + col * 2);
-}
-
-__device__ __forceinline__ bf16x8_t pack_pair(const f32x4_t& a, const f32x4_t& b) {
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-  u32x4_t r = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-__device__ __forceinline__ bf16x8_t load_frag_global(const bf16* p, bool ok) {
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (ok) v = *reinterpret_cast<const uint4*>(p);
-  return __builtin_bit_cast(bf16x8_t, v);
 }
 
 // stage ROWS rows x DH bf16 from global (row stride ld elements) into an LDS tile with row stride LD bytes;
@@ -128,28 +87,6 @@ __device__ __forceinline__ void store_row_pairs(bf16* row, int lg, Get&& get) {
   }
 }
 
-__device__ __forceinline__ float vmax(float a, float b) {  // v_max_f32 without the NaN-canonicalising pre-ops
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// max over the four lanes {li, li+16, li+32, li+48} (the four key groups of one query column), VALU only
-__device__ __forceinline__ float colmax4(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = vmax(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return vmax(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
-// sum over the four lanes {li, li+16, li+32, li+48}
-__device__ __forceinline__ float colsum4(float v) {
-  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
 template <int DH, int NW = 4>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
                                                                      float* __restrict__ lse2, int /*B*/, int N, int H, int qs) {
@@ -180,7 +117,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int q = q0 + qb * 16 + li;
-      fq[qb][ks] = load_frag_global(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, q < N);
+      fq[qb][ks] = ldg_frag(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, q < N);
     }
 
   f32x4_t ot[DB][QB];
@@ -248,7 +185,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf
             if (TAIL && (t * 64 + kb * 16 + 4 * lg + r >= N)) st[kb][qb][r] = -INFINITY;
             tmax = fmaxf(tmax, st[kb][qb][r]);  // raw scores: the scale c > 0 commutes with max
           }
-        tmax = colmax4(tmax);
+        tmax = groups_max_swap(tmax);
         const float mn = fmaxf(m[qb], tmax * c);
         const float alpha = __builtin_amdgcn_exp2f(m[qb] - mn);
         m[qb] = mn;
@@ -300,7 +237,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_bf16_kernel(const bf
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     float l = lsum[qb];
-    l = colsum4(l);
+    l = groups_sum_swap(l);
     const int q = q0 + qb * 16 + li;
     if (q < N) {
       const float inv = 1.0f / l;
@@ -338,50 +275,22 @@ constexpr int RES_MAX_N = 576;    // (N rounded to 32) * 256 B of K and V images
 constexpr int RES_A = 1;          // tiles whose DMA is issued before any compute (2 gave the same forward time)
 constexpr float RES_TAU = 6.0f;   // log2 of the largest probability kept before a rescale
 
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  typedef __attribute__((address_space(1))) const void gptr_t;
-  typedef __attribute__((address_space(3))) void lptr_t;
-  __builtin_amdgcn_global_load_lds((gptr_t*)g, (lptr_t*)l, 16, 0, 0);
-}
-
-// The same LDS-DMA issued as inline asm.  hipcc (ROCm 7.2) drains vmcnt to 0 in front of every compiler-visible LDS read
-// that follows a compiler-visible LDS-DMA (its wait-count pass takes the DMA for a store that may alias the read): the
-// pieces fed from hooks inside the first tile's compute then cost a full memory round trip each.  An asm DMA is opaque to
-// that pass; the kernels' own wait_all_loads() + s_barrier order the LDS reads of a tile after its arrival, and vmcnt is
-// in-order, so the compiler's own counted waits for its global loads only become more conservative.  AVF_ATTN_DMA_ASM=0
-// at build time (-DAVF_ATTN_DMA_ASM=0) restores the builtin.
+// The DMA of the head-resident forward is the asm form (glds16_asm; mfma_frag.hpp says why): with the builtin the pieces
+// fed from hooks inside the first tile's compute cost a full memory round trip each.  AVF_ATTN_DMA_ASM=0 at build time
+// (-DAVF_ATTN_DMA_ASM=0) restores the builtin.
 #ifndef AVF_ATTN_DMA_ASM
 #define AVF_ATTN_DMA_ASM 1
 #endif
-__device__ __forceinline__ void glds16_res(const void* g, char* l) {
+__device__ __forceinline__ void res_dma16(const void* g, char* l) {
 #if AVF_ATTN_DMA_ASM
-  typedef __attribute__((address_space(3))) char lds_c;
-  const uint32_t la = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_c*)l);
-  uint32_t keep;  // m0 is a reserved register: saved and restored, so whatever the compiler keeps in it survives
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(la), "v"(g)
-               : "memory");
+  glds16_asm(g, l);
 #else
-  glds16(g, l);
+  glds<16>(g, l);
 #endif
 }
 
-__device__ __forceinline__ void wait_all_loads() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 __device__ __forceinline__ bf16x8_t ones_frag() {
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
   u32x4_t r = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-__device__ __forceinline__ bf16x8_t lds_row_frag(const char* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-
-__device__ __forceinline__ bf16x8_t lds_tr_frag(const char* p) {  // rows +0 and +16 of a 32-row k-step
-  const lds_char* q = (const lds_char*)p;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)q);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(q + 16 * 128));
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, r);
 }
 
@@ -408,8 +317,8 @@ struct ResLoader {
       const int i = cur >> 1;
       int row = i * 8 + lrow;
       row = row < N ? row : N - 1;
-      if (cur & 1) glds16_res(b + (int64_t)row * ldb + chunk * 8, lb + i * 1024);
-      else glds16_res(a + (int64_t)row * lda + chunk * 8, la + i * 1024);
+      if (cur & 1) res_dma16(b + (int64_t)row * ldb + chunk * 8, lb + i * 1024);
+      else res_dma16(a + (int64_t)row * lda + chunk * 8, la + i * 1024);
       cur += W;
     }
   }
@@ -456,18 +365,6 @@ __device__ __forceinline__ void res_sweep(int N, bool first, TileFn&& tile, Sync
   if (nfull < nt && t0 <= nfull) tile(nfull, std::true_type{}, std::false_type{});
 }
 
-// 4 x 4 transpose of one dword between the register index and the lane group (lanes l, l + 16, l + 32, l + 48):
-// in: a[d] of lane group g = X[d][g]; out: a[k] of lane group g = X[g][k]
-__device__ __forceinline__ void tr4x4(uint32_t (&a)[4]) {
-  // lane groups g <-> g ^ 1: even groups keep X[d0][g] and take X[d0][g + 1], odd groups take X[d1][g - 1] and keep X[d1][g]
-  const auto p01 = __builtin_amdgcn_permlane16_swap(a[0], a[1], false, false);
-  const auto p23 = __builtin_amdgcn_permlane16_swap(a[2], a[3], false, false);
-  // lane groups g <-> g ^ 2 on the first / second words of the two pairs
-  const auto x = __builtin_amdgcn_permlane32_swap(p01[0], p23[0], false, false);
-  const auto y = __builtin_amdgcn_permlane32_swap(p01[1], p23[1], false, false);
-  a[0] = x[0]; a[1] = y[0]; a[2] = x[1]; a[3] = y[1];
-}
-
 // MULTI: more 32-row groups than waves (each wave loops over its groups); otherwise exactly one group per wave.
 // QS: the q columns already carry log2(e)/sqrt(dh) (layer path) - the scores leave the MFMA in the log2 domain, and the
 // subtraction of the running maximum rides in the MFMA's C operand: no per-score FMA.
@@ -507,7 +404,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
   if constexpr (MASKED) {
     uint8_t* kw = reinterpret_cast<uint8_t*>(res_smem + 2 * NP * 128);
     for (int i = tid; i < ((N + 63) & ~63); i += blockDim.x) kw[i] = i < N ? keep[(int64_t)b * N + i] : (uint8_t)0;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the first arrival barrier of the sweep publishes them)
+    wait_lgkmcnt<0>();  // (the first arrival barrier of the sweep publishes them)
   }
 
   int grp = wave;
@@ -529,7 +426,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int q = q0 + qb * 16 + li;
-        fq[qb][ks] = load_frag_global(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, q < N);
+        fq[qb][ks] = ldg_frag(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, q < N);
       }
     if (first_pass) loader.issue_until(16 * RES_A);
 
@@ -558,7 +455,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
         if (!TAIL || kb < nkb) {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8_t fk = lds_row_frag(kt + kb * 2048 + off.row[ks]);
+            const bf16x8_t fk = row_frag(kt + kb * 2048 + off.row[ks]);
             st[kb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[0][ks], st[kb][0], 0, 0, 0);
             st[kb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk, fq[1][ks], st[kb][1], 0, 0, 0);
           }
@@ -574,7 +471,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
       if constexpr (VPF) {
         if (!TAIL || nkb > 0) {
 #pragma unroll
-          for (int d = 0; d < DB; ++d) fvp[0][d] = lds_tr_frag(vt + off.tr[d]);
+          for (int d = 0; d < DB; ++d) fvp[0][d] = tr_frag<128>((const lds_char*)(vt + off.tr[d]));
         }
       }
       if constexpr (QS) {
@@ -603,7 +500,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
               }
               tmax = fmaxf(tmax, st[kb][qb][r]);
             }
-          cm[qb] = colmax4(tmax);
+          cm[qb] = groups_max_swap(tmax);
           if constexpr (MASKED) grow = grow || (cen[qb] ? cm[qb] > RES_TAU : cm[qb] > -1.0e30f);  // (a tile may hold no kept key)
           else grow = grow || (cm[qb] > RES_TAU);
         }
@@ -654,7 +551,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
             if (TAIL && (t * 64 + kb * 16 + 4 * lg + r >= N)) st[kb][qb][r] = -INFINITY;
             tmax = fmaxf(tmax, st[kb][qb][r]);
           }
-        cand[qb] = colmax4(tmax) * c;
+        cand[qb] = groups_max_swap(tmax) * c;
         grow = grow || (cand[qb] > m[qb] + RES_TAU);
       }
       if (__builtin_amdgcn_ballot_w64(grow) != 0) {  // wave-uniform
@@ -687,14 +584,14 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
         if constexpr (VPF) {
           if (s2 == 0 && (!TAIL || nkb > 2)) {
 #pragma unroll
-            for (int d = 0; d < DB; ++d) fvp[1][d] = lds_tr_frag(vt + 4096 + off.tr[d]);
+            for (int d = 0; d < DB; ++d) fvp[1][d] = tr_frag<128>((const lds_char*)(vt + 4096 + off.tr[d]));
           }
         }
 #pragma unroll
         for (int d = 0; d < DB; ++d) {
           bf16x8_t fv;
           if constexpr (VPF) fv = fvp[s2][d];
-          else fv = lds_tr_frag(vt + s2 * 4096 + off.tr[d]);
+          else fv = tr_frag<128>((const lds_char*)(vt + s2 * 4096 + off.tr[d]));
           ot[d][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, p0, ot[d][0], 0, 0, 0);
           ot[d][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv, p1, ot[d][1], 0, 0, 0);
         }
@@ -707,7 +604,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
     };
     AVF_PHASE_MARK(1);
     res_sweep<MULTI>(N, first_pass, tile, [&] {
-      wait_all_loads();
+      wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       AVF_PHASE_MARK(0);
     });
@@ -751,8 +648,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_res_kernel(const bf16* __r
           float am = 0.f;
 #pragma unroll
           for (int r = 0; r < 4; ++r) am = fmaxf(am, fmaxf(fabsf(vb[2 * blk][r]), fabsf(vb[2 * blk + 1][r])));
-          am = fmaxf(am, __shfl_xor(am, 16, 64));
-          am = fmaxf(am, __shfl_xor(am, 32, 64));
+          am = groups_max_shfl(am);
           float sinv;
           sb[blk] = mx8_scale_byte(am, &sinv);
           qw[2 * blk] = mx8_pack4(vb[2 * blk], sinv);
@@ -808,8 +704,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_dq_bf16_kernel(const bf1
     const bool ok = q < N;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      fq[qb][ks] = load_frag_global(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, ok);
-      fg[qb][ks] = load_frag_global(gbase + (int64_t)q * I + ks * 32 + 8 * lg, ok);
+      fq[qb][ks] = ldg_frag(qbase + (int64_t)q * ld + ks * 32 + 8 * lg, ok);
+      fg[qb][ks] = ldg_frag(gbase + (int64_t)q * I + ks * 32 + 8 * lg, ok);
     }
     L[qb] = ok ? lse2[(int64_t)bh * N + q] : 0.f;
     dl[qb] = ok ? delta[(int64_t)bh * N + q] : 0.f;
@@ -942,8 +838,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_dkv_bf16_kernel(const bf
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int key = k0 + kb * 16 + li;
-      fk[kb][ks] = load_frag_global(kbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
-      fv[kb][ks] = load_frag_global(vbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
+      fk[kb][ks] = ldg_frag(kbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
+      fv[kb][ks] = ldg_frag(vbase + (int64_t)key * ld + ks * 32 + 8 * lg, key < N);
     }
   f32x4_t dvt[DB][KB], dkt[DB][KB];
 #pragma unroll

@@ -33,28 +33,15 @@
 #include <type_traits>
 
 #include "attn_dispatch.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(8))) short m_s16x8_t;
-typedef __attribute__((ext_vector_type(4))) uint32_t m_u32x4_t;
-typedef __attribute__((address_space(3))) char m_lds_char;
-
-// Phase stamps for tools/diag/attn_m4_phases.hip (that file defines these and includes this one); nothing in the product.
-#ifndef AVF_PHASE_MARK
-#define AVF_PHASE_INIT()
-#define AVF_PHASE_MARK(slot)
-#define AVF_PHASE_FLUSH()
-#endif
-
 #ifndef AVF_M4_MAXKB
 #define AVF_M4_MAXKB 4
 #endif
-
-constexpr float kLog2E = 1.4426950408889634f;
 
 #define AVF_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 #define AVF_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
@@ -78,24 +65,6 @@ __device__ __forceinline__ int m_swz(int row) { return (((row >> 1) & 1) << 2) |
 // 8-byte stores of 16 consecutive keys hit distinct banks, with (key>>2)&1 on slot bit 2, so the two 4-row blocks a
 // 16x16x32 transposed read takes from rows k .. k+3 and k+4 .. k+7 use different halves of their rows.
 __device__ __forceinline__ int m_txor(int key) { return (((key >> 2) & 1) << 2) | (((key >> 1) & 1) << 1) | ((key >> 3) & 1); }
-
-__device__ __forceinline__ void m_glds16(const void* g, char* l) {  // LDS-DMA, opaque to hipcc's wait-count pass
-  const uint32_t la = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(m_lds_char*)l);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(la), "v"(g)
-               : "memory");
-}
-
-__device__ __forceinline__ bf16x8_t m_row_frag(const char* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-
-__device__ __forceinline__ bf16x8_t m_tr_frag(const char* p0, const char* p1) {
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(const m_lds_char*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(const m_lds_char*)p1);
-  m_s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
 
 __device__ __forceinline__ float m_dot8(const uint4& x, const uint4& y) {
   const uint32_t a[4] = {x.x, x.y, x.z, x.w}, b[4] = {y.x, y.y, y.z, y.w};
@@ -235,7 +204,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
   for (int pc = wave; pc < 16 * KB; pc += 4) {
     const int row = pc * 8 + lrow;
     const int src = row < N ? row : N - 1;
-    m_glds16(kbase + (int64_t)src * ld + ((lslot ^ m_swz(row)) << 3), kimg + pc * 1024);
+    glds16_asm(kbase + (int64_t)src * ld + ((lslot ^ m_swz(row)) << 3), kimg + pc * 1024);
   }
   auto issue_slice = [&](int s) {  // wave w brings rows 8 w .. 8 w + 7 of the slice's Q and dO
     char* slot = ring + (s & 1) * 8192;
@@ -243,8 +212,8 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     int row = 32 * s + lr;
     row = row < N ? row : N - 1;
     const int ch = (lslot ^ m_swz(lr)) << 3;
-    m_glds16(qbase + (int64_t)row * ld + ch, slot + wave * 1024);
-    m_glds16(gbase + (int64_t)row * I + ch, slot + 4096 + wave * 1024);
+    glds16_asm(qbase + (int64_t)row * ld + ch, slot + wave * 1024);
+    glds16_asm(gbase + (int64_t)row * I + ch, slot + 4096 + wave * 1024);
   };
   issue_slice(0);
   // V fragments of the wave's keys (B operand of dP = dO V^T: lane (r, hf) holds V[key r][16 ks + 8 hf ..])
@@ -290,7 +259,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
   // the builtin form is VISIBLE to hipcc's wait-count pass (it retires the V fragment loads in its books: with the asm form
   // alone it put a vmcnt(0) in front of their first use in EVERY slice, exposing the latency of that slice's own DMA)
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt unconstrained
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
   if (N < NKB * 32) {  // zero the K rows past N (wave-uniform condition)
     for (int idx = N * 8 + tid; idx < NKB * 32 * 8; idx += 256)
@@ -315,14 +284,14 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
   int kopq = 0;
   bf16x8_t qa[4], ga[4], kf[4];
   f32x16_t sacc, pacc;
-  m_u32x4_t pk[2], dk[2];  // bf16 pairs of P and dS of the block whose stage C is pending, one k-step (8 registers) each
+  u32x4_t pk[2], dk[2];  // bf16 pairs of P and dS of the block whose stage C is pending, one k-step (8 registers) each
 
   // The row statistics enter S and dP through the matrix pipe: a fifth k-step whose A operand holds, for query row r, the
   // three bf16 pieces hi + mid + lo = -lse2[r] (exactly: 3 x 8 significand bits) in its first three k slots and whose B
   // operand is 1 there - S = Q K^T + (-lse2) 1^T.  Loading them into the C operand instead (the first version) cost 8
   // broadcast ds_read_b128 per key block and made the first MFMA of every block wait for LDS; this costs two MFMAs.
   bf16x8_t nlA, ndA;
-  const bf16x8_t onesB = __builtin_bit_cast(bf16x8_t, m_u32x4_t{hf ? 0u : 0x3F803F80u, hf ? 0u : 0x00003F80u, 0u, 0u});
+  const bf16x8_t onesB = __builtin_bit_cast(bf16x8_t, u32x4_t{hf ? 0u : 0x3F803F80u, hf ? 0u : 0x00003F80u, 0u, 0u});
   auto split3 = [&](float x) {
     const float hi = __uint_as_float(__float_as_uint(x) & 0xffff0000u);
     const float r1 = x - hi;
@@ -330,12 +299,12 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     const float lo = r1 - mid;
     const uint32_t w0 = (__float_as_uint(hi) >> 16) | (__float_as_uint(mid) & 0xffff0000u);
     const uint32_t w1 = pack_bf16x2(lo, 0.f);
-    return __builtin_bit_cast(bf16x8_t, m_u32x4_t{hf ? 0u : w0, hf ? 0u : w1, 0u, 0u});
+    return __builtin_bit_cast(bf16x8_t, u32x4_t{hf ? 0u : w0, hf ? 0u : w1, 0u, 0u});
   };
   auto load_kf = [&](int j) {
     const char* kblk = kimg + (kb0 + j) * 4096 + kopq;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) kf[ks] = m_row_frag(kblk + off_row[ks]);
+    for (int ks = 0; ks < 4; ++ks) kf[ks] = row_frag(kblk + off_row[ks]);
   };
   // stage A(j): ten MFMAs, no operand fresher than a whole phase
   auto stage_a = [&](auto jtag) {
@@ -366,7 +335,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     }
   };
   // stage B in eight chunks of six VALU instructions: chunk c turns elements 2 c, 2 c + 1 into one dword of P and of dS
-  auto b_chunk = [&](int c, m_u32x4_t (&pkn)[2], m_u32x4_t (&dkn)[2]) {
+  auto b_chunk = [&](int c, u32x4_t (&pkn)[2], u32x4_t (&dkn)[2]) {
     const float p0 = __builtin_amdgcn_exp2f(sacc[2 * c]), p1 = __builtin_amdgcn_exp2f(sacc[2 * c + 1]);
     float d0 = p0 * pacc[2 * c], d1 = p1 * pacc[2 * c + 1];
     if constexpr (MASKED) {  // no gradient through the (filled) scores of a dropped query
@@ -376,7 +345,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     pkn[c >> 2][c & 3] = pack_bf16x2(p0, p1);
     dkn[c >> 2][c & 3] = pack_bf16x2(d0, d1);
   };
-  auto write_t = [&](auto jtag, const m_u32x4_t (&d)[2]) {  // dS^T of block j: registers 4 g .. 4 g + 3 are dwords 2 g, 2 g + 1
+  auto write_t = [&](auto jtag, const u32x4_t (&d)[2]) {  // dS^T of block j: registers 4 g .. 4 g + 3 are dwords 2 g, 2 g + 1
     constexpr int j = decltype(jtag)::value;
     char* timg = tcur + j * 2048;
 #pragma unroll
@@ -386,8 +355,8 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     }
   };
   auto tr_qg = [&](int db, int s2, bf16x8_t& gt, bf16x8_t& qt) {
-    gt = m_tr_frag(gsl + s2 * 2048 + off_tra[db][0], gsl + s2 * 2048 + off_tra[db][1]);
-    qt = m_tr_frag(qsl + s2 * 2048 + off_tra[db][0], qsl + s2 * 2048 + off_tra[db][1]);
+    gt = tr_frag_at(gsl + s2 * 2048 + off_tra[db][0], gsl + s2 * 2048 + off_tra[db][1]);
+    qt = tr_frag_at(qsl + s2 * 2048 + off_tra[db][0], qsl + s2 * 2048 + off_tra[db][1]);
   };
   // stage C(j) - eight accumulating MFMAs - with stage B(j+1) riding between them (NX) and the operands of A(j+2)
   // preloaded into the registers B(j+1) has finished with (NX2).  The LDS reads run two slots ahead of their MFMAs.
@@ -397,7 +366,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     constexpr int j = decltype(jtag)::value;
     constexpr bool NX = j + 1 < KB, NX2 = j + 2 < KB;
     bf16x8_t g0, q0, g1, q1;
-    m_u32x4_t pkn[2], dkn[2];
+    u32x4_t pkn[2], dkn[2];
     const bf16x8_t pk0 = __builtin_bit_cast(bf16x8_t, pk[0]), pk1 = __builtin_bit_cast(bf16x8_t, pk[1]);
     const bf16x8_t dk0 = __builtin_bit_cast(bf16x8_t, dk[0]), dk1 = __builtin_bit_cast(bf16x8_t, dk[1]);
     g0 = cg0; q0 = cq0; g1 = cg1; q1 = cq1;  // (0,0) and (0,1): requested before stage A(j+1)
@@ -443,11 +412,11 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     const char* tb = tbuf + (sp & 1) * (NKB * 2048);
     const char* kb = kimg + kopq;
     f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    m_u32x4_t pkn[2], dkn[2];
+    u32x4_t pkn[2], dkn[2];
     const int tq0 = MXQ ? (wave & 1) : 0;  // (MXQ: t1 carries the second A fragment, not a second query tile)
-    bf16x8_t ka = m_tr_frag(kb + off_kq[0], kb + off_kq[1]);
-    bf16x8_t t0 = m_tr_frag(tb + off_tq[tq0][0], tb + off_tq[tq0][1]);
-    bf16x8_t t1 = MXQ ? m_tr_frag(kb + off_kq2[0], kb + off_kq2[1]) : m_tr_frag(tb + off_tq[1][0], tb + off_tq[1][1]);
+    bf16x8_t ka = tr_frag_at(kb + off_kq[0], kb + off_kq[1]);
+    bf16x8_t t0 = tr_frag_at(tb + off_tq[tq0][0], tb + off_tq[tq0][1]);
+    bf16x8_t t1 = MXQ ? tr_frag_at(kb + off_kq2[0], kb + off_kq2[1]) : tr_frag_at(tb + off_tq[1][0], tb + off_tq[1][1]);
 #pragma unroll
     for (int kbk = 0; kbk < NKB; ++kbk) {
       AVF_FENCE();
@@ -455,9 +424,9 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
       if (kbk + 1 < NKB) {
         const char* kn = kb + (kbk + 1) * 4096;
         const char* tn = tb + (kbk + 1) * 2048;
-        kan = m_tr_frag(kn + off_kq[0], kn + off_kq[1]);
-        t0n = m_tr_frag(tn + off_tq[tq0][0], tn + off_tq[tq0][1]);
-        t1n = MXQ ? m_tr_frag(kn + off_kq2[0], kn + off_kq2[1]) : m_tr_frag(tn + off_tq[1][0], tn + off_tq[1][1]);
+        kan = tr_frag_at(kn + off_kq[0], kn + off_kq[1]);
+        t0n = tr_frag_at(tn + off_tq[tq0][0], tn + off_tq[tq0][1]);
+        t1n = MXQ ? tr_frag_at(kn + off_kq2[0], kn + off_kq2[1]) : tr_frag_at(tn + off_tq[1][0], tn + off_tq[1][1]);
       }
       acc0 = AVF_MFMA16(ka, t0, acc0);
       acc1 = MXQ ? AVF_MFMA16(t1, t0, acc1) : AVF_MFMA16(ka, t1, acc1);
@@ -549,8 +518,8 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     asm volatile("" : "+v"(kopq));
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      qa[ks] = m_row_frag(qsl + off_row[ks]);
-      ga[ks] = m_row_frag(gsl + off_row[ks]);
+      qa[ks] = row_frag(qsl + off_row[ks]);
+      ga[ks] = row_frag(gsl + off_row[ks]);
     }
     load_kf(0);
     // every wave runs all its KB blocks, padded ones included (zero K rows and V, masked scores): the slice barrier
@@ -563,7 +532,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     if (s > 0) {
       dq_job(s - 1, std::true_type{});
     } else {
-      m_u32x4_t pkn[2], dkn[2];
+      u32x4_t pkn[2], dkn[2];
 #pragma unroll
       for (int c = 0; c < 8; ++c) b_chunk(c, pkn, dkn);
       pk[0] = pkn[0]; pk[1] = pkn[1]; dk[0] = dkn[0]; dk[1] = dkn[1];
@@ -580,7 +549,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
     //  dozen VALU instructions run beside the matrix pipe instead of on the slice's critical path)
     if (more) {
       // delta of the next slice: its dO rows 8 w .. 8 w + 7 were brought in by THIS wave (own vmcnt suffices)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       const char* gn = ring + ((s + 1) & 1) * 8192 + 4096;
       // onext is logical chunk dch of the row: its partner sits in physical slot dch ^ swz(row)
       const uint4 gv = *reinterpret_cast<const uint4*>(gn + (drow & 31) * 128 + ((dch ^ m_swz(drow & 31)) << 4));
@@ -619,7 +588,7 @@ __global__ __launch_bounds__(256) void attn_bwd_m4_kernel(const bf16* __restrict
 
   // ---- dK, dV of the wave's keys ---------------------------------------------------------------------------------
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");  // the last accumulating MFMA has retired before the AGPRs are read
-  const float kscale = 1.0f / kLog2E;  // dK = dS^T q' / log2(e) with q' = q log2(e) / sqrt(dh)
+  const float kscale = 1.0f / LOG2E;  // dK = dS^T q' / log2(e) with q' = q log2(e) / sqrt(dh)
 #pragma unroll
   for (int j = 0; j < KB; ++j) {
     const int key = 32 * (kb0 + j) + r;

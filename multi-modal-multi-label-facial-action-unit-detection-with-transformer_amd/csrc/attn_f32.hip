@@ -21,7 +21,6 @@ namespace avf {
 namespace {
 
 constexpr int KT = 32;  // keys (or queries) staged per step
-constexpr float LOG2E = 1.4426950408889634f;
 
 template <int DH, typename T>
 __device__ __forceinline__ void stage_rows(float* dst, const T* src, int64_t ld, int row0, int nrows_valid) {

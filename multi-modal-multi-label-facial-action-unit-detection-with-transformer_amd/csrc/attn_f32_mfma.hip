@@ -73,17 +73,13 @@ struct ParityF32Mfma {
     }
   }
 
-  // A 16 x 16 block of P (or dS) becomes the B operand of the next product by a 4 x 4 transpose of one dword between the register
-  // index and the lane group (lanes l, l + 16, l + 32, l + 48; two v_permlane16_swap + two v_permlane32_swap per dword pair):
-  // in: v[d] of lane group g = X[d][g]; out: v[k] of lane group g = X[g][k], so register m of lane (li, lg) holds
+  // A 16 x 16 block of P (or dS) becomes the B operand of the next product by the 4 x 4 transpose between the register index
+  // and the lane group (tr4x4: two v_permlane16_swap + two v_permlane32_swap): register m of lane (li, lg) then holds
   // P[key 4 m + lg][query li], exactly what k-step m (keys 4 m .. 4 m + 3) of   O^T += V^T P   asks of that lane.
   __device__ __forceinline__ static void as_operand(f32x4_t& v) {
-    const uint32_t a0 = __float_as_uint(v[0]), a1 = __float_as_uint(v[1]), a2 = __float_as_uint(v[2]), a3 = __float_as_uint(v[3]);
-    const auto p01 = __builtin_amdgcn_permlane16_swap(a0, a1, false, false);
-    const auto p23 = __builtin_amdgcn_permlane16_swap(a2, a3, false, false);
-    const auto x = __builtin_amdgcn_permlane32_swap(p01[0], p23[0], false, false);
-    const auto y = __builtin_amdgcn_permlane32_swap(p01[1], p23[1], false, false);
-    v[0] = __uint_as_float(x[0]); v[1] = __uint_as_float(y[0]); v[2] = __uint_as_float(x[1]); v[3] = __uint_as_float(y[1]);
+    uint32_t a[4] = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+    tr4x4(a);
+    v[0] = __uint_as_float(a[0]); v[1] = __uint_as_float(a[1]); v[2] = __uint_as_float(a[2]); v[3] = __uint_as_float(a[3]);
   }
 
   // out[db] (transposed: out[db][r] of lane (li, lg) = column 16 db + 4 lg + r of this lane's row li) += sum over the tile's 32

@@ -29,21 +29,12 @@
 //   tile_dot, as_operand, tile_acc    the two products
 #pragma once
 #include "common.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 namespace {
 
 constexpr int kParityTile = 32;  // rows of the streamed operand per tile
-constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float max_groups(float v) {  // maximum over the four lane groups (lanes li, li + 16, + 32, + 48)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float sum_groups(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
 
 // where a workgroup and a lane stand: (clip b, head h), row `row` of the 64 (a query or a key), the head's columns of qkv / o
 struct ParityCoords {
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(256) void attn_fwd_parity_kernel(const float* __res
   const ParityCoords c = ParityCoords::make<DH>(qkv, N, H);
   const int li = c.li, lg = c.lg, I = c.I;
   typename Ops::RowFrags qf;
-  Ops::load_row(qf, c.base + (int64_t)c.row * c.ld, c.valid, lg, kLog2e / sqrtf((float)DH));
+  Ops::load_row(qf, c.base + (int64_t)c.row * c.ld, c.valid, lg, LOG2E / sqrtf((float)DH));
   f32x4_t acc[NC];
 #pragma unroll
   for (int db = 0; db < NC; ++db) acc[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -104,7 +95,7 @@ __global__ __launch_bounds__(256) void attn_fwd_parity_kernel(const float* __res
         if (16 * kb + 4 * lg + r >= nk) s[kb][r] = -INFINITY;
         tmax = fmaxf(tmax, s[kb][r]);
       }
-    tmax = max_groups(tmax);
+    tmax = groups_max_shfl(tmax);
     const float mn = fmaxf(m, tmax);
     const float alpha = exp2f(m - mn);
     m = mn;
@@ -124,7 +115,7 @@ __global__ __launch_bounds__(256) void attn_fwd_parity_kernel(const float* __res
     }
     Ops::tile_acc(acc, Vt, s, li, lg);  // O^T += V^T P
   }
-  l = sum_groups(l);
+  l = groups_sum_shfl(l);
   if (c.valid) {
     const float inv = 1.0f / l;
     float* orow = o + ((int64_t)c.b * N + c.row) * I + c.h * DH;
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(256) void attn_dq_parity_kernel(const float* __rest
   const int li = c.li, lg = c.lg, I = c.I;
   const float scale = 1.0f / sqrtf((float)DH);
   typename Ops::RowFrags qf, gf;
-  Ops::load_row(qf, c.base + (int64_t)c.row * c.ld, c.valid, lg, kLog2e * scale);
+  Ops::load_row(qf, c.base + (int64_t)c.row * c.ld, c.valid, lg, LOG2E * scale);
   Ops::load_row(gf, d_o + ((int64_t)c.b * N + c.row) * I + c.h * DH, c.valid, lg, 1.0f);
   const float L = c.valid ? lse2[(int64_t)c.bh * N + c.row] : INFINITY;  // rows past the end: P = 2^(s - inf) = 0
   float dl = 0.f;
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(256) void attn_dq_parity_kernel(const float* __rest
           dl = fmaf(gv.x, ov.x, dl); dl = fmaf(gv.y, ov.y, dl); dl = fmaf(gv.z, ov.z, dl); dl = fmaf(gv.w, ov.w, dl);
         }
     }
-    dl = sum_groups(dl);
+    dl = groups_sum_shfl(dl);
     if (c.valid && lg == 0) delta[(int64_t)c.bh * N + c.row] = dl;
   } else {
     if (c.valid) dl = delta[(int64_t)c.bh * N + c.row];
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(256) void attn_dkv_parity_kernel(const float* __res
   const float* gbase = d_o + (int64_t)c.b * N * I + c.h * DH;
   const float scale = 1.0f / sqrtf((float)DH);
   typename Ops::RowFrags kf, vf;
-  Ops::load_row(kf, c.base + I + (int64_t)c.row * c.ld, c.valid, lg, kLog2e * scale);
+  Ops::load_row(kf, c.base + I + (int64_t)c.row * c.ld, c.valid, lg, LOG2E * scale);
   Ops::load_row(vf, c.base + 2 * I + (int64_t)c.row * c.ld, c.valid, lg, 1.0f);
   f32x4_t dk[NC], dv[NC];
 #pragma unroll

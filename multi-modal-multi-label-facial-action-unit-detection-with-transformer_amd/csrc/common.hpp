@@ -42,6 +42,7 @@ inline int tuning_int(const char* name, int def) {
 // the tiled kernels take (kWorkgroupSlots / 2: one workgroup per CU).  A grid below it leaves CUs without work, one above
 // it runs a second round.  A constant of the MI355X, not read from the device: deriving it would change dispatch on other parts.
 constexpr int kWorkgroupSlots = 512;
+constexpr float LOG2E = 1.4426950408889634f;  // the attention kernels take softmax in base 2: exp2(log2(e) x)
 // a run-time integer as a compile-time one: helpers switch over the values a template is instantiated for and hand a generic
 // lambda an int_c<V>{}
 template <int N>

@@ -144,10 +144,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(NtParam
     char* sb = sa + A_BYTES;
 #pragma unroll
     for (int j = 0; j < A_INS; ++j)
-      if (A_TOT % NW == 0 || wave + j * NW < A_TOT) glds16(ga[j] + k0, sa + (wave + j * NW) * 1024);
+      if (A_TOT % NW == 0 || wave + j * NW < A_TOT) glds<16>(ga[j] + k0, sa + (wave + j * NW) * 1024);
 #pragma unroll
     for (int j = 0; j < B_INS; ++j)
-      if (B_TOT % NW == 0 || wave + j * NW < B_TOT) glds16(gb[j] + k0, sb + (wave + j * NW) * 1024);
+      if (B_TOT % NW == 0 || wave + j * NW < B_TOT) glds<16>(gb[j] + k0, sb + (wave + j * NW) * 1024);
   };
 
   // Weight warm-up.  In the step a weight image was last touched a whole pass ago: it is in no cache, every workgroup walks K
@@ -372,17 +372,6 @@ struct TnParams {
   int kchunk;     // reduction rows per split (multiple of TR)
 };
 
-// transposed fragment: 8 reduction rows x 16 columns -> lane (col = cb + li) gets rows
-// k-slot j: 16*(j>>2) + 4*lg + (j&3) of the 32-row k-step (same slot map for both operands).
-__device__ __forceinline__ bf16x8_t tr_frag(const lds_char* tile, int row_base, int col_base, int li, int lg) {
-  const lds_char* p0 = tile + (row_base + 4 * lg + (li >> 2)) * TN_LD + (col_base + 4 * (li & 3)) * 2;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * TN_LD));
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
 __global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(TnParams p) {
   extern __shared__ __attribute__((aligned(16))) char dyn_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -439,8 +428,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(TnParams p) {
       bf16x8_t fa[4], fb[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        fa[i] = tr_frag(sa, ks * 32, wm * 64 + i * 16, li, lg);
-        fb[i] = tr_frag(sb, ks * 32, wn * 64 + i * 16, li, lg);
+        fa[i] = tr_frag<TN_LD>(sa, ks * 32, wm * 64 + i * 16, li, lg);
+        fb[i] = tr_frag<TN_LD>(sb, ks * 32, wn * 64 + i * 16, li, lg);
       }
       // D[i = n][j = m]: A_op rows = N-side columns, B_op cols = M-side columns
 #pragma unroll
@@ -505,18 +494,6 @@ struct TnGroup {
 // both travel by value: the group to the GEMM kernels, the group and the column folds to fold_group_kernel
 static_assert(sizeof(TnGroup) + sizeof(FoldList) + 16 <= 4096, "TnGroup + FoldList exceed the 4 KiB kernel-argument budget");
 
-__device__ __forceinline__ bf16x8_t tr_frag_swz(const lds_char* tile, int row_base, int col_base, int li, int lg) {
-  const int row = row_base + 4 * lg + (li >> 2);  // row & 7 is the same for the +16 read
-  const int chunk = (col_base >> 3) + ((li & 3) >> 1);
-  const int off = ((chunk ^ ((row & 7) << 1)) << 4) + ((li & 1) << 3);
-  const lds_char* p0 = tile + row * 256 + off;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * 256));
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
 // WNW = wavefronts along N (2 -> 4 waves of 64x64, 4 -> 8 waves of 64x32)
 template <int WNW>
 __global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g) {
@@ -557,9 +534,9 @@ __global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g
     char* sa = smem + st * 2 * OPB;
     char* sb = sa + OPB;
 #pragma unroll
-    for (int j = 0; j < INS; ++j) glds16(ga[j] + t * astep, sa + (wave * INS + j) * 1024);
+    for (int j = 0; j < INS; ++j) glds<16>(ga[j] + t * astep, sa + (wave * INS + j) * 1024);
 #pragma unroll
-    for (int j = 0; j < INS; ++j) glds16(gb[j] + t * bstep, sb + (wave * INS + j) * 1024);
+    for (int j = 0; j < INS; ++j) glds<16>(gb[j] + t * bstep, sb + (wave * INS + j) * 1024);
   };
 
   f32x4_t acc[4][NI];
@@ -580,9 +557,9 @@ __global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8_t fa[4], fb[NI];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = tr_frag_swz(sa, ks * 32, wm * 64 + i * 16, li, lg);
+      for (int i = 0; i < 4; ++i) fa[i] = tr_frag_swz<256>(sa, ks * 32, wm * 64 + i * 16, li, lg);
 #pragma unroll
-      for (int j = 0; j < NI; ++j) fb[j] = tr_frag_swz(sb, ks * 32, wn * (16 * NI) + j * 16, li, lg);
+      for (int j = 0; j < NI; ++j) fb[j] = tr_frag_swz<256>(sb, ks * 32, wn * (16 * NI) + j * 16, li, lg);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -613,41 +590,10 @@ __global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g
 // 256 B (four per instruction); the same chunk XOR (row & 7) << 1 keeps ds_read_b64_tr_b16 conflict-free for both row
 // lengths (either is a multiple of the 256-byte bank row).  NS-stage ring (3: 144 KB), counted vmcnt, one raw
 // s_barrier per K-step - weight gradients reduce over thousands of token rows, so the ring runs at depth for the whole
-// launch and there is no short-K prologue / epilogue problem here.
+// launch and there is no short-K prologue / epilogue problem here.  The fragment reads are inline asm (tr_frag_asm;
+// mfma_frag.hpp says why), or the ring would drain to depth one whatever the counted waits say.
 // ------------------------------------------------------------------------------------------
 constexpr int TBM = 256;  // big-tile M extent (columns of A)
-
-template <int ROWB>
-__device__ __forceinline__ bf16x8_t tr_frag_swz_rb(const lds_char* tile, int row_base, int col_base, int li, int lg) {
-  const int row = row_base + 4 * lg + (li >> 2);  // row & 7 is the same for the +16 read
-  const int chunk = (col_base >> 3) + ((li & 3) >> 1);
-  const int off = ((chunk ^ ((row & 7) << 1)) << 4) + ((li & 1) << 3);
-  const lds_char* p0 = tile + row * ROWB + off;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * ROWB));
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-// Fragment reads as INLINE ASM.  hipcc treats an LDS-DMA in flight as a pending LDS store that may alias any later
-// ds_read of the same array and puts s_waitcnt vmcnt(0) in front of the first read of every K-step - which drains the ring
-// to depth one whatever the counted waits in the source say.  The asm is opaque to that pass; ordering against the DMA is
-// the kernel's own counted vmcnt + s_barrier, and every use of the results sits behind an explicit s_waitcnt lgkmcnt(0)
-// followed by sched_barrier(0) (the compiler may otherwise hoist register-only MFMAs above the asm wait).
-template <int OFF>
-__device__ __forceinline__ s16x4_t lds_tr16_asm(uint32_t addr) {
-  s16x4_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF_LO, int OFF_HI>
-__device__ __forceinline__ bf16x8_t tr_frag_asm(uint32_t addr) {
-  const s16x4_t lo = lds_tr16_asm<OFF_LO>(addr), hi = lds_tr16_asm<OFF_HI>(addr);
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  const s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
 
 template <int NS>
 __global__ __launch_bounds__(512) void gemm_bf16_tn_group_big_kernel(TnGroup g) {
@@ -722,9 +668,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_group_big_kernel(TnGroup g) 
     char* sa = dsm + st * STAGE;
     char* sb = sa + A_BYTES;
 #pragma unroll
-    for (int j = 0; j < A_INS; ++j) glds16(ga[j] + t * astep, sa + (wave * A_INS + j) * 1024);
+    for (int j = 0; j < A_INS; ++j) glds<16>(ga[j] + t * astep, sa + (wave * A_INS + j) * 1024);
 #pragma unroll
-    for (int j = 0; j < B_INS; ++j) glds16(gb[j] + t * bstep, sb + (wave * B_INS + j) * 1024);
+    for (int j = 0; j < B_INS; ++j) glds<16>(gb[j] + t * bstep, sb + (wave * B_INS + j) * 1024);
   };
 
   f32x4_t acc[4][4];
@@ -785,7 +731,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_group_big_kernel(TnGroup g) 
     } else {
       wait_vmcnt<0>();
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);

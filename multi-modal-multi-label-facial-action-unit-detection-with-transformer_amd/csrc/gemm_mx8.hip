@@ -32,10 +32,6 @@ struct Mx8Params {
   const uint8_t* Bs;  // [N][K/32]
 };
 
-__device__ __forceinline__ void glds4(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((gptr_t*)g, (lptr_t*)l, 4, 0, 0);
-}
-
 // LEAN (bit flags): 0 = the general epilogue; 1 = nt_epilogue_lean (gemm_nt.hpp; the host has checked nt_lean_ok), + 2 = with
 // column sums, + 4 = with the MX-FP8 image of C
 template <int EPI, typename CT, int WM, int WN, int MI, int NI, int LEAN = 0>
@@ -99,12 +95,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx8_nt_kernel(Mx8Params q, 
     char* ss = sb + B_BYTES;
 #pragma unroll
     for (int j = 0; j < A_INS; ++j)
-      if (A_TOT % NW == 0 || wave + j * NW < A_TOT) glds16(ga[j] + t * KS, sa + (wave + j * NW) * 1024);
+      if (A_TOT % NW == 0 || wave + j * NW < A_TOT) glds<16>(ga[j] + t * KS, sa + (wave + j * NW) * 1024);
 #pragma unroll
     for (int j = 0; j < B_INS; ++j)
-      if (B_TOT % NW == 0 || wave + j * NW < B_TOT) glds16(gb[j] + t * KS, sb + (wave + j * NW) * 1024);
+      if (B_TOT % NW == 0 || wave + j * NW < B_TOT) glds<16>(gb[j] + t * KS, sb + (wave + j * NW) * 1024);
 #pragma unroll
-    for (int j = 0; j < S_INS; ++j) glds4(gs[j] + t * 4, ss + spiece[j] * 256);
+    for (int j = 0; j < S_INS; ++j) glds<4>(gs[j] + t * 4, ss + spiece[j] * 256);
   };
 
   f32x4_t acc[MI][NI];

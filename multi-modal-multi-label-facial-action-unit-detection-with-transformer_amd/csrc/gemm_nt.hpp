@@ -1,5 +1,5 @@
 // gemm_nt.hpp - pieces shared by the NT GEMM kernels (gemm_bf16.hip: bf16 operands; gemm_mx8.hip: MX-FP8 operands):
-// parameter block, LDS tile addressing, the fused epilogue, LDS-DMA and launch-order helpers.
+// parameter block, LDS tile addressing, the fused epilogue.  (LDS-DMA, asm LDS reads, waits, block order: mfma_frag.hpp.)
 #pragma once
 #include <stdlib.h>
 
@@ -7,11 +7,10 @@
 
 #include "common.hpp"
 #include "gemm_dispatch.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 namespace {
-
-typedef __attribute__((address_space(3))) char lds_char;
 
 constexpr int TB = 128;            // block tile (both M and N)
 constexpr int TK = 64;             // bf16 K per stage (128 bytes per tile row)
@@ -265,8 +264,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4_t (&acc)[MI
           float am = 0.f;
 #pragma unroll
           for (int r = 0; r < 4; ++r) am = fmaxf(am, fmaxf(fabsf(mxv[j][r]), fabsf(mxv[j + 1][r])));
-          am = fmaxf(am, __shfl_xor(am, 16, 64));
-          am = fmaxf(am, __shfl_xor(am, 32, 64));
+          am = groups_max_shfl(am);
           float inv;
           const uint32_t sb = mx8_scale_byte(am, &inv);
           store_pair8(p.mxq + (int64_t)mm[ii] * p.N, nn[j], nn[j + 1], lg, mx8_pack4(mxv[j], inv), mx8_pack4(mxv[j + 1], inv),
@@ -526,44 +524,6 @@ __device__ __forceinline__ void nt_epilogue_lean(const NtParams& p, f32x4_t (&ac
     nt_epilogue_lean_body<EPI, CT, MI, NI, CS, PRE, false, MXO, BIAS, DROP>(p, acc, m_base, n_base, li, lg, part_row, pre, cs_acc, dkey);
 }
 
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((gptr_t*)g, (lptr_t*)l, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int id, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = id & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Fragment reads as inline asm.  With an LDS-DMA in flight hipcc (ROCm 7.2) drains vmcnt to 0 in front of the first
-// compiler-visible ds_read of a K-step (its wait-count pass takes the DMA for an LDS store that may alias the read), which
-// serialises the next tile's DMA with this tile's reads and MFMAs.  These reads are opaque to that pass: the kernel's own
-// vmcnt + s_barrier order them against the DMA, and the caller waits with wait_lgkmcnt<N>() + sched_barrier(0) before the
-// first use of the destination registers (the hardware does not interlock LDS returns).  DESIGN_HISTORY.md section 12(a).
-template <typename V, int OFF>
-__device__ __forceinline__ V lds_read_b128(uint32_t addr) {
-  V v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_read_b32(uint32_t addr) {
-  uint32_t v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
 // dst[i] = the 16 bytes at addr + i * STRIDE, i = 0 .. sizeof...(Is) - 1 (immediate offsets)
 template <typename V, int STRIDE, int... Is>
 __device__ __forceinline__ void lds_read_frags(V* dst, uint32_t addr, std::integer_sequence<int, Is...>) {

@@ -54,14 +54,6 @@ __device__ unsigned long long g_ws_stamps[512 * 8 * WS_NSTAMP];
 #define WS_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ void ws_glds16(const void* g, uint32_t lds_addr) {
-  uint32_t keep;  // m0 is compiler-reserved: saved and restored around the DMA
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_addr), "v"(g)
-               : "memory");
-}
-
 // fragment-major image of W[N][512] (row-major, ldw): chunk (panel, wave, j, s, lane) = the 16 bytes lane (li, lg) feeds to the
 // MFMA of column block j, k-step s:  W[256 panel + 32 wave + 16 j + li][32 s + 8 lg .. + 7]
 __global__ __launch_bounds__(256) void pack_ws_kernel(const bf16* __restrict__ w, int64_t ldw, uint4* __restrict__ out, int n_chunks) {
@@ -120,8 +112,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
       const int c = q / PPW, rg = q % PPW;
       int r = row0 + rg * 8 + lrow;
       r = r < p.M ? r : p.M - 1;  // rows past the edge re-read the last row and are never stored
-      ws_glds16(p.A + (int64_t)r * p.lda + c * 64 + lchunk * 8,
-                __builtin_amdgcn_readfirstlane(slot_addr + (uint32_t)(c * CH + rg * 1024)));
+      glds16_asm(p.A + (int64_t)r * p.lda + c * 64 + lchunk * 8,
+                 __builtin_amdgcn_readfirstlane(slot_addr + (uint32_t)(c * CH + rg * 1024)));
     }
   };
   uint32_t abase[2];
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
       for (int i = 0; i < MI; ++i) {
         int r = tile * BM + 16 * i + li;
         r = r < p.M ? r : p.M - 1;
-        ws_glds16(src + (int64_t)r * ldx + cp0, __builtin_amdgcn_readfirstlane(pre_lds + (uint32_t)((buf * MI + i) * 1024)));
+        glds16_asm(src + (int64_t)r * ldx + cp0, __builtin_amdgcn_readfirstlane(pre_lds + (uint32_t)((buf * MI + i) * 1024)));
       }
     }
   };
@@ -275,7 +267,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
     if constexpr (PRE_LDS) {  // this wave's staged rows of tile t: the 16 bytes a lane would have loaded (lane-linear image)
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         const u32x4_t v = lds_read_b128<u32x4_t, 0>(pre_lds + (uint32_t)(((t & 1) * MI + i) * 1024) + (uint32_t)lane * 16);
         pre.raw[i][0] = make_uint4(v[0], v[1], v[2], v[3]);
       }

@@ -14,14 +14,11 @@
 // AU_former / former_AU_head stacks.  Measured on the real avformer head model (B=64, 12 tokens, three stacks): -3 % per
 // step under hipGraph replay, -5..10 % in the host-bound eager loop (42 fewer launches per step).
 #include "common.hpp"
+#include "mfma_frag.hpp"
 
 namespace avf {
 
 namespace {
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-
 
 struct SmallArgs {
   const float* x_in;
@@ -36,35 +33,6 @@ struct SmallArgs {
   float eps, score_scale;  // score_scale: 1 when the q rows of wqkv carry log2(e)/sqrt(dh), that factor otherwise
   DropCfg dr0, dr1, dr2;
 };
-
-__device__ __forceinline__ bf16x8_t ldg_frag(const bf16* p) {
-  return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(p));
-}
-
-__device__ __forceinline__ bf16x8_t pack_pair_s(const f32x4_t& a, const f32x4_t& b) {
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-  u32x4_t r = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-template <int LD>  // LD: row stride in bytes of the image the fragment is read from
-__device__ __forceinline__ bf16x8_t tr_frag_s(const lds_char* tile, int row_base, int col_base, int li, int lg) {
-  const lds_char* p0 = tile + (row_base + 4 * lg + (li >> 2)) * LD + (col_base + 4 * (li & 3)) * 2;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * LD));
-  s16x8_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-// max / sum over the four lanes {li, li+16, li+32, li+48}
-__device__ __forceinline__ float quad_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
 
 // LayerNorm of the clip's rows: wave w takes rows w, w+NW, ... of the R-row block; x is fp32 with row stride ldx (global
 // or LDS); the bf16 result goes to the LDS operand buffer ylds (row stride ldy elements; rows past N are zeroed, so that
@@ -215,7 +183,7 @@ __global__ __launch_bounds__(NW * 64) void layer_fwd_small_kernel(SmallArgs a) {
           mx = fmaxf(mx, sc);
         }
       }
-      mx = quad_max(mx);
+      mx = groups_max_shfl(mx);
       float sum = 0.f;
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
@@ -224,15 +192,15 @@ __global__ __launch_bounds__(NW * 64) void layer_fwd_small_kernel(SmallArgs a) {
           st[kb][r] = __builtin_amdgcn_exp2f(st[kb][r] - mx);
           sum += st[kb][r];
         }
-      sum = quad_sum(sum);
+      sum = groups_sum_shfl(sum);
       f32x4_t ot[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int s2 = 0; s2 < KB / 2; ++s2) {
-        const bf16x8_t pp = pack_pair_s(st[2 * s2], st[2 * s2 + 1]);
+        const bf16x8_t pp = pack_pair(st[2 * s2], st[2 * s2 + 1]);
 #pragma unroll
         for (int d = 0; d < 2; ++d)
           ot[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              tr_frag_s<LDQ * 2>((const lds_char*)(qh + 2 * I), 32 * s2, 16 * d, li, lg), pp, ot[d], 0, 0, 0);
+              tr_frag<LDQ * 2>((const lds_char*)(qh + 2 * I), 32 * s2, 16 * d, li, lg), pp, ot[d], 0, 0, 0);
       }
       const int q = 16 * qb + li;
       const float inv = 1.0f / sum;
@@ -575,7 +543,6 @@ __global__ __launch_bounds__(NW * 64) void layer_bwd_small_b_kernel(SmallBwdB a)
       float dl = 0.f;
       if (li < N) {
         const bf16x8_t fo = ldg_frag(a.o + (row0 + li) * I + h * 32 + 8 * lg);
-        typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
         const u32x4_t x = __builtin_bit_cast(u32x4_t, fdo), y = __builtin_bit_cast(u32x4_t, fo);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -583,7 +550,7 @@ __global__ __launch_bounds__(NW * 64) void layer_bwd_small_b_kernel(SmallBwdB a)
           dl = fmaf(__uint_as_float(x[i] & 0xffff0000u), __uint_as_float(y[i] & 0xffff0000u), dl);
         }
       }
-      dl = quad_sum(dl);
+      dl = groups_sum_shfl(dl);
       const float lse = li < N ? a.lse2[(b * H + h) * N + li] : 0.f;
       float pv[4], dsv[4];
 #pragma unroll
@@ -600,7 +567,6 @@ __global__ __launch_bounds__(NW * 64) void layer_bwd_small_b_kernel(SmallBwdB a)
     if (head) {
       const int h = wave;
       const bf16* qh = sbuf + h * 32;
-      typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
       // B operands with the k-slot order of the transposed A fragments: slots 0..3 = k 4 lg + 0..3, slots 4..7 = k 16 + ... = 0
       auto bfrag = [&](const bf16* tile) {
         const uint2 v = *reinterpret_cast<const uint2*>(tile + li * 16 + 4 * lg);
@@ -612,9 +578,9 @@ __global__ __launch_bounds__(NW * 64) void layer_bwd_small_b_kernel(SmallBwdB a)
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
         // transposed A fragments: rows = d (16 d + ...), k = token (32-row images, rows past N zero)
-        const bf16x8_t a_do = tr_frag_s<LDO * 2>((const lds_char*)(dobuf + h * 32), 0, 16 * d, li, lg);
-        const bf16x8_t a_q = tr_frag_s<LDS_ * 2>((const lds_char*)qh, 0, 16 * d, li, lg);
-        const bf16x8_t a_k = tr_frag_s<LDS_ * 2>((const lds_char*)(qh + I), 0, 16 * d, li, lg);
+        const bf16x8_t a_do = tr_frag<LDO * 2>((const lds_char*)(dobuf + h * 32), 0, 16 * d, li, lg);
+        const bf16x8_t a_q = tr_frag<LDS_ * 2>((const lds_char*)qh, 0, 16 * d, li, lg);
+        const bf16x8_t a_k = tr_frag<LDS_ * 2>((const lds_char*)(qh + I), 0, 16 * d, li, lg);
         const f32x4_t dv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_do, bp, z, 0, 0, 0);     // dV^T[d][key li]
         const f32x4_t dk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_q, bds_t, z, 0, 0, 0);   // dK^T[d][key li]
         const f32x4_t dq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_k, bds_q, z, 0, 0, 0);   // dQ^T[d][query li]
