@@ -230,6 +230,34 @@ int avf_gemm_tn_group(int count, int64_t K, const void* const* A, const void* co
 int avf_gemm_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out);
 int avf_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int32_t* out);
 
+/* Test plumbing for the fp32 (parity-mode) GEMM family of csrc/gemm_f32.hip: C[M,N] = epilogue(op(A) op(B)) as
+ * avf_gemm(AVF_F32, transA, transB, ...) runs it - fp32 operands, C, residual and aux; workspace optional (without it the call
+ * runs unsplit) - plus the dropout site only a layer call could ask of it so far: (seed_lo, seed_hi, layer_index, site, p) as
+ * avf_gemm_nt_ex takes them, element index m * N + n, p == 0 is no dropout, not on AVF_EPI_NONE.
+ * avf_gemm_f32_plan: what that call decides under the arithmetic selected now (avf_set_f32_arith), by the function the launcher
+ * itself acts on (host code only).  Pointers are replaced by their presence and alignment: bit i of `misaligned` set = that
+ * operand is 4 bytes past a 16-byte boundary (bit 0 A, 1 B, 2 C, 3 bias, 4 residual, 5 aux, 6 workspace).
+ * out[0] = the kernel: 0 = gemm_f32x3_kernel (bf16x3), 1 = gemm_f32_kernel on 32 x 32 tiles (T = 1), 2 = on 64 x 64 tiles
+ * (T = 2); out[1] / out[2] = 1 when the reduction is the unit-stride axis of A / of B (AKF / BKF of the bf16x3 kernel);
+ * out[3] = S, the split count (1: unsplit); out[4] = reduction rows per split (0 when unsplit); out[5] = 1 when the bf16x3
+ * kernel's epilogue (or its slab store) uses 16-byte accesses. */
+int avf_gemm_f32_ex(int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                    int64_t ldb, void* C, int64_t ldc, int epilogue, const float* bias, const float* residual, int64_t ldres,
+                    void* aux, int64_t ldaux, void* workspace, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site,
+                    float p, void* stream);
+int avf_gemm_f32_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                      int epilogue, int has_bias, int64_t ldres, int64_t ldaux, int has_workspace, int misaligned, int32_t* out);
+/* The weight gradients of one parity-mode layer as ONE launch in the bf16x3 arithmetic: 2 .. 4 C_i[M_i,N_i] (fp32, dense) =
+ * A_i[K,M_i]^T B_i[K,N_i] (fp32, token-major, rows lda[i] / ldb[i] apart; null: dense) sharing K >= 512, M_i >= 96, N_i >= 96,
+ * N_i % 4 == 0, every pointer 16-byte aligned, split over K into slabs in `workspace` (..._workspace_bytes) and folded by a
+ * second launch.  avf_gemm_f32_tn_group_plan: out[0] = 1 when the launch takes the group under the arithmetic selected now
+ * (else the rest is 0 and avf_gemm_f32_tn_group refuses), out[1] = 128 x 128 tiles of the group, out[2] = S, out[3] =
+ * reduction rows per split (a multiple of 32). */
+size_t avf_gemm_f32_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N);
+int avf_gemm_f32_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out);
+int avf_gemm_f32_tn_group(int count, int64_t K, const void* const* A, const int64_t* lda, const void* const* B,
+                          const int64_t* ldb, float* const* C, const int64_t* M, const int64_t* N, void* workspace, void* stream);
+
 /* MX-FP8 operands (OCP microscaling: e4m3 elements, one E8M0 scale byte per 32 consecutive elements of a row) for the
  * forward nn.Linear GEMMs (heads.py:191,195,212) on v_mfma_scale_f32_16x16x128_f8f6f4 - BASELINE config 5.
  *   avf_quant_mx8:   x [rows,cols] (AVF_F32 | AVF_BF16, cols % 32 == 0) -> q [rows,cols] bytes, scales [rows,cols/32] bytes;

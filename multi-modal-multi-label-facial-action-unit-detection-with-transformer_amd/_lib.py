@@ -94,6 +94,12 @@ SIGNATURES = {
     "avf_gemm_tn_group": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avf_gemm_tn_group_plan": (_int, [_int, _i64, _vp, _vp, _vp]),
     "avf_gemm_tn_plan": (_int, [_i64, _i64, _i64, _vp]),
+    "avf_gemm_f32_ex": (_int, [_int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp,
+                               C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
+    "avf_gemm_f32_plan": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _i64, _int, _int, _vp]),
+    "avf_gemm_f32_tn_group_workspace_bytes": (_sz, [_int, _i64, _vp, _vp]),
+    "avf_gemm_f32_tn_group_plan": (_int, [_int, _i64, _vp, _vp, _vp]),
+    "avf_gemm_f32_tn_group": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avf_stack_quant_weights_mx8": (_int, [_vp, _int, _vp, _vp]),
     "avf_quant_mx8": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp]),
     "avf_gemm_mx8_nt": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64,

@@ -378,6 +378,73 @@ extern "C" int avf_gemm_tn_group(int count, int64_t K, const void* const* A, con
   return gemm_bf16_tn_group(g, (hipStream_t)stream, nullptr);
 }
 
+// ---- the fp32 (parity-mode) GEMM family with everything a layer can ask of it (test plumbing) ----
+extern "C" int avf_gemm_f32_ex(int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
+                               int64_t ldb, void* C, int64_t ldc, int epilogue, const float* bias, const float* residual,
+                               int64_t ldres, void* aux, int64_t ldaux, void* workspace, uint32_t seed_lo, uint32_t seed_hi,
+                               int layer_index, int site, float p, void* stream) {
+  AVF_REQUIRE(A && B && C, "gemm_f32_ex: null pointer");
+  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "gemm_f32_ex: bad dropout site %d / p %g", site, (double)p);
+  GemmArgs a = gemm_dense(AVF_F32, transA, transB, M, N, K);
+  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
+  a.c_dtype = AVF_F32; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
+  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace;
+  if (p > 0.f) a.drop = make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site);
+  return gemm_f32(a, (hipStream_t)stream);
+}
+extern "C" int avf_gemm_f32_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                                 int epilogue, int has_bias, int64_t ldres, int64_t ldaux, int has_workspace, int misaligned,
+                                 int32_t* out) {
+  AVF_REQUIRE(out, "gemm_f32_plan: null pointer");
+  // never dereferenced: the predicates look at null-ness and alignment only
+  auto ptr = [&](int bit) { return (void*)(uintptr_t)(256 + ((misaligned >> bit) & 1) * 4); };
+  GemmArgs a = gemm_dense(AVF_F32, transA, transB, M, N, K);
+  a.A = ptr(0); a.lda = lda; a.B = ptr(1); a.ldb = ldb; a.C = ptr(2); a.ldc = ldc;
+  a.c_dtype = AVF_F32; a.epilogue = epilogue; a.ldres = ldres; a.ldaux = ldaux;
+  if (has_bias) a.bias = (const float*)ptr(3);
+  if (epilogue == AVF_EPI_BIAS_RES) a.residual = ptr(4);
+  if (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) a.aux = ptr(5);
+  if (has_workspace) a.workspace = ptr(6);
+  F32Plan pl;
+  AVF_TRY(gemm_f32_plan(a, &pl));
+  out[0] = pl.kernel; out[1] = pl.akf; out[2] = pl.bkf; out[3] = pl.S; out[4] = pl.kchunk; out[5] = pl.vec;
+  return 0;
+}
+static int fill_f32_tn_group(TnGroupArgs* g, int count, int64_t K, const void* const* A, const int64_t* lda, const void* const* B,
+                             const int64_t* ldb, float* const* C, const int64_t* M, const int64_t* N) {
+  AVF_TRY(fill_tn_group(g, count, K, A, B, C, M, N));
+  for (int i = 0; i < count; ++i) {
+    if (lda) g->lda[i] = lda[i];
+    if (ldb) g->ldb[i] = ldb[i];
+    AVF_REQUIRE(g->lda[i] >= M[i] && g->ldb[i] >= N[i], "gemm_f32_tn_group: lda / ldb below the row length of problem %d", i);
+  }
+  return 0;
+}
+extern "C" size_t avf_gemm_f32_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N) {
+  TnGroupArgs g;
+  if (fill_f32_tn_group(&g, count, K, nullptr, nullptr, nullptr, nullptr, nullptr, M, N)) return 0;
+  return gemm_f32x3_tn_group_ws(g);
+}
+extern "C" int avf_gemm_f32_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out) {
+  AVF_REQUIRE(out, "gemm_f32_tn_group_plan: null pointer");
+  TnGroupArgs g;
+  AVF_TRY(fill_f32_tn_group(&g, count, K, nullptr, nullptr, nullptr, nullptr, nullptr, M, N));
+  int tiles, S, kchunk;
+  out[0] = gemm_f32x3_tn_group_plan(g, &tiles, &S, &kchunk);
+  out[1] = tiles; out[2] = S; out[3] = kchunk;
+  return 0;
+}
+extern "C" int avf_gemm_f32_tn_group(int count, int64_t K, const void* const* A, const int64_t* lda, const void* const* B,
+                                     const int64_t* ldb, float* const* C, const int64_t* M, const int64_t* N, void* workspace,
+                                     void* stream) {
+  AVF_REQUIRE(A && B && C, "gemm_f32_tn_group: null pointer");
+  TnGroupArgs g;
+  AVF_TRY(fill_f32_tn_group(&g, count, K, A, lda, B, ldb, C, M, N));
+  for (int i = 0; i < count; ++i) AVF_REQUIRE(A[i] && B[i] && C[i], "gemm_f32_tn_group: null operand %d", i);
+  g.workspace = workspace;
+  return gemm_f32x3_tn_group(g, (hipStream_t)stream);
+}
+
 extern "C" int avf_layernorm_fwd_mx8(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean,
                                      float* rstd, void* y_q, void* y_scales, int64_t rows, int dim, float eps, void* stream) {
   AVF_REQUIRE(x && gamma && beta && y_bf16 && mean && rstd && y_q && y_scales, "layernorm_fwd_mx8: null pointer");

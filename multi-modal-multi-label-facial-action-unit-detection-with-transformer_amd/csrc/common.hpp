@@ -576,6 +576,16 @@ size_t gemm_f32_ws(int64_t M, int64_t N, int64_t K);  // split-K slabs of skinny
 // 0 = the f32-input MFMA (v_mfma_f32_16x16x4_f32).  Process-wide; avf_set_f32_arith / avf_get_f32_arith.
 void set_f32_arith(int mode);
 int get_f32_arith();
+// Which kernel gemm_f32 runs and how, under the arithmetic selected now: the launcher acts on exactly this (f32_plan in
+// gemm_f32.hip), gemm_f32_plan answers a test's or a profile tool's question from the same function.
+enum { F32_KERNEL_X3 = 0, F32_KERNEL_MFMA_T1 = 1, F32_KERNEL_MFMA_T2 = 2 };
+struct F32Plan {
+  int kernel;    // F32_KERNEL_X3 = gemm_f32x3_kernel (bf16x3), F32_KERNEL_MFMA_T1 / _T2 = gemm_f32_kernel on 32 x 32 / 64 x 64 tiles
+  int akf, bkf;  // the reduction is the unit-stride axis of A / of B (the AKF / BKF of gemm_f32x3_kernel)
+  int S, kchunk; // split count (1: unsplit, kchunk = 0) and reduction rows per split
+  int vec;       // gemm_f32x3_kernel: 16-byte epilogue / slab accesses
+};
+int gemm_f32_plan(const GemmArgs& a, F32Plan* out);  // pointers are looked at for null-ness and alignment only
 int gemm_bf16_nt(const GemmArgs& a, hipStream_t s);
 // Which kernel gemm_bf16_nt runs for a call that does not go to the weight-stationary kernel: the launcher acts on exactly
 // this (nt_plan_bf16 in gemm_bf16.hip), gemm_bf16_nt_plan answers a test's or a profile tool's question from the same function.
@@ -636,6 +646,8 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
 bool gemm_f32x3_tn_group_ok(const TnGroupArgs& a);
 size_t gemm_f32x3_tn_group_ws(const TnGroupArgs& a);
 int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s);
+// what that launch decides (the setup it acts on): -> gemm_f32x3_tn_group_ok; tiles of the group, split count, rows per split
+int gemm_f32x3_tn_group_plan(const TnGroupArgs& a, int* tiles, int* S, int* kchunk);
 
 int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
 // fp32-arithmetic attention on fp32 / bf16 storage with the optional token mask keep [B, N] (bytes, 1 = kept; heads.py:225-232)

@@ -1,7 +1,8 @@
 // gemm_f32.hip - parity-mode GEMM: fp32 operands, fp32 accumulate, on v_mfma_f32_16x16x4_f32.
 //
 // The f32-input MFMA is bit-for-bit a k-ordered fmaf chain (one rounding per product), so this
-// path reproduces an fp32 CPU matmul to ~1e-7 relative.  It serves every operand orientation
+// path reproduces an fp32 CPU matmul to ~1e-7 relative (tests/test_gpu_gemm_f32.py compares the bits with that chain, and every
+// variant below element-wise with fp64; avf_gemm_f32_plan tells which variant a call runs).  It serves every operand orientation
 // (nn.Linear forward "NT", dX "NN", dW "TN") through element strides, because the f32 MFMA
 // fragment is ONE value per lane (A[i=l&15][k=l>>4], B[k=l>>4][j=l&15]) and needs no particular
 // LDS layout.  Replaces aten mm/addmm under models/heads.py:191-196, 212, 214-217.
@@ -528,18 +529,15 @@ int launch_f32_fold(const F32GemmParams& p, const GemmArgs& a, int S, hipStream_
   gemm_f32_fold_kernel<<<(unsigned)ceil_div(a.M * a.N, 256), 256, 0, s>>>(p, S, a.epilogue == AVF_EPI_BIAS_RES ? 1 : 0);
   return check_launch("gemm_f32_fold_kernel");
 }
-// K split `wanted` ways over the grid on (32 T) x (32 T) tiles of the f32-input MFMA kernel: raw partials into the caller's
-// workspace, one fold launch with the epilogue - deterministic (no atomics)
+// K split S ways (p.kchunk rows each: f32_plan) over the grid on (32 T) x (32 T) tiles of the f32-input MFMA kernel: raw partials
+// into the caller's workspace, one fold launch with the epilogue - deterministic (no atomics)
 template <int T>
-int launch_f32_split(F32GemmParams p, const GemmArgs& a, int wanted, const char* what, hipStream_t s) {
-  const SplitPlan plan = split_plan(a.K, wanted, 32);
-  p.slabs = (float*)a.workspace;
-  p.kchunk = plan.kchunk;
-  dim3 grid((unsigned)ceil_div(a.N, 32 * T), (unsigned)ceil_div(a.M, 32 * T), (unsigned)plan.S);
+int launch_f32_split(const F32GemmParams& p, const GemmArgs& a, int S, const char* what, hipStream_t s) {
+  dim3 grid((unsigned)ceil_div(a.N, 32 * T), (unsigned)ceil_div(a.M, 32 * T), (unsigned)S);
   AVF_REQUIRE(grid.y < 65536, "gemm_f32: M too large for grid");
   gemm_f32_kernel<AVF_EPI_NONE, T, true><<<grid, 256, 0, s>>>(p);
   AVF_TRY(check_launch(what));
-  return launch_f32_fold(p, a, plan.S, s);
+  return launch_f32_fold(p, a, S, s);
 }
 
 }  // namespace
@@ -595,6 +593,13 @@ bool gemm_f32x3_tn_group_ok(const TnGroupArgs& a) {
   F32GroupParams g;
   return f32x3_group_setup(a, &g) != 0;
 }
+int gemm_f32x3_tn_group_plan(const TnGroupArgs& a, int* tiles, int* S, int* kchunk) {
+  F32GroupParams g;
+  *tiles = *S = *kchunk = 0;
+  if (!f32x3_group_setup(a, &g)) return 0;
+  *tiles = g.tile0[g.count]; *S = g.S; *kchunk = g.p[0].kchunk;
+  return 1;
+}
 size_t gemm_f32x3_tn_group_ws(const TnGroupArgs& a) {  // (whatever arithmetic is selected NOW: a buffer sized under one serves both)
   F32GroupParams g;
   if (!f32x3_group_setup(a, &g, true)) return 0;
@@ -618,13 +623,13 @@ int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s) {
   return check_launch("gemm_f32x3_group_fold_kernel");
 }
 
-int gemm_f32(const GemmArgs& a, hipStream_t s) {
+// GemmArgs -> the kernels' parameter block (the checks every fp32 GEMM call and plan query must pass)
+static int f32_params(const GemmArgs& a, F32GemmParams* out) {
   AVF_REQUIRE(a.c_dtype == AVF_F32, "gemm_f32: C must be fp32");
   AVF_REQUIRE(!a.drop.thresh16 || a.epilogue != AVF_EPI_NONE, "gemm_f32: dropout needs a fused epilogue");
   AVF_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm_f32: bad shape");
   AVF_REQUIRE(a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31), "gemm_f32: shape too large");
-  F32GemmParams p;
-  TimingScope ts(KC_GEMM_F32, 2.0 * a.M * a.N * a.K, 4.0 * (a.M * a.K + a.N * a.K + a.M * a.N), s);
+  F32GemmParams& p = *out;
   p.A = (const float*)a.A;
   p.B = (const float*)a.B;
   if (a.transA) { p.a_sm = 1; p.a_sk = a.lda; } else { p.a_sm = a.lda; p.a_sk = 1; }
@@ -639,41 +644,81 @@ int gemm_f32(const GemmArgs& a, hipStream_t s) {
   p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
   p.drop = a.drop;
   p.kchunk = 0; p.slabs = nullptr;
-  AVF_TRY(require_epilogue_operands(a, "gemm_f32", 0));  // (no leading-dimension multiple: scalar accesses where they are odd)
+  return require_epilogue_operands(a, "gemm_f32", 0);  // (no leading-dimension multiple: scalar accesses where they are odd)
+}
+
+// Everything gemm_f32 decides before it launches: the launcher acts on exactly this, gemm_f32_plan reports it.  Pointers are
+// looked at for null-ness and alignment only.
+static F32Plan f32_plan(const F32GemmParams& p, const GemmArgs& a) {
+  F32Plan pl;
+  pl.akf = p.a_sk == 1; pl.bkf = p.b_sk == 1;
+  pl.S = 1; pl.kchunk = 0; pl.vec = 0;
   if (g_f32_arith == 1 && f32x3_ok(p)) {  // bf16x3 on the bf16 matrix pipe (round 6)
+    pl.kernel = F32_KERNEL_X3;
     const int S0 = a.workspace ? f32x3_splits(a.M, a.N, a.K, a.epilogue) : 1;
-    int S = 1;
     if (S0 > 1) {
       const SplitPlan plan = split_plan(a.K, S0, SBK);
-      p.slabs = (float*)a.workspace;
-      p.kchunk = plan.kchunk;
-      S = plan.S;
+      pl.kchunk = plan.kchunk;
+      pl.S = plan.S;
     }
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     int vec = (p.N % 4 == 0);
-    if (S > 1) vec = vec && al16(p.slabs);
+    if (pl.S > 1) vec = vec && al16(a.workspace);
     else
       vec = vec && p.ldc % 4 == 0 && al16(p.C) && (!p.bias || al16(p.bias)) &&
             (a.epilogue != AVF_EPI_BIAS_RES || (p.ldres % 4 == 0 && al16(p.residual))) &&
             ((a.epilogue != AVF_EPI_BIAS_GELU && a.epilogue != AVF_EPI_DGELU) || (p.ldaux % 4 == 0 && al16(p.aux)));
-    AVF_REQUIRE(ceil_div(p.M, SBM) < 65536, "gemm_f32: M too large for grid");
-    const bool akf = p.a_sk == 1, bkf = p.b_sk == 1;
-    int rc;
-    if (akf && bkf) rc = launch_f32x3<true, true>(p, a.epilogue, S, vec, s);
-    else if (akf) rc = launch_f32x3<true, false>(p, a.epilogue, S, vec, s);
-    else if (bkf) rc = launch_f32x3<false, true>(p, a.epilogue, S, vec, s);
-    else rc = launch_f32x3<false, false>(p, a.epilogue, S, vec, s);
-    AVF_TRY(rc);
-    return S > 1 ? launch_f32_fold(p, a, S, s) : 0;
+    pl.vec = vec;
+    return pl;
   }
   // skinny GEMMs with a long reduction (the heads' projections on a few dozen clips): split K on the 32 x 32 tiles
   const int sp = a.workspace ? f32_splits(a.M, a.N, a.K, a.epilogue) : 1;
-  if (sp > 1) return launch_f32_split<1>(p, a, sp, "gemm_f32_kernel(split)", s);
   // weight-gradient-shaped GEMMs: 64 x 64 tiles, split K (f32_split64)
-  const int sp64 = a.workspace ? f32_split64(a.M, a.N, a.K, a.epilogue) : 1;
-  if (sp64 > 1) return launch_f32_split<2>(p, a, sp64, "gemm_f32_kernel(split64)", s);
+  const int sp64 = (sp > 1 || !a.workspace) ? 1 : f32_split64(a.M, a.N, a.K, a.epilogue);
+  if (sp > 1 || sp64 > 1) {
+    const SplitPlan plan = split_plan(a.K, sp > 1 ? sp : sp64, 32);
+    pl.kernel = sp > 1 ? F32_KERNEL_MFMA_T1 : F32_KERNEL_MFMA_T2;
+    pl.S = plan.S;
+    pl.kchunk = plan.kchunk;
+    return pl;
+  }
   // 32 x 32 tiles when 64 x 64 ones would not give every CU a workgroup (the small GEMMs of the heads)
   const bool small = ceil_div(a.N, 64) * ceil_div(a.M, 64) < 256;
+  pl.kernel = small ? F32_KERNEL_MFMA_T1 : F32_KERNEL_MFMA_T2;
+  return pl;
+}
+
+int gemm_f32_plan(const GemmArgs& a, F32Plan* out) {
+  F32GemmParams p;
+  AVF_TRY(f32_params(a, &p));
+  *out = f32_plan(p, a);
+  return 0;
+}
+
+int gemm_f32(const GemmArgs& a, hipStream_t s) {
+  F32GemmParams p;
+  AVF_TRY(f32_params(a, &p));
+  TimingScope ts(KC_GEMM_F32, 2.0 * a.M * a.N * a.K, 4.0 * (a.M * a.K + a.N * a.K + a.M * a.N), s);
+  const F32Plan pl = f32_plan(p, a);
+  if (pl.S > 1) {
+    p.slabs = (float*)a.workspace;
+    p.kchunk = pl.kchunk;
+  }
+  if (pl.kernel == F32_KERNEL_X3) {
+    AVF_REQUIRE(ceil_div(p.M, SBM) < 65536, "gemm_f32: M too large for grid");
+    int rc;
+    if (pl.akf && pl.bkf) rc = launch_f32x3<true, true>(p, a.epilogue, pl.S, pl.vec, s);
+    else if (pl.akf) rc = launch_f32x3<true, false>(p, a.epilogue, pl.S, pl.vec, s);
+    else if (pl.bkf) rc = launch_f32x3<false, true>(p, a.epilogue, pl.S, pl.vec, s);
+    else rc = launch_f32x3<false, false>(p, a.epilogue, pl.S, pl.vec, s);
+    AVF_TRY(rc);
+    return pl.S > 1 ? launch_f32_fold(p, a, pl.S, s) : 0;
+  }
+  const bool small = pl.kernel == F32_KERNEL_MFMA_T1;
+  if (pl.S > 1) {
+    return small ? launch_f32_split<1>(p, a, pl.S, "gemm_f32_kernel(split)", s)
+                 : launch_f32_split<2>(p, a, pl.S, "gemm_f32_kernel(split64)", s);
+  }
   const int bt = small ? 32 : 64;
   dim3 grid((unsigned)ceil_div(a.N, bt), (unsigned)ceil_div(a.M, bt));
   AVF_REQUIRE(grid.y < 65536, "gemm_f32: M too large for grid");

@@ -455,6 +455,154 @@ def gemm_tn_group(pairs, outs=None, workspace=None):
     return Cs
 
 
+F32_KERNELS = ("x3", "mfma_t1", "mfma_t2")
+_F32_MISALIGN_BITS = ("a", "b", "out", "bias", "residual", "aux", "workspace")
+
+
+def gemm_f32_plan(M: int, N: int, K: int, trans_a: bool = False, trans_b: bool = True, epilogue: int = EPI_NONE,
+                  bias: bool = False, workspace: bool = True, lda: Optional[int] = None, ldb: Optional[int] = None,
+                  ldc: Optional[int] = None, ldres: Optional[int] = None, ldaux: Optional[int] = None, misaligned=()) -> dict:
+    """What ``gemm_f32_ex`` decides for these arguments under the fp32 arithmetic selected now (avf_gemm_f32_plan: the
+    launcher's own decision, host code only, no device needed): dict(kernel = "x3" (gemm_f32x3_kernel) | "mfma_t1" | "mfma_t2"
+    (gemm_f32_kernel on 32 x 32 / 64 x 64 tiles), akf / bkf = the reduction is the unit-stride axis of A / B, S = split count,
+    kchunk = reduction rows per split (0 unsplit), vec = 16-byte epilogue accesses of the x3 kernel).  Leading dimensions
+    default to the dense ones; misaligned: names among a, b, out, bias, residual, aux, workspace of operands that are not
+    16-byte aligned."""
+    mask = sum(1 << _F32_MISALIGN_BITS.index(n) for n in misaligned)
+    out = (C.c_int32 * 6)()
+    _lib.check(_lib.load().avf_gemm_f32_plan(int(trans_a), int(trans_b), int(M), int(N), int(K),
+                                             int((M if trans_a else K) if lda is None else lda),
+                                             int((K if trans_b else N) if ldb is None else ldb), int(N if ldc is None else ldc),
+                                             int(epilogue), int(bool(bias)), int(N if ldres is None else ldres),
+                                             int(N if ldaux is None else ldaux), int(bool(workspace)), mask, out), "gemm_f32_plan")
+    return dict(kernel=F32_KERNELS[out[0]], akf=bool(out[1]), bkf=bool(out[2]), S=int(out[3]), kchunk=int(out[4]), vec=bool(out[5]))
+
+
+def gemm_f32_workspace_bytes(M: int, N: int, K: int, trans_a: bool = False, trans_b: bool = True) -> int:
+    """the split-K workspace avf_gemm_workspace_bytes promises an fp32 GEMM of this shape (0: it never splits)"""
+    return int(_lib.load().avf_gemm_workspace_bytes(F32, int(trans_a), int(trans_b), int(M), int(N), int(K)))
+
+
+def _f32_view(who: str, name: str, t: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
+    if not (t.dim() == 2 and tuple(t.shape) == (rows, cols) and t.stride(1) == 1 and t.stride(0) >= cols and t.dtype == torch.float32):
+        raise ValueError(f"{who}: {name} must be a [{rows}, {cols}] fp32 tensor or row-strided view of one "
+                         f"(got {tuple(t.shape)}, strides {t.stride()}, {t.dtype})")
+    return t
+
+
+def gemm_f32_ex(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool = True, out: Optional[torch.Tensor] = None,
+                epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                aux: Optional[torch.Tensor] = None, drop=None, workspace=True):
+    """C = epilogue(op(A) op(B)) on the fp32 GEMM family (avf_gemm_f32_ex) with the dropout site a layer call can ask of it.
+    a is [M, K] ([K, M] with trans_a), b is [N, K] with trans_b ([K, N] without); out / residual / aux [M, N]; all fp32, all
+    used in place as row-strided views (leading dimension = row stride, any alignment).  A 1-D residual [N] is the broadcast
+    row (ldres = 0).  EPI_BIAS_GELU writes aux (made here when not given), EPI_DGELU reads it.  drop: (seed, layer, site, p) as
+    ops.dropout_factors takes them, or None.  workspace: True = what avf_gemm_workspace_bytes asks for, made here; False / None
+    = none (the call runs unsplit); or a contiguous tensor to hold the split-K slabs.
+    Returns (C, aux or None, plan) with plan = gemm_f32_plan of exactly this call."""
+    who = "gemm_f32_ex"
+    _need_cuda(a, b, out, bias, residual, aux)
+    lib = _lib.load()
+    if a.dim() != 2 or b.dim() != 2:
+        raise ValueError(f"{who}: a and b are 2-D (got {tuple(a.shape)}, {tuple(b.shape)})")
+    M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
+    N, Kb = (b.shape[0], b.shape[1]) if trans_b else (b.shape[1], b.shape[0])
+    if K != Kb:
+        raise ValueError(f"{who}: reduction lengths differ ({tuple(a.shape)}, {tuple(b.shape)}, trans_a={trans_a}, trans_b={trans_b})")
+    a = _f32_view(who, "a", a, *a.shape)
+    b = _f32_view(who, "b", b, *b.shape)
+    c = _f32_view(who, "out", out, M, N) if out is not None else torch.empty((M, N), dtype=torch.float32, device=a.device)
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,) or bias.stride(0) != 1):
+        raise TypeError(f"{who}: bias is a unit-stride fp32 [N]")
+    if (residual is not None) != (epilogue == EPI_BIAS_RES):
+        raise ValueError(f"{who}: a residual goes with EPI_BIAS_RES, and only with it")
+    if epilogue == EPI_DGELU and aux is None:
+        raise ValueError(f"{who}: EPI_DGELU reads aux, the saved pre-activation")
+    if epilogue in (EPI_NONE, EPI_BIAS_RES) and aux is not None:
+        raise ValueError(f"{who}: aux goes with EPI_BIAS_GELU / EPI_DGELU only")
+    if epilogue == EPI_BIAS_GELU and aux is None:
+        aux = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    ldres = N
+    if residual is not None:
+        if residual.dim() == 1:
+            if residual.dtype != torch.float32 or tuple(residual.shape) != (N,) or residual.stride(0) != 1:
+                raise TypeError(f"{who}: a broadcast residual is a unit-stride fp32 [N]")
+            ldres = 0
+        else:
+            ldres = _f32_view(who, "residual", residual, M, N).stride(0)
+    ldaux = _f32_view(who, "aux", aux, M, N).stride(0) if aux is not None else N
+    if workspace is True:
+        ws = _bytes(gemm_f32_workspace_bytes(M, N, K, trans_a, trans_b), a.device)
+    elif workspace is False or workspace is None:
+        ws = None
+    else:
+        ws = workspace
+        _need_cuda(ws)
+        if not ws.is_contiguous() or ws.numel() * ws.element_size() < gemm_f32_workspace_bytes(M, N, K, trans_a, trans_b):
+            raise ValueError(f"{who}: workspace must be contiguous and hold what gemm_f32_workspace_bytes asks for")
+    seed, layer, site, p = drop if drop is not None else (0, 0, 0, 0.0)
+    named = (("a", a), ("b", b), ("out", c), ("bias", bias), ("residual", residual), ("aux", aux), ("workspace", ws))
+    plan = gemm_f32_plan(M, N, K, trans_a, trans_b, epilogue, bias is not None, ws is not None, a.stride(0), b.stride(0),
+                         c.stride(0), ldres, ldaux, [n for n, t in named if t is not None and t.data_ptr() % 16])
+    _lib.check(lib.avf_gemm_f32_ex(int(trans_a), int(trans_b), M, N, K, _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c),
+                                   c.stride(0), int(epilogue), _ptr(bias), _ptr(residual), ldres, _ptr(aux), ldaux, _ptr(ws),
+                                   seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, layer, site, float(p), _stream()), who)
+    return c, aux, plan
+
+
+def gemm_f32_tn_group_plan(shapes, K: int) -> dict:
+    """What ``gemm_f32_tn_group`` decides for problems of the shapes [(M_i, N_i), ...] over K reduction rows under the fp32
+    arithmetic selected now (avf_gemm_f32_tn_group_plan, host code only): dict(ok = the grouped bf16x3 launch takes them,
+    tiles = 128 x 128 tiles of the group, S = split count, kchunk = rows per split, workspace_bytes = what
+    avf_gemm_f32_tn_group_workspace_bytes promises)."""
+    lib = _lib.load()
+    n = len(shapes)
+    Ms = (C.c_int64 * n)(*[int(m) for m, _ in shapes])
+    Ns = (C.c_int64 * n)(*[int(k) for _, k in shapes])
+    out = (C.c_int32 * 4)()
+    _lib.check(lib.avf_gemm_f32_tn_group_plan(n, int(K), Ms, Ns, out), "gemm_f32_tn_group_plan")
+    return dict(ok=bool(out[0]), tiles=int(out[1]), S=int(out[2]), kchunk=int(out[3]),
+                workspace_bytes=int(lib.avf_gemm_f32_tn_group_workspace_bytes(n, int(K), Ms, Ns)))
+
+
+def gemm_f32_tn_group(pairs, outs=None, workspace=None):
+    """[(A_i [K, M_i] fp32, B_i [K, N_i] fp32), ...] (2 .. 4, same K) -> [C_i [M_i, N_i] fp32 = A_i^T B_i] in the bf16x3
+    arithmetic: the one launch that makes the weight gradients of a parity-mode layer (avf_gemm_f32_tn_group).  The operands
+    are used in place as row-strided views (lda / ldb = their row strides), as the layer passes them.  outs: contiguous fp32
+    [M_i, N_i] tensors to write into (returned); workspace: a contiguous, 16-byte aligned tensor of at least
+    gemm_f32_tn_group_plan(...)["workspace_bytes"].  Raises where the plan says the group is not eligible."""
+    who = "gemm_f32_tn_group"
+    lib = _lib.load()
+    n = len(pairs)
+    K = pairs[0][0].shape[0]
+    As = [_f32_view(who, "A", a, K, a.shape[1]) for a, _ in pairs]
+    Bs = [_f32_view(who, "B", b, K, b.shape[1]) for _, b in pairs]
+    _need_cuda(*As, *Bs)
+    shapes = [(a.shape[1], b.shape[1]) for a, b in zip(As, Bs)]
+    Ms = (C.c_int64 * n)(*[m for m, _ in shapes])
+    Ns = (C.c_int64 * n)(*[k for _, k in shapes])
+    lda = (C.c_int64 * n)(*[a.stride(0) for a in As])
+    ldb = (C.c_int64 * n)(*[b.stride(0) for b in Bs])
+    if outs is None:
+        Cs = [torch.empty(s, dtype=torch.float32, device=As[0].device) for s in shapes]
+    else:
+        Cs = list(outs)
+        _need_cuda(*Cs)
+        if len(Cs) != n or not all(c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == s for c, s in zip(Cs, shapes)):
+            raise ValueError(f"{who}: outs are contiguous fp32 [M_i, N_i] tensors, one per pair")
+    need = int(lib.avf_gemm_f32_tn_group_workspace_bytes(n, K, Ms, Ns))
+    if workspace is None:
+        ws = _bytes(need, As[0].device)
+    else:
+        ws = workspace
+        _need_cuda(ws)
+        if not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+            raise ValueError(f"{who}: workspace must be contiguous, 16-byte aligned and hold {need} bytes")
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    _lib.check(lib.avf_gemm_f32_tn_group(n, K, arr(As), lda, arr(Bs), ldb, arr(Cs), Ms, Ns, _ptr(ws), _stream()), who)
+    return Cs
+
+
 def quant_mx8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """[rows, cols] f32|bf16 -> (e4m3 bytes [rows, cols] uint8, E8M0 scale bytes [rows, cols/32] uint8)."""
     _need_cuda(x)

@@ -62,6 +62,50 @@ def hip_transformer_run(t, x, loss_fn):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Guarded outputs and NaN-surrounded operands of the element-wise GEMM tests (test_gpu_gemm_nt.py, test_gpu_gemm_f32.py):
+# a kernel that writes outside its output meets a sentinel, one that reads outside an operand meets a NaN.
+# ------------------------------------------------------------------------------------------------------------------
+SENTINEL = -24576.0  # exact in bf16
+F32 = torch.float32
+
+
+def _pre_rows(ld, dtype):
+    """guard rows in front of a view: one, or two where one row is not a multiple of 16 bytes (the view stays aligned)"""
+    return 1 if (ld * torch.empty((), dtype=dtype).element_size()) % 16 == 0 else 2
+
+
+def _guarded(M, N, dtype, pad=8):
+    """an [M, N] output view in a sentinel parent: guard rows before and after, sentinel columns N .. N + pad - 1"""
+    ld = N + pad
+    pre = _pre_rows(ld, dtype)
+    buf = torch.full((M + pre + 1, ld), SENTINEL, dtype=dtype, device="cuda")
+    return buf, buf[pre:pre + M, :N], pre
+
+
+def _guards_intact(what, buf, view, pre):
+    M, N = view.shape
+    ok = bool((buf[:pre] == SENTINEL).all()) and bool((buf[pre + M:] == SENTINEL).all()) and bool((buf[:, N:] == SENTINEL).all())
+    assert ok, what + ": a write outside the output"
+
+
+def _in_nan(t, pad=8):
+    """a copy of the 2-D operand t on the device as a view into a NaN parent: `pad` NaN columns per row, NaN rows around"""
+    M, N = t.shape
+    ld = N + pad
+    pre = _pre_rows(ld, t.dtype)
+    buf = torch.full((M + pre + 1, ld), float("nan"), dtype=t.dtype, device="cuda")
+    view = buf[pre:pre + M, :N]
+    view.copy_(t)
+    return view
+
+
+def _bias_in_nan(b):
+    buf = torch.full((b.numel() + 8,), float("nan"), dtype=F32, device="cuda")
+    buf[4:4 + b.numel()] = b
+    return buf[4:4 + b.numel()]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Calibrated low-precision bounds.  A bf16 / mx8 assertion states a CAP (what the format allows in the worst case)
 # and is additionally held to 3x the error MEASURED for that exact case on an MI355X, recorded in
 # tests/golden/lowp_measured.json (written by a calibration run: AVF_RECORD_ERRORS=<path> pytest -m gpu, then

@@ -36,11 +36,11 @@ import pytest
 import torch
 
 import gemm_nt_util as G
+from gpu_util import SENTINEL, _bias_in_nan, _guarded, _guards_intact, _in_nan  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BF, F32 = torch.bfloat16, torch.float32
-SENTINEL = -24576.0  # exact in bf16
 DROP = (0x1234567887654321, 2, 1, 0.2)  # (seed, layer, site, p) as ops.dropout_factors takes them
 EPIS = (G.EPI_NONE, G.EPI_BIAS_RES, G.EPI_BIAS_GELU, G.EPI_DGELU)
 
@@ -74,42 +74,6 @@ def _note(plan):
     if plan["kind"] == 1:
         REACHED.add(("tile", plan["tile"]))
         REACHED.add(("lean", plan["lean"]))
-
-
-def _pre_rows(ld, dtype):
-    """guard rows in front of a view: one, or two where one row is not a multiple of 16 bytes (the view stays aligned)"""
-    return 1 if (ld * torch.empty((), dtype=dtype).element_size()) % 16 == 0 else 2
-
-
-def _guarded(M, N, dtype, pad=8):
-    """an [M, N] output view in a sentinel parent: guard rows before and after, sentinel columns N .. N + pad - 1"""
-    ld = N + pad
-    pre = _pre_rows(ld, dtype)
-    buf = torch.full((M + pre + 1, ld), SENTINEL, dtype=dtype, device="cuda")
-    return buf, buf[pre:pre + M, :N], pre
-
-
-def _guards_intact(what, buf, view, pre):
-    M, N = view.shape
-    ok = bool((buf[:pre] == SENTINEL).all()) and bool((buf[pre + M:] == SENTINEL).all()) and bool((buf[:, N:] == SENTINEL).all())
-    assert ok, what + ": a write outside the output"
-
-
-def _in_nan(t, pad=8):
-    """a copy of the 2-D operand t on the device as a view into a NaN parent: `pad` NaN columns per row, NaN rows around"""
-    M, N = t.shape
-    ld = N + pad
-    pre = _pre_rows(ld, t.dtype)
-    buf = torch.full((M + pre + 1, ld), float("nan"), dtype=t.dtype, device="cuda")
-    view = buf[pre:pre + M, :N]
-    view.copy_(t)
-    return view
-
-
-def _bias_in_nan(b):
-    buf = torch.full((b.numel() + 8,), float("nan"), dtype=F32, device="cuda")
-    buf[4:4 + b.numel()] = b
-    return buf[4:4 + b.numel()]
 
 
 _cache = {}
