@@ -274,6 +274,23 @@ int avf_gemm_mx8_nt(int64_t M, int64_t N, int64_t K, const void* a_q, const void
                     const void* b_scales, void* C, int64_t ldc, int c_dtype, int epilogue, const float* bias,
                     const float* residual, int64_t ldres, void* aux, int64_t ldaux, void* c_q, void* c_scales,
                     void* stream);
+/* Test plumbing for the MX-FP8 NT GEMM: the same kernel family as avf_gemm_mx8_nt with what only a layer call could ask of it
+ * so far.  lda / ldb: row strides of the e4m3 images in BYTES (multiples of 16; the scale images stay dense, [rows][K/32]);
+ * residual and aux in C's type with their own leading dimensions; colsum (nullable) fp32 [N]: column sums over the rows of the
+ * values behind the stored C (fp32, before their rounding to c_dtype), needs workspace >= avf_gemm_nt_ws_workspace_bytes(M, N);
+ * (seed_lo, seed_hi, layer_index, site, p): a dropout site as avf_gemm_nt_ex takes it (element index m * N + n, p == 0 is no
+ * dropout, not on AVF_EPI_NONE); c_q / c_scales as avf_gemm_mx8_nt.
+ * avf_gemm_mx8_nt_plan: which instantiation that call runs, decided by the function the launcher itself acts on.  Pointers are
+ * replaced by their presence (every operand 16-byte aligned).  *tile: the tile configuration's id; *lean: the LEAN code
+ * (0 = general epilogue, 1 = lean, + 2 = with column sums, + 4 = with the MX-FP8 image of C). */
+int avf_gemm_mx8_nt_ex(int64_t M, int64_t N, int64_t K, const void* a_q, int64_t lda, const void* a_scales, const void* b_q,
+                       int64_t ldb, const void* b_scales, void* C, int64_t ldc, int c_dtype, int epilogue, const float* bias,
+                       const void* residual, int64_t ldres, void* aux, int64_t ldaux, void* workspace, float* colsum,
+                       uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site, float p, void* c_q, void* c_scales,
+                       void* stream);
+int avf_gemm_mx8_nt_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int c_dtype, int epilogue,
+                         int has_bias, int64_t ldres, int64_t ldaux, int want_colsum, float p, int want_image, int* tile,
+                         int* lean);
 /* nn.LayerNorm forward (heads.py:178-185) writing the bf16 output AND its MX-FP8 image (dim % 32 == 0, dim <= 1536) */
 int avf_layernorm_fwd_mx8(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd,
                           void* y_q, void* y_scales, int64_t rows, int dim, float eps, void* stream);

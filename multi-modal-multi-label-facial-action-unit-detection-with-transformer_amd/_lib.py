@@ -104,6 +104,10 @@ SIGNATURES = {
     "avf_quant_mx8": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp]),
     "avf_gemm_mx8_nt": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64,
                                _vp, _vp, _vp]),
+    "avf_gemm_mx8_nt_ex": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64,
+                                  _vp, _vp, C.c_uint32, C.c_uint32, _int, _int, _f, _vp, _vp, _vp]),
+    "avf_gemm_mx8_nt_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _i64, _i64, _int, _f, _int,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "avf_layernorm_fwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _vp]),
     "avf_attn_fwd": (_int, [_int, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "avf_attn_bwd_workspace_bytes": (_sz, [_int, _int, _int, _int]),

@@ -503,6 +503,41 @@ extern "C" int avf_gemm_mx8_nt(int64_t M, int64_t N, int64_t K, const void* a_q,
   a.aux = aux; a.ldaux = ldaux;
   return gemm_mx8_nt(a, a_scales, b_scales, (hipStream_t)stream, c_q, c_scales);
 }
+// ---- the MX-FP8 NT GEMM with everything a layer can ask of it (test plumbing) ----
+extern "C" int avf_gemm_mx8_nt_ex(int64_t M, int64_t N, int64_t K, const void* a_q, int64_t lda, const void* a_scales,
+                                  const void* b_q, int64_t ldb, const void* b_scales, void* C, int64_t ldc, int c_dtype,
+                                  int epilogue, const float* bias, const void* residual, int64_t ldres, void* aux, int64_t ldaux,
+                                  void* workspace, float* colsum, uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site,
+                                  float p, void* c_q, void* c_scales, void* stream) {
+  AVF_REQUIRE(a_q && a_scales && b_q && b_scales && C, "gemm_mx8_nt_ex: null pointer");
+  AVF_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || (site >= 0 && site < 3)), "gemm_mx8_nt_ex: bad dropout site %d / p %g", site, (double)p);
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = a_q; a.lda = lda; a.B = b_q; a.ldb = ldb; a.C = C; a.ldc = ldc;
+  a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
+  a.aux = aux; a.ldaux = ldaux; a.workspace = workspace; a.colsum = colsum;
+  if (p > 0.f) a.drop = make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site);
+  return gemm_mx8_nt(a, a_scales, b_scales, (hipStream_t)stream, c_q, c_scales);
+}
+extern "C" int avf_gemm_mx8_nt_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int c_dtype,
+                                    int epilogue, int has_bias, int64_t ldres, int64_t ldaux, int want_colsum, float p,
+                                    int want_image, int* tile, int* lean) {
+  AVF_REQUIRE(tile && lean, "gemm_mx8_nt_plan: null pointer");
+  AVF_REQUIRE(p >= 0.f && p < 1.f, "gemm_mx8_nt_plan: bad dropout p %g", (double)p);
+  void* aligned = (void*)(uintptr_t)256;  // never dereferenced: the predicates look at null-ness and alignment only
+  GemmArgs a = gemm_dense(AVF_BF16, 0, 1, M, N, K);
+  a.A = aligned; a.lda = lda; a.B = aligned; a.ldb = ldb; a.C = aligned; a.ldc = ldc;
+  a.c_dtype = c_dtype; a.epilogue = epilogue; a.ldres = ldres; a.ldaux = ldaux;
+  if (has_bias) a.bias = (const float*)aligned;
+  if (epilogue == AVF_EPI_BIAS_RES) a.residual = aligned;
+  if (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) a.aux = aligned;
+  if (want_colsum) { a.workspace = aligned; a.colsum = (float*)aligned; }
+  if (want_image) { a.mx_q = aligned; a.mx_s = aligned; }
+  if (p > 0.f) a.drop = make_drop(p, 1, 0, 0);
+  NtPlan pl;
+  AVF_TRY(gemm_mx8_nt_plan(a, &pl));
+  *tile = pl.tile; *lean = pl.lean;
+  return 0;
+}
 
 extern "C" int avf_attn_fwd(int dtype, const void* qkv, void* o, float* lse2, int batch, int tokens, int heads,
                             int dim_head, void* stream) {

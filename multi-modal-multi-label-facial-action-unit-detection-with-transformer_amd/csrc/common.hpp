@@ -602,6 +602,10 @@ int gemm_bf16_tn(const GemmArgs& a, hipStream_t s);
 // mx_q / mx_s (optional, BIAS_GELU only): also write the MX-FP8 image of C ([M,N] e4m3 + [M,N/32] E8M0)
 int gemm_mx8_nt(const GemmArgs& a, const void* a_scales, const void* b_scales, hipStream_t s, void* mx_q = nullptr,
                 void* mx_s = nullptr);
+// Which instantiation gemm_mx8_nt runs (the image of C asked for through a.mx_q / a.mx_s): the launcher acts on exactly this
+// (nt_plan_mx8 in gemm_mx8.hip).  kind = 1 and wpf = 0 always; lean = 0 general epilogue, 1 = lean, + 2 = with column sums,
+// + 4 = with the MX-FP8 image of C.  Pointers are looked at for null-ness and alignment only.
+int gemm_mx8_nt_plan(const GemmArgs& a, NtPlan* out);
 struct MxQuantJob {
   const void* x;  // bf16 [R,K]
   void* q;        // e4m3 [R,K]

@@ -193,16 +193,23 @@ int launch_mx8(const Mx8Params& q, hipStream_t s, int* part_rows, TimingScope* t
 constexpr bool mx8_lean_exists(int epi, int lean) {
   return lean == 0 || ((!(lean & 2) || epi == AVF_EPI_DGELU) && (!(lean & 4) || epi == AVF_EPI_BIAS_GELU || epi == AVF_EPI_DGELU));
 }
+// The one place that decides which instantiation a call runs: the tile and the LEAN code.  gemm_mx8_nt launches what this
+// returns; gemm_mx8_nt_plan reports it.  (kind = 1 and wpf = 0 always: one kernel, no weight warm-up.)
 template <int EPI, typename CT>
-int launch_mx8_any(const Mx8Params& q, hipStream_t s, int* part_rows, TimingScope* ts) {
+NtPlan nt_plan_mx8(const NtParams& p) {
   // K/2: the same LDS bytes per row as a bf16 problem of that depth; the kernel has two LDS stages
-  const int tile = pick_nt_tile(q.nt.M, q.nt.N, q.nt.K / 2), ti = nt_tile_index(tile, /*max_stages=*/2);
+  const int tile = pick_nt_tile(p.M, p.N, p.K / 2), ti = nt_tile_index(tile, /*max_stages=*/2);
   // The instantiations are (tile, LEAN): tiles 0, 1, 2, 3, 5 with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every
   // epilogue), 5 (BIAS_GELU, DGELU) and 3, 7 (DGELU).  The lean epilogue (options fixed at compile time) runs when nothing asks
   // for the general one's (and never on an id that only runs as tile 2 because this kernel does not have it).
-  int lean = 1 + (q.nt.cs_partial ? 2 : 0) + (q.nt.mxq ? 4 : 0);
-  if (kNtTiles[ti].id != tile || !kNtTiles[ti].lean() || !mx8_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(q.nt, kNtTiles[ti].bn(), /*mx_ok=*/true))
+  int lean = 1 + (p.cs_partial ? 2 : 0) + (p.mxq ? 4 : 0);
+  if (kNtTiles[ti].id != tile || !kNtTiles[ti].lean() || !mx8_lean_exists(EPI, lean) || !nt_lean_ok<EPI, CT>(p, kNtTiles[ti].bn(), /*mx_ok=*/true))
     lean = 0;
+  return NtPlan{1, kNtTiles[ti].id, ti, lean, 0};
+}
+template <int EPI, typename CT>
+int launch_mx8_any(const Mx8Params& q, const NtPlan& pl, hipStream_t s, int* part_rows, TimingScope* ts) {
+  const int ti = pl.index, lean = pl.lean;
   return with_nt_tile(ti, [&](auto ic) {
     const auto launch = [&](auto lc) {
       constexpr NtTile t = kNtTiles[decltype(ic)::value];
@@ -353,13 +360,27 @@ int gemm_mx8_nt(const GemmArgs& a, const void* a_scales, const void* b_scales, h
   AVF_TRY(require_epilogue_operands(a, "gemm_mx8_nt", 4));
   AVF_TRY(with_epilogue(a.epilogue, "gemm_mx8_nt", [&](auto epi) {
     return with_c_type(a.c_dtype, "gemm_mx8_nt", [&](auto ct) {
-      return launch_mx8_any<decltype(epi)::value, decltype(ct)>(q, s, &part_rows, &ts);
+      return launch_mx8_any<decltype(epi)::value, decltype(ct)>(q, nt_plan_mx8<decltype(epi)::value, decltype(ct)>(q.nt), s,
+                                                                &part_rows, &ts);
     });
   }));
   AVF_TRY(check_launch("gemm_mx8_nt_kernel"));
   AVF_REQUIRE(!a.colsum || (size_t)part_rows * a.N * sizeof(float) <= gemm_nt_colsum_ws(a.M, a.N),
               "gemm_mx8_nt: column-sum partials exceed their workspace (internal error)");
   return finish_colsum(a, p.cs_partial, part_rows, s);
+}
+
+int gemm_mx8_nt_plan(const GemmArgs& a, NtPlan* out) {
+  AVF_REQUIRE(out && a.M > 0 && a.N > 0 && a.K > 0 && a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31) &&
+                  a.K % 128 == 0 && a.N % 4 == 0,
+              "gemm_mx8_nt_plan: bad arguments");
+  const NtParams p = nt_params_from(a);  // (mxq / mxs: a.mx_q / a.mx_s, which gemm_mx8_nt takes as arguments of its own)
+  return with_epilogue(a.epilogue, "gemm_mx8_nt_plan", [&](auto epi) {
+    return with_c_type(a.c_dtype, "gemm_mx8_nt_plan", [&](auto ct) {
+      *out = nt_plan_mx8<decltype(epi)::value, decltype(ct)>(p);
+      return 0;
+    });
+  });
 }
 
 }  // namespace avf

@@ -249,10 +249,10 @@ def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool 
     return c
 
 
-def _row_view(name: str, t: torch.Tensor, rows: int, cols: int, dtype) -> torch.Tensor:
-    """a [rows, cols] operand of gemm_nt_ex, used in place: its row stride is its leading dimension"""
+def _row_view(name: str, t: torch.Tensor, rows: int, cols: int, dtype, who: str = "gemm_nt_ex") -> torch.Tensor:
+    """a [rows, cols] operand of gemm_nt_ex / gemm_mx8_ex, used in place: its row stride is its leading dimension"""
     if not (t.dim() == 2 and tuple(t.shape) == (rows, cols) and t.stride(1) == 1 and t.stride(0) >= cols and t.dtype == dtype):
-        raise ValueError(f"gemm_nt_ex: {name} must be a [{rows}, {cols}] {dtype} tensor or row-strided view of one "
+        raise ValueError(f"{who}: {name} must be a [{rows}, {cols}] {dtype} tensor or row-strided view of one "
                          f"(got {tuple(t.shape)}, strides {t.stride()}, {t.dtype})")
     return t
 
@@ -709,6 +709,89 @@ def gemm_mx8(a_q: torch.Tensor, a_s: torch.Tensor, b_q: torch.Tensor, b_s: torch
     if want_image:
         out = out + (cq, cs)
     return out if len(out) > 1 else out[0]
+
+
+def gemm_mx8_plan(M: int, N: int, K: int, out_dtype=torch.float32, epilogue: int = EPI_NONE, bias: bool = True,
+                  want_colsum: bool = False, p: float = 0.0, want_image: bool = False, lda: Optional[int] = None,
+                  ldb: Optional[int] = None, ldc: Optional[int] = None, ldres: Optional[int] = None,
+                  ldaux: Optional[int] = None) -> dict:
+    """Which instantiation ``gemm_mx8_ex`` runs for these arguments (avf_gemm_mx8_nt_plan; 16-byte aligned operands assumed):
+    dict(tile = the tile id, lean = the LEAN code: 0 general epilogue, 1 lean, + 2 column sums, + 4 MX-FP8 image of C).
+    Leading dimensions default to the dense ones (lda, ldb in bytes)."""
+    out = [C.c_int(-1) for _ in range(2)]
+    _lib.check(_lib.load().avf_gemm_mx8_nt_plan(int(M), int(N), int(K), int(K if lda is None else lda), int(K if ldb is None else ldb),
+                                                int(N if ldc is None else ldc), avf_dtype(torch_dtype(out_dtype)), int(epilogue),
+                                                int(bool(bias)), int(N if ldres is None else ldres),
+                                                int(N if ldaux is None else ldaux), int(bool(want_colsum)), float(p),
+                                                int(bool(want_image)), *[C.byref(o) for o in out]), "gemm_mx8_nt_plan")
+    return dict(tile=out[0].value, lean=out[1].value)
+
+
+def gemm_mx8_ex(a_q: torch.Tensor, a_s: torch.Tensor, b_q: torch.Tensor, b_s: torch.Tensor, out: Optional[torch.Tensor] = None,
+                out_dtype=None, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+                residual: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None, want_colsum: bool = False, drop=None,
+                want_image: bool = False):
+    """C = epilogue(A B^T) from MX-FP8 images (avf_gemm_mx8_nt_ex) with the column sums, the dropout site and the operand /
+    output views a layer call can ask of the kernel.  a_q [M, K], b_q [N, K] uint8 (row-strided views allowed: the row stride
+    in bytes is the leading dimension); a_s [M, K/32], b_s [N, K/32] uint8, contiguous; out / residual / aux [M, N] in C's type,
+    row-strided views allowed.  EPI_BIAS_GELU writes aux (made here when not given), EPI_DGELU reads it.  drop: (seed, layer,
+    site, p) as ops.dropout_factors takes them, or None.  want_image: also the MX-FP8 image of C (BIAS_GELU / DGELU, N % 32 == 0);
+    True, or the pair of buffers to write it to.
+    Returns (C, aux or None, column sums or None, (image bytes, image scales) or None, plan) with plan = gemm_mx8_plan of
+    exactly this call."""
+    _need_cuda(a_q, a_s, b_q, b_s, out, bias, residual, aux)
+    lib = _lib.load()
+    if a_q.dim() != 2 or b_q.dim() != 2 or a_q.shape[1] != b_q.shape[1]:
+        raise ValueError(f"gemm_mx8_ex: a_q is [M, K] and b_q is [N, K] (got {tuple(a_q.shape)}, {tuple(b_q.shape)})")
+    M, K = a_q.shape
+    N = b_q.shape[0]
+    a_q = _row_view("a_q", a_q, M, K, torch.uint8, "gemm_mx8_ex")
+    b_q = _row_view("b_q", b_q, N, K, torch.uint8, "gemm_mx8_ex")
+    for name, t, rows in (("a_s", a_s, M), ("b_s", b_s, N)):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (rows, K // 32) or not t.is_contiguous():
+            raise ValueError(f"gemm_mx8_ex: {name} must be a contiguous uint8 [{rows}, {K // 32}]")
+    cdt = out.dtype if out is not None else (torch_dtype(out_dtype) if out_dtype is not None else torch.float32)
+    if cdt not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"gemm_mx8_ex: C is bf16 or fp32, not {cdt}")
+    c = torch.empty((M, N), dtype=cdt, device=a_q.device) if out is None else _row_view("out", out, M, N, cdt, "gemm_mx8_ex")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,) or not bias.is_contiguous()):
+        raise TypeError("gemm_mx8_ex: bias is a contiguous fp32 [N]")
+    if (residual is not None) != (epilogue == EPI_BIAS_RES):
+        raise ValueError("gemm_mx8_ex: a residual goes with EPI_BIAS_RES, and only with it")
+    if epilogue == EPI_DGELU and aux is None:
+        raise ValueError("gemm_mx8_ex: EPI_DGELU reads aux, the saved pre-activation")
+    if epilogue in (EPI_NONE, EPI_BIAS_RES) and aux is not None:
+        raise ValueError("gemm_mx8_ex: aux goes with EPI_BIAS_GELU / EPI_DGELU only")
+    if epilogue == EPI_BIAS_GELU and aux is None:
+        aux = torch.empty((M, N), dtype=cdt, device=a_q.device)
+    if residual is not None:
+        residual = _row_view("residual", residual, M, N, cdt, "gemm_mx8_ex")
+    if aux is not None:
+        aux = _row_view("aux", aux, M, N, cdt, "gemm_mx8_ex")
+    seed, layer, site, p = drop if drop is not None else (0, 0, 0, 0.0)
+    cs = torch.empty(N, dtype=torch.float32, device=a_q.device) if want_colsum else None
+    ws = _bytes(lib.avf_gemm_nt_ws_workspace_bytes(M, N), a_q.device) if want_colsum else None
+    if isinstance(want_image, tuple):  # the caller's buffers: contiguous uint8 [M, N] and [M, N / 32]
+        cq, csc = want_image
+        if not (cq.dtype == csc.dtype == torch.uint8 and tuple(cq.shape) == (M, N) and tuple(csc.shape) == (M, N // 32) and
+                cq.is_contiguous() and csc.is_contiguous() and cq.is_cuda and csc.is_cuda):
+            raise ValueError("gemm_mx8_ex: the image buffers are contiguous uint8 [M, N] and [M, N / 32] on the device")
+        want_image = True
+    else:
+        cq = torch.empty((M, N), dtype=torch.uint8, device=a_q.device) if want_image else None
+        csc = torch.empty((M, N // 32), dtype=torch.uint8, device=a_q.device) if want_image else None
+    ldres = residual.stride(0) if residual is not None else N
+    ldaux = aux.stride(0) if aux is not None else N
+    plan = gemm_mx8_plan(M, N, K, cdt, epilogue, bias is not None, want_colsum, p, want_image, a_q.stride(0), b_q.stride(0),
+                         c.stride(0), ldres, ldaux)
+    for name, t in (("a_q", a_q), ("b_q", b_q), ("out", c), ("bias", bias), ("residual", residual), ("aux", aux)):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"gemm_mx8_ex: {name} must be 16-byte aligned")
+    _lib.check(lib.avf_gemm_mx8_nt_ex(M, N, K, _ptr(a_q), a_q.stride(0), _ptr(a_s), _ptr(b_q), b_q.stride(0), _ptr(b_s), _ptr(c),
+                                      c.stride(0), avf_dtype(cdt), int(epilogue), _ptr(bias), _ptr(residual), ldres, _ptr(aux),
+                                      ldaux, _ptr(ws), _ptr(cs), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, layer, site,
+                                      float(p), _ptr(cq), _ptr(csc), _stream()), "gemm_mx8_nt_ex")
+    return c, aux, cs, ((cq, csc) if want_image else None), plan
 
 
 def attn_fwd(qkv: torch.Tensor, batch: int, tokens: int, heads: int, dim_head: int, q_prescaled: bool = False):

@@ -1,0 +1,315 @@
+"""fp64 reference, element-wise bounds, exact data families and mutants for the MX-FP8 NT GEMM (csrc/gemm_mx8.hip:
+gemm_mx8_nt_kernel; csrc/gemm_nt.hpp: nt_epilogue, nt_epilogue_lean_body).  CPU only: tests/test_gpu_gemm_mx8.py feeds it what the
+device returned, tests/test_gemm_mx8_ref_cpu.py shows without a device that the checks bite.
+
+The operation: A = dequant(a_q, a_s) [M, K], B = dequant(b_q, b_s) [N, K] (e4m3 bytes times 2^(E8M0 byte - 127) per 32
+consecutive k: every value is an fp32 value, oracle.mx8_dequant is exact), P = A B^T, then the epilogues, the dropout site and
+the column sums of tests/gemm_nt_util.py (reference and check_outputs are that module's; only the accumulation bound eP is
+this family's own).
+
+Operand families, built as images directly (only "quantised" goes through a quantiser):
+  "dense-int"  elements in {0, +-1, +-2}; A scale bytes 127 .. 130 and B scale bytes 118 .. 121, drawn independently for every
+               32-block.  The 128 terms of one instruction span at most 2^8 (elements 2^2, scales 2^6), far inside the ~2^17
+               alignment window the kernel's header records; every partial sum is an integer times 2^-9 below 2^24
+               (|sum| <= magP <= K / 2), so the fp32 accumulator holds P exactly in any order: eP = 0.  std(P) is about 1.6 at
+               K = 384: u = P + bias lies in the live range of the GELU.
+  "sparse-a"   one-block-wide A: one non-zero 32-block per row of A at a random block index, the others all-zero with scale byte
+               0 (what the quantiser writes for a zero block); B dense, every block non-zero.  Non-zero blocks: elements in
+               {0, +-1, +-2} with at least one non-zero, scale bytes uniform in 87 .. 167.  Each C element is 2^(sa + sb - 254)
+               times a sum of 32 small integers: exact under any alignment window and any accumulation order (eP = 0), an fp32
+               normal or zero, |P| from 2^-80 to ~2^84.
+  "sparse-b"   the same with the roles exchanged: dense A, one-block-wide B.
+  "unit"       elements in {0, +-1} (A one in eight non-zero), every scale byte 127: P is a small integer, so that with
+               aux = 30 (gelu' = 1 exactly in the kernel's fast form: e = exp2(-large) = 0, s = 1, u s (1 - s) = 0) DGELU stores P,
+               and with bias = 64 BIAS_GELU stores u = P + 64 (gelu(u) = u / (1 + 0)), both bf16-representable: the fp32 value the
+               epilogue quantises IS the stored bf16 value.
+  "quantised"  randn data (A rows scaled by 2^-3 .. 2^3, B by 0.05) through the quantiser, as tests/test_gpu_mx8.py builds it.
+               Carries the project's stated accumulation bound eP = 2e-3 magP (the matrix core aligns the 128 products of one
+               instruction to the largest and truncates what lies ~2^17 below; tests/test_gpu_mx8.py reports up to 4e-4).
+
+Checks.  Every output element-wise within gemm_nt_util's bounds with this family's eP (check_outputs).  For eP = 0 the only terms
+left are the epilogue's own fp32 roundings and the activation's; beyond that, bit for bit (check_exact):
+  EPI_NONE   fp32 C == P, bf16 C == bf16(P)                                    (every exact family)
+  BIAS_RES   without dropout, "dense-int": bias and residual are multiples of 2^-9 (2^-4) below 2^3, P + bias + res is a
+             multiple of 2^-9 below 2^10: fp32 C == P + bias + res, bf16 C == bf16 of it
+  BIAS_GELU  aux == P + bias in fp32, bf16 of it in bf16                        ("dense-int", "unit")
+
+The MX-FP8 image of C (contract, read from nt_epilogue and nt_epilogue_lean_body: both quantise mxv = v, the fp32 value of the
+epilogue BEFORE its rounding to C's type, dropout factors included): image == oracle.mx8_quant(v).  With fp32 C v is the stored
+C, so the image must be the conversion of the stored tensor bit for bit on any data.  With bf16 C v is not observable; the
+"unit" family makes v the stored value, and there the image must again be the conversion of the stored tensor.  On general data
+the two candidate sources differ (image_contracts_differ): a kernel that quantised the rounded bf16 value would be refused by
+the fp32-C check's analogue; simulate(image="fp32" | "bf16") returns either, and tests/test_gemm_mx8_ref_cpu.py shows that a
+check stating one contract refuses an image made by the other, both ways.
+
+Mutants: simulate(..., mutant=) returns what a subtly wrong kernel would; see MUTANTS."""
+import torch
+
+import gemm_nt_util as G
+import oracle
+
+EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = G.EPI_NONE, G.EPI_BIAS_RES, G.EPI_BIAS_GELU, G.EPI_DGELU
+EPI_NAMES = G.EPI_NAMES
+EXACT_FAMILIES = ("dense-int", "sparse-a", "sparse-b", "unit")
+FAMILIES = EXACT_FAMILIES + ("quantised",)
+ACC_REL = 2e-3  # "quantised": the stated accumulation bound, relative to magP
+# The variants launch_mx8_any can pick (pick_nt_tile on (M, N, K / 2), kWorkgroupSlots = 512) and the smallest shapes (M, N, K) that
+# select each and still cover: a ragged and a full last row tile, N < 128, one K-step, an odd number of K-steps (both LDS
+# stages, the last one differs), K = 1024.  name -> (tile, lean tile: N % 128 == 0 on an 8-wave tile, shapes)
+VARIANTS = {
+    "TILE5_LEAN": (5, True, [(7, 128, 128), (200, 256, 384), (96, 128, 1024)]),
+    "TILE5_GEN": (5, False, [(100, 36, 256), (2100, 264, 128), (130, 160, 384)]),
+    "TILE1": (1, False, [(3100, 2048, 128), (3100, 2044, 384)]),
+    "TILE2_LEAN": (2, True, [(4000, 2048, 384), (4096, 2048, 128)]),
+    "TILE2_GEN": (2, False, [(4000, 2040, 128)]),
+}
+FORCED_SHAPES = [(300, 256, 384), (300, 264, 384)]  # tiles 0 and 3 (AVF_TUNING=1 AVF_NT_TILE=0|3), one child process each
+UNIT_BIAS, UNIT_AUX = 64.0, 30.0
+
+
+def _e4m3(x):
+    """small integers -> e4m3 bytes (exact)"""
+    q = x.float().to(torch.float8_e4m3fn)
+    assert torch.equal(q.float(), x.float())
+    return q.view(torch.uint8)
+
+
+def _small_ints(rows, cols, g):
+    return torch.randint(-2, 3, (rows, cols), generator=g)
+
+
+def _block_wide(rows, K, g, sparse):
+    """one operand of the one-block-wide families -> (q, s)"""
+    kb = K // 32
+    v = _small_ints(rows, K, g)
+    v[:, ::32] = torch.where(v[:, ::32] == 0, torch.ones((), dtype=v.dtype), v[:, ::32])  # no all-zero block
+    s = torch.randint(87, 168, (rows, kb), generator=g)
+    if sparse:
+        keep = torch.zeros(rows, kb, dtype=torch.bool)
+        keep[torch.arange(rows), torch.randint(0, kb, (rows,), generator=g)] = True
+        v = v * keep.repeat_interleave(32, dim=1)
+        s = s * keep
+    return _e4m3(v), s.to(torch.uint8)
+
+
+def make_images(M, N, K, seed, family, quant=oracle.mx8_quant):
+    """-> dict(aq [M, K], as_ [M, K/32], bq [N, K], bs [N, K/32]) uint8 on the CPU.  quant: the quantiser "quantised" goes
+    through (x fp32 -> (q, s)); the device's on the GPU, its bit-identical emulation here."""
+    assert family in FAMILIES and K % 128 == 0
+    g = torch.Generator().manual_seed(seed)
+    kb = K // 32
+    if family == "dense-int":
+        aq, bq = _e4m3(_small_ints(M, K, g)), _e4m3(_small_ints(N, K, g))
+        as_ = torch.randint(127, 131, (M, kb), generator=g).to(torch.uint8)
+        bs = torch.randint(118, 122, (N, kb), generator=g).to(torch.uint8)
+    elif family in ("sparse-a", "sparse-b"):
+        aq, as_ = _block_wide(M, K, g, family == "sparse-a")
+        bq, bs = _block_wide(N, K, g, family == "sparse-b")
+    elif family == "unit":
+        a = torch.randint(-1, 2, (M, K), generator=g) * (torch.rand(M, K, generator=g) < 0.125)
+        aq, bq = _e4m3(a), _e4m3(torch.randint(-1, 2, (N, K), generator=g))
+        as_ = torch.full((M, kb), 127, dtype=torch.uint8)
+        bs = torch.full((N, kb), 127, dtype=torch.uint8)
+    else:
+        a = torch.randn(M, K, generator=g) * torch.exp2(torch.randint(-3, 4, (M, 1), generator=g).float())
+        b = torch.randn(N, K, generator=g) * 0.05
+        (aq, as_), (bq, bs) = quant(a), quant(b)
+        aq, as_, bq, bs = (t.cpu() for t in (aq, as_, bq, bs))
+    return dict(aq=aq, as_=as_, bq=bq, bs=bs)
+
+
+def products(img):
+    """P and magP in fp64 from the dequantised images: once per (shape, data), shared by every epilogue"""
+    a = oracle.mx8_dequant(img["aq"], img["as_"]).double()
+    b = oracle.mx8_dequant(img["bq"], img["bs"]).double()
+    return a @ b.t(), a.abs() @ b.abs().t()
+
+
+def make_inputs(M, N, K, seed, family, c_dtype, epilogue, images):
+    """the epilogue's operands beside the images: fp32 bias [N] (None for DGELU), res (BIAS_RES) / aux_in (DGELU) [M, N] in
+    c_dtype.  The dict is what gemm_nt_util.reference takes."""
+    g = torch.Generator().manual_seed(seed * 8 + epilogue + 1)
+    inp = dict(M=M, N=N, K=K, family=family, epilogue=epilogue, c_dtype=c_dtype, bias=None, res=None, aux_in=None, **images)
+    # (EPI_NONE takes a bias too; not where P + bias would no longer be exact, nor on "unit")
+    if epilogue != EPI_DGELU and not (epilogue == EPI_NONE and family in ("sparse-a", "sparse-b", "unit")):
+        if family == "unit":
+            inp["bias"] = torch.full((N,), UNIT_BIAS)
+        elif family in EXACT_FAMILIES:  # multiples of 2^-9 in [-3, 3]
+            inp["bias"] = torch.randint(-1536, 1537, (N,), generator=g).float() * 2.0 ** -9
+        else:
+            inp["bias"] = torch.rand(N, generator=g) * 6 - 3
+    if epilogue == EPI_BIAS_RES:
+        if family in EXACT_FAMILIES:  # multiples of 2^-4 in [-8, 8]: exact in bf16
+            inp["res"] = (torch.randint(-128, 129, (M, N), generator=g).float() * 2.0 ** -4).to(c_dtype)
+        else:
+            inp["res"] = (torch.randn(M, N, generator=g) * 3).to(c_dtype)
+    if epilogue == EPI_DGELU:
+        if family == "unit":
+            x = torch.full((M, N), UNIT_AUX)
+        else:
+            x = torch.rand(M, N, generator=g) * 20 - 10
+            flat = x.view(-1)
+            for i, v in enumerate(G.SPECIAL_AUX):
+                flat[i * 7::61 * len(G.SPECIAL_AUX)] = v
+        inp["aux_in"] = x.to(c_dtype)
+    return inp
+
+
+def accumulation_bound(family, magP):
+    return 0.0 if family in EXACT_FAMILIES else ACC_REL * magP
+
+
+def reference(inp, f=None, prod=None):
+    prod = prod if prod is not None else products(inp)
+    return G.reference(inp, f, prod, eP=accumulation_bound(inp["family"], prod[1]))
+
+
+check_outputs = G.check_outputs
+mask_not_vacuous = G.mask_not_vacuous
+make_factors = G.make_factors
+
+
+def check_exact(what, inp, prod, c, aux=None, dropout=False):
+    """the bit-for-bit part of an exact family's check (module docstring); -> the number of outputs compared"""
+    fam, epi, cdt = inp["family"], inp["epilogue"], inp["c_dtype"]
+    assert fam in EXACT_FAMILIES
+    P = prod[0]
+    n = 0
+    if epi == EPI_NONE:
+        want = P if inp["bias"] is None else P + inp["bias"].double()
+    elif epi == EPI_BIAS_RES and fam in ("dense-int", "unit") and not dropout:
+        want = P + inp["bias"].double() + inp["res"].double()
+    elif fam == "unit" and epi == EPI_BIAS_GELU and not dropout:
+        want = P + inp["bias"].double()
+    elif fam == "unit" and epi == EPI_DGELU and not dropout:
+        want = P
+    else:
+        want = None
+    if want is not None:
+        assert torch.equal(want.float().double(), want), what + ": the family's value is not an fp32 value"
+        assert torch.equal(c.cpu(), G.round_to(want, cdt)), what + ": C is not the exact result bit for bit"
+        n += 1
+    if epi == EPI_BIAS_GELU and fam in ("dense-int", "unit"):
+        assert aux is not None and torch.equal(aux.cpu(), G.round_to(P + inp["bias"].double(), cdt)), what + ": aux is not exact"
+        n += 1
+    return n
+
+
+def expected_image(v):
+    """the image the contract states for the epilogue's fp32 values v [M, N]"""
+    return oracle.mx8_quant(v.float())
+
+
+def check_image(what, v, q, s):
+    q_ref, s_ref = expected_image(v)
+    assert torch.equal(s.cpu(), s_ref), what + ": scale bytes of the MX-FP8 image of C"
+    assert torch.equal(q.cpu(), q_ref), what + ": element bytes of the MX-FP8 image of C"
+
+
+def image_contracts_differ(v):
+    """does the image of the fp32 values v differ from the image of their bf16 rounding?"""
+    q32, s32 = expected_image(v)
+    q16, s16 = expected_image(v.float().bfloat16().float())
+    return not (torch.equal(q32, q16) and torch.equal(s32, s16))
+
+
+# ------------------------------------------------------------------------------------------------
+# Mutants.  name -> (side, epilogue it applies to or None for all, needs dropout, needs column sums)
+# side "operand": the product itself is wrong (applies to every family); side "epilogue": applies to the families the
+# epilogue options run on ("dense-int").  tile = (BM, BN) of the block tile the mutant is placed in.
+MUTANTS = {
+    "a_scale_blocks_swapped": ("operand", None, False, False),   # A scale bytes of two blocks of one K-step exchanged, rows 16 .. 31
+    "b_scale_blocks_swapped": ("operand", None, False, False),   # the same for B (columns 16 .. 31 of C)
+    "scale_dword_stale": ("operand", None, False, False),        # A's scale dword of step t - 1 used at step t, one row tile
+    "b_scale_from_a_part": ("operand", None, False, False),      # B's scale rows 64 .. of one block tile read from the A part
+    "ragged_rows_last_scale": ("operand", None, False, False),   # rows of the ragged last tile take row M - 1's scales
+    "k_tail_dropped": ("operand", None, False, False),           # the last K-step dropped
+    "a_k_halves_swapped": ("operand", None, False, False),       # the two 64-byte k-halves exchanged in A only, rows 16 .. 31
+    "colsum_partial_lost": ("epilogue", None, False, True),      # one partial row of a wave row left out of the column sums
+    "colsum_dup_row": ("epilogue", None, False, True),           # column sums that count the clamped row M - 1 twice
+    "colsum_unmasked": ("epilogue", None, True, True),           # column sums of unmasked values
+    "mask_index_ldc": ("epilogue", None, True, False),           # the mask indexed m * ldc + n instead of m * N + n
+}
+# ... and the image mutant: simulate(image="bf16") quantises the rounded bf16 value where the contract says the fp32 one
+# (image="fp32"); a check that stated the bf16 contract would in turn refuse the fp32-sourced image (the reverse)
+
+
+def _mutated_product(inp, mutant, tile):
+    """P of the mutated operands, spliced into the true P where the mutant sits"""
+    M, N, K = inp["M"], inp["N"], inp["K"]
+    BM, BN = tile
+    aq, as_, bq, bs = (inp[k].clone() for k in ("aq", "as_", "bq", "bs"))
+    P, _ = products(inp)
+    rows, cols = slice(0, M), slice(0, N)
+    nt = K // 128
+
+    def pair(s, r):  # the non-zero block of row r (the sparse families: the one there is) and its neighbour in the K-step
+        j = int(torch.nonzero(s[r])[0]) if bool((s[r] != 0).any()) else 0
+        return j, j ^ 1
+
+    if mutant == "a_scale_blocks_swapped":
+        r0 = 16 if M >= 32 else 0
+        j, k = pair(as_, r0)
+        as_[r0:r0 + 16, [j, k]] = as_[r0:r0 + 16, [k, j]]
+        rows = slice(r0, r0 + 16)
+    elif mutant == "b_scale_blocks_swapped":
+        r0 = 16 if N >= 32 else 0
+        j, k = pair(bs, r0)
+        bs[r0:r0 + 16, [j, k]] = bs[r0:r0 + 16, [k, j]]
+        cols = slice(r0, r0 + 16)
+    elif mutant == "scale_dword_stale":
+        assert nt >= 2
+        r0 = BM if M > BM else 0
+        t = nt - 1
+        as_[r0:r0 + BM, 4 * t:4 * t + 4] = as_[r0:r0 + BM, 4 * t - 4:4 * t]
+        rows = slice(r0, min(r0 + BM, M))
+    elif mutant == "b_scale_from_a_part":
+        assert N >= BN
+        m0 = BM if M > BM else 0
+        idx = torch.arange(m0, m0 + BM).clamp_max(M - 1)
+        combined = torch.cat([as_[idx], bs[:BN]])  # the scale block of tile (m0, 0): [A rows | B rows]
+        bs[64:BN] = combined[64:BN]
+        rows, cols = slice(m0, min(m0 + BM, M)), slice(64, BN)
+    elif mutant == "ragged_rows_last_scale":
+        r0 = (M - 1) // BM * BM
+        assert M % BM != 0 and M - r0 >= 2
+        as_[r0:M] = as_[M - 1]
+        rows = slice(r0, M)
+    elif mutant == "k_tail_dropped":
+        aq[:, K - 128:] = 0
+    elif mutant == "a_k_halves_swapped":
+        r0 = 16 if M >= 32 else 0
+        aq[r0:r0 + 16] = aq[r0:r0 + 16].view(16, nt, 2, 64).flip(2).reshape(16, K)
+        rows = slice(r0, r0 + 16)
+    else:
+        return P
+    Pm, _ = products(dict(aq=aq, as_=as_, bq=bq, bs=bs))
+    P = P.clone()
+    P[rows, cols] = Pm[rows, cols]
+    return P
+
+
+def simulate(inp, f=None, f_ldc=None, mutant=None, tile=(96, 128), image=None):
+    """-> (C, aux or None, column sums, image (q, s) or None) as the (mutated) kernel would return them, in inp's C type.
+    image: None, "fp32" (the contract) or "bf16" (the image of the value rounded to bf16)"""
+    M, cdt = inp["M"], inp["c_dtype"]
+    _, magP = products(inp)
+    P = _mutated_product(inp, mutant, tile)
+    fm = f_ldc if mutant == "mask_index_ldc" else f
+    eP = accumulation_bound(inp["family"], magP)
+    ref = G.reference(inp, fm, (P, magP), eP=eP)
+    C, aux = ref["C"].clone(), (None if ref["aux"] is None else ref["aux"].clone())
+    cs_src = C
+    if mutant == "colsum_unmasked":
+        cs_src = G.reference(inp, None, (P, magP), eP=eP)["C"]
+    cs = cs_src.sum(0)
+    if mutant == "colsum_dup_row":
+        cs = cs + cs_src[M - 1]
+    if mutant == "colsum_partial_lost":
+        cs = cs - cs_src[48:96].sum(0)
+    c_out = G.round_to(C, cdt)
+    img = None
+    if image is not None:
+        v = C.float()[:, :inp["N"] // 32 * 32]  # the contract: the fp32 value of the epilogue (whole 32-blocks of a row)
+        img = expected_image(v if image == "fp32" else v.bfloat16().float())
+    return c_out, (None if aux is None else G.round_to(aux, cdt)), cs.float(), img

@@ -99,16 +99,18 @@ def products(inp):
     return a @ w.t(), a.abs() @ w.abs().t()
 
 
-def reference(inp, f=None, prod=None, bias=None, res=None, aux_in=None):
+def reference(inp, f=None, prod=None, bias=None, res=None, aux_in=None, eP=None):
     """fp64 reference and per-element fp32 bounds.  f: dropout factors [M, N] or None.  bias / res / aux_in override
-    the ones of inp (one (shape, data) serves every epilogue).  -> dict(C, bC, aux, baux, cs, bcs, premask)."""
+    the ones of inp (one (shape, data) serves every epilogue).  eP: the accumulation bound (a number or [M, N]) in place of
+    2 K U magP, for a kernel family with another accumulator (tests/gemm_mx8_util.py).
+    -> dict(C, bC, aux, baux, cs, bcs, premask)."""
     epi, M, K = inp["epilogue"], inp["M"], inp["K"]
     P, magP = prod if prod is not None else products(inp)
     bias = inp["bias"] if bias is None else bias
     res = inp["res"] if res is None else res
     aux_in = inp["aux_in"] if aux_in is None else aux_in
     f = torch.ones_like(P) if f is None else f.double()
-    eP = 2.0 * K * U * magP
+    eP = 2.0 * K * U * magP if eP is None else torch.zeros_like(P) + eP
     b = torch.zeros(P.shape[1], dtype=torch.float64) if bias is None else bias.double()
     u = P + b
     eu = eP + U * (u.abs() + eP)
