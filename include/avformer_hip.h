@@ -86,6 +86,10 @@ typedef struct avf_layer_cfg {
                           query gives dropped keys zero weight; no gradient flows through a filled score.  bf16 layers with
                           dim_head 64 and <= 512 tokens apply it inside the MFMA attention kernels (head-resident forward, merged
                           backward); every other case runs the attention core on the fp32-arithmetic kernels (correct, not tuned). */
+  int32_t f32_arith;   /* AVF_F32: the arithmetic of every GEMM and of the attention core of THIS call, 1 = bf16x3, 0 = the f32-input
+                          MFMA (the two modes of avf_set_f32_arith, below).  A layer call does not look at the process-wide default:
+                          a caller hands a backward the value its forward ran under, and lse2, o and the grouped weight-gradient
+                          decision then belong to the kernels that read them.  Must be 0 or 1 (AVF_BF16 ignores which). */
 } avf_layer_cfg;
 
 /* fp32 master parameters of one layer, in state_dict order:
@@ -234,7 +238,7 @@ int avf_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int32_t* out);
  * avf_gemm(AVF_F32, transA, transB, ...) runs it - fp32 operands, C, residual and aux; workspace optional (without it the call
  * runs unsplit) - plus the dropout site only a layer call could ask of it so far: (seed_lo, seed_hi, layer_index, site, p) as
  * avf_gemm_nt_ex takes them, element index m * N + n, p == 0 is no dropout, not on AVF_EPI_NONE.
- * avf_gemm_f32_plan: what that call decides under the arithmetic selected now (avf_set_f32_arith), by the function the launcher
+ * avf_gemm_f32_plan: what that call decides under the default arithmetic it would read (avf_set_f32_arith), by the function the launcher
  * itself acts on (host code only).  Pointers are replaced by their presence and alignment: bit i of `misaligned` set = that
  * operand is 4 bytes past a 16-byte boundary (bit 0 A, 1 B, 2 C, 3 bias, 4 residual, 5 aux, 6 workspace).
  * out[0] = the kernel: 0 = gemm_f32x3_kernel (bf16x3), 1 = gemm_f32_kernel on 32 x 32 tiles (T = 1), 2 = on 64 x 64 tiles
@@ -250,8 +254,8 @@ int avf_gemm_f32_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, i
 /* The weight gradients of one parity-mode layer as ONE launch in the bf16x3 arithmetic: 2 .. 4 C_i[M_i,N_i] (fp32, dense) =
  * A_i[K,M_i]^T B_i[K,N_i] (fp32, token-major, rows lda[i] / ldb[i] apart; null: dense) sharing K >= 512, M_i >= 96, N_i >= 96,
  * N_i % 4 == 0, every pointer 16-byte aligned, split over K into slabs in `workspace` (..._workspace_bytes) and folded by a
- * second launch.  avf_gemm_f32_tn_group_plan: out[0] = 1 when the launch takes the group under the arithmetic selected now
- * (else the rest is 0 and avf_gemm_f32_tn_group refuses), out[1] = 128 x 128 tiles of the group, out[2] = S, out[3] =
+ * second launch.  avf_gemm_f32_tn_group_plan: out[0] = 1 when the launch takes the group under the default arithmetic it would
+ * read, which must be 1 (else the rest is 0 and avf_gemm_f32_tn_group refuses), out[1] = 128 x 128 tiles of the group, out[2] = S, out[3] =
  * reduction rows per split (a multiple of 32). */
 size_t avf_gemm_f32_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N);
 int avf_gemm_f32_tn_group_plan(int count, int64_t K, const int64_t* M, const int64_t* N, int32_t* out);
@@ -351,7 +355,7 @@ int avf_attn_bwd_qs(const void* qkv, const void* o, const void* d_o, const float
 #define AVF_ATTN_MERGED 8
 int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int masked, int* fwd, int* bwd);
 /* Which kernel family the fp32-arithmetic attention (avf_attn_fwd / avf_attn_bwd on AVF_F32, and the masked / bf16-storage
- * calls that share its dispatch) takes under the arithmetic avf_get_f32_arith() reports now - host code only, read-only,
+ * calls that share its dispatch) takes under the default arithmetic those calls read (avf_get_f32_arith) - host code only, read-only,
  * answered by the predicates the dispatch itself switches on:
  *   AVF_ATTN_PARITY_VEC     the one-lane-per-query kernels (a mask, bf16 storage, pre-scaled q, another dim_head, or a tensor
  *                           that does not start on a 16-byte boundary)
@@ -953,14 +957,18 @@ int avf_stem_out_hw(int H, int W, int pool_mode, int* Hc, int* Wc, int* Hp, int*
 int avf_dropout_factors(uint32_t seed_lo, uint32_t seed_hi, int layer_index, int site, float p, int64_t rows, int cols,
                         float* out, void* stream);
 
-/* ---- arithmetic of the AVF_F32 (parity) mode, process-wide (round 6) --------------------------------------------
+/* ---- arithmetic of the AVF_F32 (parity) mode (round 6) ------------------------------------------------------------
  * The AVF_F32 GEMMs and the attention core (the fp32 aten::mm / bmm / softmax under models/heads.py:191-196, 212-238) run
  *   mode 1 ("bf16x3", default): every fp32 operand split as x = hi + lo (two bf16), a b ~ hi hi + hi lo + lo hi on
  *           v_mfma_f32_16x16x32_bf16 with fp32 accumulation: <= 3 * 2^-16 = 4.6e-5 relative error per product in the worst case,
  *           4e-6 typical (measured relative Frobenius error of a GEMM), 3 MFMAs per product;
  *   mode 0 ("f32"): the f32-input MFMA v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain, 1/16 of the bf16 rate).
  * Both hold north_star's logits rtol 1e-3; shapes the bf16x3 kernels do not take (fewer than 96 rows or columns, ragged K on the
- * contiguous axis, token masks, bf16 storage) run the mode-0 kernels in either mode.  Returns the previous mode. */
+ * contiguous axis, token masks, bf16 storage) run the mode-0 kernels in either mode.
+ * The arithmetic travels with the call.  avf_layer_cfg carries its own (f32_arith).  The operator-level entry points have no
+ * argument for it (avf_gemm, avf_gemm_f32_ex, avf_gemm_f32_plan, avf_gemm_f32_tn_group*, avf_attn_fwd, avf_attn_bwd,
+ * avf_attn_*_masked, avf_attn_parity_plan): each reads the process-wide DEFAULT set here, once, when it is called.
+ * avf_set_f32_arith returns the previous default. */
 int avf_set_f32_arith(int mode);
 int avf_get_f32_arith(void);
 

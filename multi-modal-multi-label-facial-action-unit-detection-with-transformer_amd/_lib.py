@@ -30,7 +30,8 @@ class LayerCfg(C.Structure):
                 ("dim_head", C.c_int32), ("mlp_dim", C.c_int32), ("dtype", C.c_int32), ("project_out", C.c_int32),
                 ("ln_eps", C.c_float), ("dropout_p", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
                 ("layer_index", C.c_int32), ("seed_dev", C.c_void_p), ("grad_stream_bf16", C.c_int32), ("mx8_fwd", C.c_int32),
-                ("resid_bf16", C.c_int32), ("mx8_bwd", C.c_int32), ("dx_out_mx8", C.c_int32), ("key_mask", C.c_void_p)]
+                ("resid_bf16", C.c_int32), ("mx8_bwd", C.c_int32), ("dx_out_mx8", C.c_int32), ("key_mask", C.c_void_p),
+                ("f32_arith", C.c_int32)]
 
 
 PARAM_FIELDS = ("ln1_w", "ln1_b", "w_qkv", "w_out", "b_out", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")
@@ -318,9 +319,12 @@ F32_ARITH = {"f32": 0, "bf16x3": 1}
 
 
 def set_f32_arithmetic(mode: str) -> str:
-    """Arithmetic of compute_dtype="f32" GEMMs and attention, process-wide: "bf16x3" (default: fp32 operands split in
+    """Arithmetic of compute_dtype="f32" GEMMs and attention: "bf16x3" (default: fp32 operands split in
     three bf16 products on the bf16 matrix pipe: <= 3 * 2^-16 = 4.6e-5 relative error per product in the worst case, 4e-6 typical) or "f32" (the f32-input MFMA).
-    Returns the previous mode's name."""
+    This is the default of calls that carry no arithmetic of their own: an operator-level call reads it when it is made, a
+    Transformer once per forward (its backward runs what that forward ran).  Returns the previous mode's name."""
+    if mode not in F32_ARITH:
+        raise ValueError(f"set_f32_arithmetic: unknown mode {mode!r}; the accepted modes are {sorted(F32_ARITH)}")
     prev = load().avf_set_f32_arith(F32_ARITH[mode])
     return "bf16x3" if prev else "f32"
 

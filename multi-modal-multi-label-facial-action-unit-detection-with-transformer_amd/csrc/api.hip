@@ -263,6 +263,7 @@ extern "C" int avf_gemm(int dtype, int transA, int transB, int64_t M, int64_t N,
   a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
   a.c_dtype = c_dtype; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
   a.aux = aux; a.ldaux = ldaux; a.workspace = workspace;
+  a.f32_arith = get_f32_arith();
   return gemm(a, (hipStream_t)stream);
 }
 
@@ -390,6 +391,7 @@ extern "C" int avf_gemm_f32_ex(int transA, int transB, int64_t M, int64_t N, int
   a.c_dtype = AVF_F32; a.epilogue = epilogue; a.bias = bias; a.residual = residual; a.ldres = ldres;
   a.aux = aux; a.ldaux = ldaux; a.workspace = workspace;
   if (p > 0.f) a.drop = make_drop(p, ((uint64_t)seed_hi << 32) | seed_lo, layer_index, site);
+  a.f32_arith = get_f32_arith();
   return gemm_f32(a, (hipStream_t)stream);
 }
 extern "C" int avf_gemm_f32_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
@@ -405,6 +407,7 @@ extern "C" int avf_gemm_f32_plan(int transA, int transB, int64_t M, int64_t N, i
   if (epilogue == AVF_EPI_BIAS_RES) a.residual = ptr(4);
   if (epilogue == AVF_EPI_BIAS_GELU || epilogue == AVF_EPI_DGELU) a.aux = ptr(5);
   if (has_workspace) a.workspace = ptr(6);
+  a.f32_arith = get_f32_arith();
   F32Plan pl;
   AVF_TRY(gemm_f32_plan(a, &pl));
   out[0] = pl.kernel; out[1] = pl.akf; out[2] = pl.bkf; out[3] = pl.S; out[4] = pl.kchunk; out[5] = pl.vec;
@@ -418,6 +421,7 @@ static int fill_f32_tn_group(TnGroupArgs* g, int count, int64_t K, const void* c
     if (ldb) g->ldb[i] = ldb[i];
     AVF_REQUIRE(g->lda[i] >= M[i] && g->ldb[i] >= N[i], "gemm_f32_tn_group: lda / ldb below the row length of problem %d", i);
   }
+  g->f32_arith = get_f32_arith();
   return 0;
 }
 extern "C" size_t avf_gemm_f32_tn_group_workspace_bytes(int count, int64_t K, const int64_t* M, const int64_t* N) {
@@ -461,14 +465,14 @@ extern "C" int avf_layernorm_bwd_mx8(const void* dy_bf16, const float* x, const 
 extern "C" int avf_attn_fwd_masked(int dtype, const void* qkv, void* o, float* lse2, const void* keep, int batch, int tokens,
                                    int heads, int dim_head, void* stream) {
   AVF_REQUIRE(qkv && o && lse2 && keep, "attn_fwd_masked: null pointer");
-  return attn_fwd_vec(dtype, qkv, o, lse2, batch, tokens, heads, dim_head, (hipStream_t)stream, keep, false);
+  return attn_fwd_vec(dtype, qkv, o, lse2, batch, tokens, heads, dim_head, (hipStream_t)stream, keep, false, get_f32_arith());
 }
 extern "C" int avf_attn_bwd_masked(int dtype, const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv,
                                    void* workspace, const void* keep, int batch, int tokens, int heads, int dim_head,
                                    void* stream) {
   AVF_REQUIRE(qkv && o && d_o && lse2 && dqkv && workspace && keep, "attn_bwd_masked: null pointer");
   return attn_bwd_vec(dtype, qkv, o, d_o, lse2, dqkv, (float*)workspace, batch, tokens, heads, dim_head, (hipStream_t)stream,
-                      keep, false);
+                      keep, false, get_f32_arith());
 }
 extern "C" int avf_attn_fwd_mx8(const void* qkv, void* o, float* lse2, void* o_q, void* o_scales, int batch, int tokens,
                                 int heads, int dim_head, void* stream) {
@@ -543,7 +547,7 @@ extern "C" int avf_attn_fwd(int dtype, const void* qkv, void* o, float* lse2, in
                             int dim_head, void* stream) {
   AVF_REQUIRE(qkv && o && lse2, "attn_fwd: null pointer");
   if (dtype == AVF_F32)
-    return attn_fwd_f32((const float*)qkv, (float*)o, lse2, batch, tokens, heads, dim_head, (hipStream_t)stream);
+    return attn_fwd_f32((const float*)qkv, (float*)o, lse2, batch, tokens, heads, dim_head, (hipStream_t)stream, get_f32_arith());
   if (dtype == AVF_BF16)
     return attn_fwd_bf16((const bf16*)qkv, (bf16*)o, lse2, batch, tokens, heads, dim_head, (hipStream_t)stream);
   AVF_REQUIRE(false, "attn_fwd: bad dtype %d", dtype);
@@ -557,7 +561,7 @@ extern "C" int avf_attn_bwd(int dtype, const void* qkv, const void* o, const voi
   AVF_REQUIRE(qkv && o && d_o && lse2 && dqkv && workspace, "attn_bwd: null pointer");
   if (dtype == AVF_F32)
     return attn_bwd_f32((const float*)qkv, (const float*)o, (const float*)d_o, lse2, (float*)dqkv, (float*)workspace,
-                        batch, tokens, heads, dim_head, (hipStream_t)stream);
+                        batch, tokens, heads, dim_head, (hipStream_t)stream, get_f32_arith());
   if (dtype == AVF_BF16)
     return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, (float*)workspace,
                          batch, tokens, heads, dim_head, (hipStream_t)stream);
@@ -585,10 +589,10 @@ extern "C" int avf_attn_plan(int tokens, int dim_head, int q_prescaled, int mask
   return attn_bf16_plan(tokens, dim_head, q_prescaled != 0, masked != 0, fwd, bwd);
 }
 
-// which family avf_attn_fwd / avf_attn_bwd take in the parity mode, under the arithmetic set now: host code only, answered by
-// the predicates attn_fwd_vec / attn_bwd_vec switch on
+// which family avf_attn_fwd / avf_attn_bwd take in the parity mode, under the default arithmetic those calls read
+// (avf_set_f32_arith): host code only, answered by the predicates attn_fwd_vec / attn_bwd_vec switch on
 extern "C" int avf_attn_parity_plan(int dtype, int dim_head, int masked, int q_prescaled, int aligned16, int heads) {
-  return attn_parity_plan(dtype, dim_head, masked != 0, q_prescaled != 0, aligned16 != 0, heads);
+  return attn_parity_plan(dtype, dim_head, masked != 0, q_prescaled != 0, aligned16 != 0, heads, get_f32_arith());
 }
 
 // ... with the token mask: the masked attention core exactly as avf_layer_fwd / avf_layer_bwd run it in a bf16, non-fp8 stack
@@ -671,6 +675,8 @@ extern "C" int avf_crash_line_disarm(void) {
   return 0;
 }
 
+// the parity arithmetic of the operator-level entry points above, which take none as an argument: each reads it once per call.  A
+// layer call carries its own (avf_layer_cfg::f32_arith) and does not look here.
 extern "C" int avf_set_f32_arith(int mode) {
   const int prev = get_f32_arith();
   set_f32_arith(mode);

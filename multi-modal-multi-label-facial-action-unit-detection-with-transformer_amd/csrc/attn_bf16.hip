@@ -1120,7 +1120,7 @@ int attn_fwd_masked_bf16(const void* qkv, void* o, float* lse2, const void* keep
   AVF_REQUIRE(keep, "attn_fwd_masked_bf16: no mask");
   if (attn_masked_bf16_ok(N, dh, q_prescaled))
     return attn_fwd_bf16((const bf16*)qkv, (bf16*)o, lse2, B, N, H, dh, s, true, nullptr, nullptr, keep);
-  return attn_fwd_vec(AVF_BF16, qkv, o, lse2, B, N, H, dh, s, keep, q_prescaled);
+  return attn_fwd_vec(AVF_BF16, qkv, o, lse2, B, N, H, dh, s, keep, q_prescaled, /*arith: fp32 storage only*/ 0);
 }
 
 bool attn_bwd_emits_mx8(int N, int dh, bool q_prescaled) { return attn_bwd_merged_ok(N, dh, q_prescaled); }
@@ -1160,7 +1160,7 @@ int attn_bwd_masked_bf16(const void* qkv, const void* o, const void* d_o, const 
   AVF_REQUIRE(keep, "attn_bwd_masked_bf16: no mask");
   if (attn_masked_bf16_ok(N, dh, q_prescaled))  // (as the forward chose)
     return attn_bwd_bf16((const bf16*)qkv, (const bf16*)o, (const bf16*)d_o, lse2, (bf16*)dqkv, delta, B, N, H, dh, s, true, keep);
-  return attn_bwd_vec(AVF_BF16, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, keep, q_prescaled);
+  return attn_bwd_vec(AVF_BF16, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, keep, q_prescaled, /*arith: fp32 storage only*/ 0);
 }
 
 }  // namespace avf

@@ -325,24 +325,24 @@ static int with_vec_variant(int dh, int dtype, bool masked, const char* who, F&&
 // which family attn_fwd_vec / attn_bwd_vec take, from the predicates they switch on and in their order.  aligned16 = true speaks
 // for every tensor of the call, false for a misaligned qkv; the backward asks dqkv (and, for bf16x3, o) besides the predicate's
 // pair, so a call with only one of those off the grid is not what this answers (avformer_hip.h says so)
-int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H) {
-  if (attn_f32x3_takes(dtype, dh, masked, H, aligned16, q_prescaled)) return 2;
+int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H, int arith) {
+  if (attn_f32x3_takes(dtype, dh, masked, H, aligned16, q_prescaled, arith)) return 2;
   if (attn_f32_mfma_takes(dtype, dh, masked, H, aligned16, q_prescaled)) return 1;
   return 0;
 }
 
-int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s) {
-  return attn_fwd_vec(AVF_F32, qkv, o, lse2, B, N, H, dh, s, nullptr, false);
+int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, int arith) {
+  return attn_fwd_vec(AVF_F32, qkv, o, lse2, B, N, H, dh, s, nullptr, false, arith);
 }
 
 // the fp32-arithmetic attention on fp32 or bf16 storage, with the optional token mask (keep [B, N] bytes, 1 = kept)
 int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N, int H, int dh, hipStream_t s,
-                 const void* keep, bool q_prescaled) {
+                 const void* keep, bool q_prescaled, int arith) {
   AVF_REQUIRE(B > 0 && N > 0 && H > 0, "attn_fwd_f32: bad shape");
   AVF_REQUIRE((int64_t)B * H < 65536, "attn_fwd_f32: batch*heads too large for grid");
   AVF_REQUIRE(dtype == AVF_F32 || dtype == AVF_BF16, "attn_fwd_f32: bad dtype %d", dtype);
   TimingScope ts(KC_ATTN_FWD, 4.0 * B * H * (double)N * N * dh, 4.0 * 4.0 * B * N * H * dh, s);
-  if (attn_f32x3_ok(dtype, dh, keep, H, qkv, o, q_prescaled))  // round 6: three bf16 products per fp32 product (attn_f32x3.hip)
+  if (attn_f32x3_ok(dtype, dh, keep, H, qkv, o, q_prescaled, arith))  // round 6: three bf16 products per fp32 product (attn_f32x3.hip)
     return attn_fwd_f32x3((const float*)qkv, (float*)o, lse2, B, N, H, s);
   if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, o, q_prescaled))  // fp32 storage, no mask, raw q, dim_head 32 / 64 / 128: the fp32 matrix pipe
     return attn_fwd_f32_mfma((const float*)qkv, (float*)o, lse2, B, N, H, dh, s);
@@ -358,17 +358,17 @@ int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N,
 }
 
 int attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, float* dqkv, float* delta,
-                 int B, int N, int H, int dh, hipStream_t s) {
-  return attn_bwd_vec(AVF_F32, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, nullptr, false);
+                 int B, int N, int H, int dh, hipStream_t s, int arith) {
+  return attn_bwd_vec(AVF_F32, qkv, o, d_o, lse2, dqkv, delta, B, N, H, dh, s, nullptr, false, arith);
 }
 
 int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta,
-                 int B, int N, int H, int dh, hipStream_t s, const void* keep, bool q_prescaled) {
+                 int B, int N, int H, int dh, hipStream_t s, const void* keep, bool q_prescaled, int arith) {
   AVF_REQUIRE(B > 0 && N > 0 && H > 0, "attn_bwd_f32: bad shape");
   AVF_REQUIRE((int64_t)B * H < 65536, "attn_bwd_f32: batch*heads too large for grid");
   AVF_REQUIRE(dtype == AVF_F32 || dtype == AVF_BF16, "attn_bwd_f32: bad dtype %d", dtype);
   TimingScope ts(KC_ATTN_BWD, 10.0 * B * H * (double)N * N * dh, 4.0 * 8.0 * B * N * H * dh, s);
-  if (attn_f32x3_ok(dtype, dh, keep, H, qkv, d_o, q_prescaled) && ((uintptr_t)dqkv & 15) == 0 && ((uintptr_t)o & 15) == 0)
+  if (attn_f32x3_ok(dtype, dh, keep, H, qkv, d_o, q_prescaled, arith) && ((uintptr_t)dqkv & 15) == 0 && ((uintptr_t)o & 15) == 0)
     return attn_bwd_f32x3((const float*)qkv, (const float*)o, (const float*)d_o, lse2, delta, (float*)dqkv, B, N, H, s);
   AVF_TRY(attn_delta(dtype, o, d_o, delta, B, N, H, dh, s));
   if (attn_f32_mfma_ok(dtype, dh, keep, H, qkv, d_o, q_prescaled) && ((uintptr_t)dqkv & 15) == 0)

@@ -140,12 +140,12 @@ struct ParityBf16x3 {
 
 }  // namespace
 
-// shapes these kernels take: the bf16x3 arithmetic selected, fp32 storage, no token mask, dim_head 64, q not pre-scaled, 16-byte rows
-bool attn_f32x3_takes(int dtype, int dh, bool masked, int /*H*/, bool aligned16, bool q_prescaled) {
-  return get_f32_arith() == 1 && dtype == AVF_F32 && !masked && !q_prescaled && dh == ParityBf16x3::DH && aligned16;
+// calls these kernels take: the bf16x3 arithmetic asked for, fp32 storage, no token mask, dim_head 64, q not pre-scaled, 16-byte rows
+bool attn_f32x3_takes(int dtype, int dh, bool masked, int /*H*/, bool aligned16, bool q_prescaled, int arith) {
+  return arith == 1 && dtype == AVF_F32 && !masked && !q_prescaled && dh == ParityBf16x3::DH && aligned16;
 }
-bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled) {
-  return attn_f32x3_takes(dtype, dh, keep != nullptr, H, attn_aligned16(qkv, other), q_prescaled);
+bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled, int arith) {
+  return attn_f32x3_takes(dtype, dh, keep != nullptr, H, attn_aligned16(qkv, other), q_prescaled, arith);
 }
 
 int attn_fwd_f32x3(const float* qkv, float* o, float* lse2, int B, int N, int H, hipStream_t s) {

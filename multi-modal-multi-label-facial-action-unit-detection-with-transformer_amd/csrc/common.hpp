@@ -521,6 +521,7 @@ struct GemmArgs {
   void* C = nullptr;
   int64_t lda = 0, ldb = 0, ldc = 0;
   int c_dtype = AVF_F32;
+  int f32_arith = -1;  // AVF_F32 only, and there the one field without a usable default: 1 = bf16x3, 0 = the f32-input MFMA
   int epilogue = AVF_EPI_NONE;
   const float* bias = nullptr;
   const void* residual = nullptr;  // BIAS_RES: fp32 when C is fp32; bf16 when C is bf16 (bf16 residual stream)
@@ -573,10 +574,13 @@ int gemm(const GemmArgs& a, hipStream_t s);
 int gemm_f32(const GemmArgs& a, hipStream_t s);
 size_t gemm_f32_ws(int64_t M, int64_t N, int64_t K);  // split-K slabs of skinny shapes (0: no split)
 // arithmetic of the AVF_F32 mode (round 6): 1 = operands split in three bf16 products on the bf16 matrix pipe ("bf16x3", default),
-// 0 = the f32-input MFMA (v_mfma_f32_16x16x4_f32).  Process-wide; avf_set_f32_arith / avf_get_f32_arith.
+// 0 = the f32-input MFMA (v_mfma_f32_16x16x4_f32).  Every call carries its own: GemmArgs::f32_arith, TnGroupArgs::f32_arith, the
+// `arith` argument of the parity attention, avf_layer_cfg::f32_arith.  The process-wide value behind avf_set_f32_arith /
+// avf_get_f32_arith is only the default of the operator-level C entry points (api.hip), which have no argument for it: each reads
+// it once with get_f32_arith() and passes it down; nothing below api.hip looks at it.
 void set_f32_arith(int mode);
 int get_f32_arith();
-// Which kernel gemm_f32 runs and how, under the arithmetic selected now: the launcher acts on exactly this (f32_plan in
+// Which kernel gemm_f32 runs and how, under the call's arithmetic: the launcher acts on exactly this (f32_plan in
 // gemm_f32.hip), gemm_f32_plan answers a test's or a profile tool's question from the same function.
 enum { F32_KERNEL_X3 = 0, F32_KERNEL_MFMA_T1 = 1, F32_KERNEL_MFMA_T2 = 2 };
 struct F32Plan {
@@ -626,6 +630,7 @@ struct TnGroupArgs {
   float* C[kTnGroupMax];
   int64_t M[kTnGroupMax], N[kTnGroupMax], lda[kTnGroupMax], ldb[kTnGroupMax];
   void* workspace;
+  int f32_arith;  // gemm_f32x3_tn_group* only: the group launches under 1 (bf16x3) alone
 };
 bool gemm_bf16_tn_group_ok(const TnGroupArgs& a);
 size_t gemm_bf16_tn_group_ws(const TnGroupArgs& a);
@@ -653,16 +658,17 @@ int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s);
 // what that launch decides (the setup it acts on): -> gemm_f32x3_tn_group_ok; tiles of the group, split count, rows per split
 int gemm_f32x3_tn_group_plan(const TnGroupArgs& a, int* tiles, int* S, int* kchunk);
 
-int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s);
+int attn_fwd_f32(const float* qkv, float* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, int arith);
 // fp32-arithmetic attention on fp32 / bf16 storage with the optional token mask keep [B, N] (bytes, 1 = kept; heads.py:225-232)
 // The two predicates of the parity-mode dispatch (attn_fwd_vec / attn_bwd_vec), each in two forms sharing one body: *_ok looks at
 // the call's pointers (keep for null-ness; qkv and the other tensor a kernel touches with 16-byte accesses for alignment), *_takes
-// is told the same facts - what avf_attn_parity_plan answers from.
+// is told the same facts - what avf_attn_parity_plan answers from.  arith: the call's parity arithmetic (1 = bf16x3, 0 = the
+// f32-input MFMA; bf16 storage runs on neither matrix-pipe family, whatever it says).
 inline bool attn_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 // 0 = the one-lane-per-query kernels of attn_f32.hip, 1 = attn_f32_mfma.hip, 2 = attn_f32x3.hip: the order of the dispatch.
 // aligned16: every tensor of the call starts on a 16-byte boundary; false stands for a misaligned qkv (refused by both, in both
 // passes) - which of o, d_o, dqkv each pass asks besides is in avformer_hip.h.
-int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H);
+int attn_parity_plan(int dtype, int dh, bool masked, bool q_prescaled, bool aligned16, int H, int arith);
 // parity-mode attention on the fp32 matrix pipe (attn_f32_mfma.hip): fp32 storage, no mask, dim_head 32 / 64 / 128, raw q
 bool attn_f32_mfma_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled);
 bool attn_f32_mfma_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
@@ -670,17 +676,17 @@ int attn_fwd_f32_mfma(const float* qkv, float* o, float* lse2, int B, int N, int
 int attn_bwd_f32_mfma(const float* qkv, const float* d_o, const float* lse2, const float* delta, float* dqkv, int B, int N, int H,
                       int dh, hipStream_t s);
 // parity-mode attention with three bf16 products per fp32 product (attn_f32x3.hip): fp32 storage, no mask, dim_head 64, raw q
-bool attn_f32x3_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled);
-bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled);
+bool attn_f32x3_takes(int dtype, int dh, bool masked, int H, bool aligned16, bool q_prescaled, int arith);
+bool attn_f32x3_ok(int dtype, int dh, const void* keep, int H, const void* qkv, const void* other, bool q_prescaled, int arith);
 int attn_fwd_f32x3(const float* qkv, float* o, float* lse2, int B, int N, int H, hipStream_t s);
 int attn_bwd_f32x3(const float* qkv, const float* o, const float* d_o, const float* lse2, float* delta, float* dqkv, int B, int N,
                    int H, hipStream_t s);  // (computes delta itself: no attn_delta launch in front of it)
 int attn_fwd_vec(int dtype, const void* qkv, void* o, float* lse2, int B, int N, int H, int dh, hipStream_t s, const void* keep,
-                 bool q_prescaled);
+                 bool q_prescaled, int arith);
 int attn_bwd_vec(int dtype, const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* delta,
-                 int B, int N, int H, int dh, hipStream_t s, const void* keep, bool q_prescaled);
+                 int B, int N, int H, int dh, hipStream_t s, const void* keep, bool q_prescaled, int arith);
 int attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, float* dqkv, float* delta,
-                 int B, int N, int H, int dh, hipStream_t s);
+                 int B, int N, int H, int dh, hipStream_t s, int arith);
 // q_prescaled: the q columns of qkv already hold q * log2(e)/sqrt(dh) (the layer path: folded into the bf16 copy of
 // Wqkv's query rows, attn_q_prescale); the operator-level C entry points pass false.
 // single-launch forward of one layer for short sequences (layer_small.hip)

@@ -484,9 +484,6 @@ __global__ __launch_bounds__(256) void gemm_f32x3_group_fold_kernel(F32GroupPara
   *reinterpret_cast<float4*>(g.p[i].C + (int64_t)m * g.p[i].ldc + n) = v;
 }
 
-// which arithmetic AVF_F32 GEMMs and attention run on: 1 = bf16x3 on the bf16 matrix pipe (default), 0 = the f32-input MFMA
-int g_f32_arith = 1;
-
 // shapes the bf16x3 kernel takes: tiles worth filling, one unit stride per operand, 16-byte loads where k is the fast axis
 bool f32x3_ok(const F32GemmParams& p) {
   if (p.M < 96 || p.N < 96 || p.K < 32) return false;  // at least three quarters of a tile each way (smaller: the 32 / 64 tiles above)
@@ -550,13 +547,16 @@ size_t gemm_f32_ws(int64_t M, int64_t N, int64_t K) {
   return sp > 1 ? (size_t)sp * M * N * sizeof(float) : 0;
 }
 
+// the arithmetic of the operator-level C entry points, which have no argument for one (api.hip reads it, once per call; nothing
+// in this file does): 1 = bf16x3 on the bf16 matrix pipe (default), 0 = the f32-input MFMA
+static int g_f32_arith = 1;
 void set_f32_arith(int mode) { g_f32_arith = mode ? 1 : 0; }
 int get_f32_arith() { return g_f32_arith; }
 
 // ---- the grouped weight-gradient launch of the parity mode (bf16x3 arithmetic) ---------------------------------------------------
 namespace {
 int f32x3_group_setup(const TnGroupArgs& a, F32GroupParams* g, bool any_arith = false) {
-  if ((g_f32_arith != 1 && !any_arith) || a.count < 2 || a.count > 4 || a.K < 512 || a.K >= (1LL << 31)) return 0;
+  if ((a.f32_arith != 1 && !any_arith) || a.count < 2 || a.count > 4 || a.K < 512 || a.K >= (1LL << 31)) return 0;
   int tiles = 0;
   int64_t el = 0;
   for (int i = 0; i < a.count; ++i) {
@@ -600,7 +600,7 @@ int gemm_f32x3_tn_group_plan(const TnGroupArgs& a, int* tiles, int* S, int* kchu
   *tiles = g.tile0[g.count]; *S = g.S; *kchunk = g.p[0].kchunk;
   return 1;
 }
-size_t gemm_f32x3_tn_group_ws(const TnGroupArgs& a) {  // (whatever arithmetic is selected NOW: a buffer sized under one serves both)
+size_t gemm_f32x3_tn_group_ws(const TnGroupArgs& a) {  // (whatever a.f32_arith says: a buffer sized under one arithmetic serves both)
   F32GroupParams g;
   if (!f32x3_group_setup(a, &g, true)) return 0;
   return (size_t)g.S * (size_t)g.el0[g.count] * sizeof(float);
@@ -626,6 +626,7 @@ int gemm_f32x3_tn_group(const TnGroupArgs& a, hipStream_t s) {
 // GemmArgs -> the kernels' parameter block (the checks every fp32 GEMM call and plan query must pass)
 static int f32_params(const GemmArgs& a, F32GemmParams* out) {
   AVF_REQUIRE(a.c_dtype == AVF_F32, "gemm_f32: C must be fp32");
+  AVF_REQUIRE(a.f32_arith == 0 || a.f32_arith == 1, "gemm_f32: the call names no arithmetic (GemmArgs::f32_arith = %d)", a.f32_arith);
   AVF_REQUIRE(!a.drop.thresh16 || a.epilogue != AVF_EPI_NONE, "gemm_f32: dropout needs a fused epilogue");
   AVF_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm_f32: bad shape");
   AVF_REQUIRE(a.M < (1LL << 31) && a.N < (1LL << 31) && a.K < (1LL << 31), "gemm_f32: shape too large");
@@ -653,7 +654,7 @@ static F32Plan f32_plan(const F32GemmParams& p, const GemmArgs& a) {
   F32Plan pl;
   pl.akf = p.a_sk == 1; pl.bkf = p.b_sk == 1;
   pl.S = 1; pl.kchunk = 0; pl.vec = 0;
-  if (g_f32_arith == 1 && f32x3_ok(p)) {  // bf16x3 on the bf16 matrix pipe (round 6)
+  if (a.f32_arith == 1 && f32x3_ok(p)) {  // bf16x3 on the bf16 matrix pipe (round 6)
     pl.kernel = F32_KERNEL_X3;
     const int S0 = a.workspace ? f32x3_splits(a.M, a.N, a.K, a.epilogue) : 1;
     if (S0 > 1) {

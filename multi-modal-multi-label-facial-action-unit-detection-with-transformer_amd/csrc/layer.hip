@@ -28,6 +28,7 @@ struct Dims {
   int64_t R;  // rows = batch * tokens
   int D, H, dh, I, M, B, N;
   int dt;     // compute dtype
+  int arith;  // parity mode (dt == AVF_F32): the arithmetic of every GEMM and of the attention of this call, 1 = bf16x3, 0 = f32-input MFMA
   size_t es;  // element size of compute dtype
   float p;    // dropout probability (0 = off)
   uint64_t seed;
@@ -58,6 +59,7 @@ int make_dims(const avf_layer_cfg* c, Dims* d) {
   AVF_REQUIRE(c->batch > 0 && c->tokens > 0 && c->dim > 0 && c->heads > 0 && c->dim_head > 0 && c->mlp_dim > 0,
               "layer: non-positive shape in cfg");
   AVF_REQUIRE(c->dtype == AVF_F32 || c->dtype == AVF_BF16, "layer: bad dtype %d", c->dtype);
+  AVF_REQUIRE(c->f32_arith == 0 || c->f32_arith == 1, "layer: f32_arith=%d is neither 0 (f32-input MFMA) nor 1 (bf16x3)", c->f32_arith);
   AVF_REQUIRE(c->dropout_p >= 0.0f && c->dropout_p < 1.0f, "layer: dropout_p=%g out of range", (double)c->dropout_p);
   AVF_REQUIRE(c->dropout_p == 0.0f || (c->dim % 4 == 0 && c->dim <= 1536 && c->mlp_dim % 4 == 0),
               "layer: dropout needs dim %% 4 == 0, dim <= 1536");
@@ -72,7 +74,7 @@ int make_dims(const avf_layer_cfg* c, Dims* d) {
               "layer: project_out = 0 is the nn.Identity to_out case: it needs heads == 1 and dim_head == dim (heads.py:207)");
   d->B = c->batch; d->N = c->tokens; d->D = c->dim; d->H = c->heads; d->dh = c->dim_head;
   d->I = c->heads * c->dim_head; d->M = c->mlp_dim; d->R = (int64_t)c->batch * c->tokens;
-  d->dt = c->dtype; d->es = c->dtype == AVF_BF16 ? 2 : 4;
+  d->dt = c->dtype; d->es = c->dtype == AVF_BF16 ? 2 : 4; d->arith = c->f32_arith;
   d->p = c->dropout_p; d->seed = ((uint64_t)c->seed_hi << 32) | c->seed_lo; d->layer = c->layer_index;
   d->seed_dev = (const uint64_t*)c->seed_dev;
   d->gs16 = c->grad_stream_bf16 != 0;
@@ -195,7 +197,7 @@ size_t carve_lowp(const Dims& d, void* base, LayerW* out, const avf_layer_params
 // token rows): the shapes here, the operands by dw_problem
 TnGroupArgs dw_group(const Dims& d) {
   TnGroupArgs a{};
-  a.count = kLinears; a.K = d.R;
+  a.count = kLinears; a.K = d.R; a.f32_arith = d.arith;
   for (int i = 0; i < kLinears; ++i) { a.M[i] = a.lda[i] = linear_shape(d, i).out; a.N[i] = a.ldb[i] = linear_shape(d, i).in; }
   return a;
 }
@@ -210,8 +212,8 @@ size_t work_colsum_bytes(const Dims& d) {
 size_t work_dw_bytes(const Dims& d) {
   const bool lo = d.dt == AVF_BF16;
   const TnGroupArgs ga = dw_group(d);
-  // (parity mode: narrow layers split their long token reduction, gemm_f32_ws; the grouped size does not depend on the arithmetic
-  // selected now: the buffer serves either)
+  // (parity mode: narrow layers split their long token reduction, gemm_f32_ws; neither size depends on d.arith: the buffer serves
+  // either arithmetic)
   size_t g = lo ? gemm_bf16_tn_group_ws(ga) : gemm_f32x3_tn_group_ws(ga);
   for (int i = 0; i < ga.count; ++i) g = std::max(g, lo ? gemm_bf16_tn_ws(ga.M[i], ga.N[i], d.R) : gemm_f32_ws(ga.M[i], ga.N[i], d.R));
   return g;
@@ -310,7 +312,7 @@ struct Act { const void *x, *q, *s; };
 // (the MX-FP8 image of the result) - in a GemmArgs of which nothing else is set
 int linear_fwd(const Dims& d, const LinearW& L, const Act& x, void* C, int c_dtype, const GemmArgs& e, hipStream_t s) {
   GemmArgs a = gemm_dense(d.dt, 0, 1, d.R, L.out, L.in, e);
-  a.C = C; a.c_dtype = c_dtype;
+  a.C = C; a.c_dtype = c_dtype; a.f32_arith = d.arith;
   if (d.mx && x.q && L.q) {
     a.A = x.q; a.B = L.q; a.mx_q = a.mx_s = nullptr;
     return gemm_mx8_nt(a, x.s, L.s, s, e.mx_q, e.mx_s);
@@ -326,7 +328,7 @@ int linear_dx(const Dims& d, const LinearW& L, const Act& dy, void* dX, const Ge
   const bool lo = d.dt == AVF_BF16;
   GemmArgs a = gemm_dense(d.dt, 0, lo ? 1 : 0, d.R, L.in, L.out, e);
   a.A = dy.x; a.B = lo ? L.lo_t : (const void*)L.w; a.Bp = L.tp;
-  a.C = dX; a.c_dtype = d.dt;
+  a.C = dX; a.c_dtype = d.dt; a.f32_arith = d.arith;
   if (!(d.mxb && dy.q && L.tq) || (ws_first && gemm_bf16_nt_ws_ok(a))) return gemm(a, s);
   a.A = dy.q; a.B = L.tq; a.Bp = nullptr; a.mx_q = a.mx_s = nullptr;
   return gemm_mx8_nt(a, dy.s, L.ts, s, e.mx_q, e.mx_s);
@@ -335,7 +337,7 @@ int linear_dx(const Dims& d, const LinearW& L, const Act& dy, void* dX, const Ge
 // dW[out, in] = dY[R, out]^T * X[R, in]   (fp32 result)
 int linear_dw(const Dims& d, const LinearW& L, const void* dY, const void* X, float* dW, void* ws, hipStream_t s) {
   GemmArgs a = gemm_dense(d.dt, 1, 0, L.out, L.in, d.R);
-  a.A = dY; a.B = X; a.C = dW; a.c_dtype = AVF_F32; a.workspace = ws;
+  a.A = dY; a.B = X; a.C = dW; a.c_dtype = AVF_F32; a.workspace = ws; a.f32_arith = d.arith;
   return gemm(a, s);
 }
 
@@ -484,9 +486,9 @@ static int fwd_attention(const Dims& d, const Saved& sv, void* oq, void* os, hip
   // token mask (heads.py:225-232): on the MFMA kernels where they carry it (bf16, dim_head 64, up to 512 tokens), else on
   // the fp32-arithmetic ones (attn_fwd_masked_bf16 chooses); the fp8 mode and the fp32 mode go to the fp32-arithmetic ones directly
   if (d.keep && lo && !d.mx) return attn_fwd_masked_bf16(sv.qkv, sv.o, sv.lse2, d.keep, d.B, d.N, d.H, d.dh, s, attn_q_prescale_on());
-  if (d.keep) return attn_fwd_vec(d.dt, sv.qkv, sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.keep, d.mx && attn_q_prescale_on());
+  if (d.keep) return attn_fwd_vec(d.dt, sv.qkv, sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.keep, d.mx && attn_q_prescale_on(), d.arith);
   if (lo) return attn_fwd_bf16((const bf16*)sv.qkv, (bf16*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), oq, os);
-  return attn_fwd_f32((const float*)sv.qkv, (float*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s);
+  return attn_fwd_f32((const float*)sv.qkv, (float*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.arith);
 }
 
 static int layer_fwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, const void* lowp, const LayerFwdIO& io,
@@ -820,13 +822,13 @@ int LayerBwd::attn_half() {
                                  attn_q_prescale_on()));
   else if (d.keep)
     AVF_TRY(attn_bwd_vec(d.dt, sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, d.B, d.N, d.H, d.dh, s, d.keep,
-                         lo && attn_q_prescale_on()));
+                         lo && attn_q_prescale_on(), d.arith));
   else if (lo)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
                           d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), nullptr, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr));
   else
     AVF_TRY(attn_bwd_f32((const float*)sv.qkv, (const float*)sv.o, (const float*)w.d_o, sv.lse2, (float*)w.dqkv,
-                         w.delta, d.B, d.N, d.H, d.dh, s));
+                         w.delta, d.B, d.N, d.H, d.dh, s, d.arith));
   if (grouped32) AVF_TRY(gemm_f32x3_tn_group(grp, s));
   // dh1 = dqkv Wqkv (dq_mx: on MX-FP8 operands, the image of dqkv left the attention backward's epilogue)
   return linear_dx(d, W.lin[kQkv], Act{w.dqkv, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr}, w.dh, GemmArgs{}, s);

@@ -462,7 +462,7 @@ _F32_MISALIGN_BITS = ("a", "b", "out", "bias", "residual", "aux", "workspace")
 def gemm_f32_plan(M: int, N: int, K: int, trans_a: bool = False, trans_b: bool = True, epilogue: int = EPI_NONE,
                   bias: bool = False, workspace: bool = True, lda: Optional[int] = None, ldb: Optional[int] = None,
                   ldc: Optional[int] = None, ldres: Optional[int] = None, ldaux: Optional[int] = None, misaligned=()) -> dict:
-    """What ``gemm_f32_ex`` decides for these arguments under the fp32 arithmetic selected now (avf_gemm_f32_plan: the
+    """What ``gemm_f32_ex`` decides for these arguments under the default arithmetic it reads (set_f32_arithmetic; avf_gemm_f32_plan: the
     launcher's own decision, host code only, no device needed): dict(kernel = "x3" (gemm_f32x3_kernel) | "mfma_t1" | "mfma_t2"
     (gemm_f32_kernel on 32 x 32 / 64 x 64 tiles), akf / bkf = the reduction is the unit-stride axis of A / B, S = split count,
     kchunk = reduction rows per split (0 unsplit), vec = 16-byte epilogue accesses of the x3 kernel).  Leading dimensions
@@ -551,8 +551,8 @@ def gemm_f32_ex(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b
 
 
 def gemm_f32_tn_group_plan(shapes, K: int) -> dict:
-    """What ``gemm_f32_tn_group`` decides for problems of the shapes [(M_i, N_i), ...] over K reduction rows under the fp32
-    arithmetic selected now (avf_gemm_f32_tn_group_plan, host code only): dict(ok = the grouped bf16x3 launch takes them,
+    """What ``gemm_f32_tn_group`` decides for problems of the shapes [(M_i, N_i), ...] over K reduction rows under the default
+    arithmetic it reads (set_f32_arithmetic; avf_gemm_f32_tn_group_plan, host code only): dict(ok = the grouped bf16x3 launch takes them,
     tiles = 128 x 128 tiles of the group, S = split count, kchunk = rows per split, workspace_bytes = what
     avf_gemm_f32_tn_group_workspace_bytes promises)."""
     lib = _lib.load()

@@ -160,14 +160,17 @@ class _StackFn(torch.autograd.Function):
         if keep is not None and keep.shape != (B, N):
             raise ValueError(f"mask has incorrect dimensions: {tuple(keep.shape)} after the leading True, tokens {(B, N)}")
         ctx.keep = keep  # token mask bytes (heads.py:225-232); the layer configurations carry its device pointer
+        # the parity mode's arithmetic, read HERE and nowhere later: the configurations carry it, and backward (ctx.cfgs) runs
+        # what this forward ran whatever set_f32_arithmetic has been told by then
+        arith = _lib.get_f32_arithmetic()
         # the L layer configurations are rebuilt only when something in them changes (shape, live dropout, seed / mask pointers)
         ckey = (B, N, mod.training, mod.dropout, None if seed_t is None else seed_t.data_ptr(),
-                None if keep is None else keep.data_ptr(), mod.compute_dtype, mod.mx8, mod.mx8_bwd, mod.resid_bf16)
+                None if keep is None else keep.data_ptr(), mod.compute_dtype, mod.mx8, mod.mx8_bwd, mod.resid_bf16, arith)
         chit = mod.__dict__.get("_cfg_cache")
         if chit is not None and chit[0] == ckey:
             cfgs = chit[1]
         else:
-            cfgs = [mod._cfg(B, N, l, seed_t, keep) for l in range(L)]
+            cfgs = [mod._cfg(B, N, l, seed_t, keep, arith) for l in range(L)]
             mod.__dict__["_cfg_cache"] = (ckey, cfgs)
         cfg = cfgs[0]
         params = list(params)  # (grad mode is off inside Function.forward: the Parameters are used for their storage only)
@@ -460,13 +463,16 @@ class Transformer(nn.Module):
         self._grad_hook = hook
 
     def _cfg(self, B: int, N: int, layer: int = 0, seed_t: Optional[torch.Tensor] = None,
-             keep: Optional[torch.Tensor] = None) -> _lib.LayerCfg:
+             keep: Optional[torch.Tensor] = None, arith: Optional[str] = None) -> _lib.LayerCfg:
+        """arith: the parity mode's arithmetic ("bf16x3" / "f32") of the calls made with this configuration; None = the
+        default of the moment (get_f32_arithmetic)"""
         p = self.dropout if self.training else 0.0  # nn.Dropout semantics: identity in eval()
         return _lib.LayerCfg(B, N, self.dim, self.heads, self.dim_head, self.mlp_dim, self.compute_dtype,
                              int(self.project_out), 1e-5, float(p), 0, 0, layer,
                              seed_t.data_ptr() if (seed_t is not None and p != 0.0) else None,
                              int(self._grad_stream_bf16(p)), int(self.mx8), int(self.resid_bf16), int(self.mx8_bwd),
-                             int(self.mx8_bwd and layer < self.depth - 1), None if keep is None else keep.data_ptr())
+                             int(self.mx8_bwd and layer < self.depth - 1), None if keep is None else keep.data_ptr(),
+                             _lib.F32_ARITH[arith if arith is not None else _lib.get_f32_arithmetic()])
 
     def _grad_stream_bf16(self, p: float) -> bool:
         """backward keeps the residual gradient between the LayerNorm backward kernels in bf16 (the GEMMs read that image

@@ -255,3 +255,44 @@ def test_group_plans(ops):
         assert not ops.gemm_f32_tn_group_plan(G.GROUP_CASES[0][0], 512)["ok"]
     finally:
         _with_arith(prev)
+
+
+def test_a_layer_configuration_carries_its_own_arithmetic(ops):
+    """avf_layer_cfg ends in f32_arith and the binding agrees on its size; what a layer call is told about its arithmetic comes
+    from that field alone, so the host-side queries answer the same under both settings of the process-wide default - which
+    stays the default of the operator-level plan queries, as before.  The buffers of a layer serve either arithmetic."""
+    import ctypes as C
+    L = A._lib
+    lib = L.load()
+    assert C.sizeof(L.LayerCfg) == lib.avf_sizeof_layer_cfg()
+    assert L.LayerCfg._fields_[-1][0] == "f32_arith"
+    mk = lambda dt, arith, N=64, D=128, H=2, dh=64, M=256: L.LayerCfg(8, N, D, H, dh, M, dt, 1, 1e-5, 0.0, 0, 0, 0, None, 0, 0, 0, 0, 0,
+                                                                      None, arith)
+    sizes = lambda cfg: tuple(f(C.byref(cfg)) for f in (lib.avf_layer_saved_bytes, lib.avf_layer_workspace_bytes, lib.avf_layer_lowp_bytes))
+    small = dict(N=16, D=256, H=8, dh=32)  # the short-sequence layer: fused kernels on bf16 (7), none on fp32 (0)
+    prev = L.get_f32_arithmetic()
+    try:
+        answers = set()
+        for setting in ("bf16x3", "f32"):
+            _with_arith(setting)
+            for arith in (0, 1):
+                assert A.ops.layer_small_path(mk(L.BF16, arith, **small)) == 7
+                assert A.ops.layer_small_path(mk(L.F32, arith, **small)) == 0
+                assert A.ops.layer_small_path(mk(L.F32, arith)) == 0
+                answers.add((sizes(mk(L.F32, arith)), sizes(mk(L.BF16, arith))))
+            assert sizes(mk(L.F32, 2)) == (0, 0, 0) and sizes(mk(L.F32, -1)) == (0, 0, 0)  # neither 0 nor 1: refused
+            assert A.ops.layer_small_path(mk(L.BF16, 2, **small)) == 0
+            assert "f32_arith" in lib.avf_last_error().decode()
+            # the operator-level queries read the default
+            x3 = setting == "bf16x3"
+            assert ops.gemm_f32_plan(128, 128, 64)["kernel"] == ("x3" if x3 else "mfma_t1")
+            assert bool(ops.gemm_f32_tn_group_plan(G.GROUP_CASES[0][0], 512)["ok"]) == x3
+            assert lib.avf_attn_parity_plan(L.F32, 64, 0, 0, 1, 2) == (2 if x3 else 1)
+            assert L.get_f32_arithmetic() == setting  # (no query moves it)
+        assert len(answers) == 1, answers  # one set of sizes, whatever the field and the default say
+        f32_sizes, bf16_sizes = answers.pop()
+        assert min(f32_sizes[:2]) > 0 and min(bf16_sizes) > 0, (f32_sizes, bf16_sizes)  # (and they are sizes, not refusals)
+        with pytest.raises(ValueError, match="bf16x3"):
+            L.set_f32_arithmetic("fp32")
+    finally:
+        _with_arith(prev)

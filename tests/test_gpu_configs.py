@@ -315,3 +315,50 @@ def test_g10_gelu_fixture_through_the_bf16x3_epilogues():
         auxin[:n, 0] = u
         d = ops.gemm(ones.to(DEV), w.to(DEV), epilogue=ops.EPI_DGELU, aux=auxin.to(DEV))
         torch.testing.assert_close(d[:n, 0].cpu(), g["dy_du"], atol=5e-6, rtol=5e-5)
+
+
+# ---------------------------------------------------------------------------------- the arithmetic travels with the call
+def test_backward_runs_the_arithmetic_its_forward_ran():
+    """A parity-mode stack reads set_f32_arithmetic once, when its forward builds the layer configurations; its backward runs
+    from those.  On a shape whose every GEMM, grouped weight gradient and attention call is planned onto bf16x3: a backward
+    issued after the default was flipped to "f32" gives the output and all 22 parameter gradients of the unflipped run bit for
+    bit, while a whole step under "f32" does not (so the comparison can see the arithmetic at all)."""
+    import avformer_amd as A
+    from attn_parity_util import parity_plan
+    ops, L = A.ops, A._lib
+    B, N, D, depth, H, dh, M = 8, 64, 128, 2, 2, 64, 256
+    R, inner = B * N, H * dh
+    linears = [(3 * inner, D), (D, inner), (M, D), (D, M)]  # W[out, in] of to_qkv, to_out, net.0, net.3
+    with f32_arithmetic("bf16x3"):
+        planned = (all(ops.gemm_f32_plan(R, o, i)["kernel"] == "x3" for o, i in linears)                      # y = x W^T
+                   and all(ops.gemm_f32_plan(R, i, o, trans_b=False)["kernel"] == "x3" for o, i in linears)   # dx = dy W
+                   and ops.gemm_f32_tn_group_plan(linears, R)["ok"]                                           # dW = dy^T x
+                   and parity_plan(A, dh, H) == "bf16x3")
+    if not planned:
+        pytest.skip("the dispatch heuristics no longer plan this shape onto the bf16x3 kernels")
+    sd, g = _state(D, depth, H, dh, M, 4242)
+    x = torch.randn(B, N, D, generator=g)
+    t = make_hip_transformer(sd, D, depth, H, dh, M, "f32")
+
+    def run(forward_under, backward_under):
+        xd = x.to(DEV).requires_grad_(True)
+        for p in t.parameters():
+            p.grad = None
+        prev = L.set_f32_arithmetic(forward_under)
+        try:
+            y = t(xd)
+            L.set_f32_arithmetic(backward_under)
+            SQ(y).backward()
+            torch.cuda.synchronize()
+        finally:
+            L.set_f32_arithmetic(prev)
+        return y.detach().clone(), {k: p.grad.clone() for k, p in t.named_parameters()}
+
+    ya, ga = run("bf16x3", "bf16x3")
+    yb, gb = run("bf16x3", "f32")
+    yc, gc = run("f32", "f32")
+    assert len(ga) == 22 and all(torch.isfinite(v).all() for v in ga.values())
+    assert torch.equal(yb, ya), "the forward under bf16x3 is not repeatable"
+    moved = [k for k in ga if not torch.equal(gb[k], ga[k])]
+    assert not moved, f"a backward after the flip ran another arithmetic than its forward: {moved}"
+    assert any(not torch.equal(gc[k], ga[k]) for k in ga), "a step under f32 equals the bf16x3 step bit for bit"
