@@ -5,7 +5,7 @@ The compute lives in ``lib/libavformer_hip.so`` (hand-written HIP for gfx950, C 
 ``include/avformer_hip.h``); this package is the host-side mirror of the reference's
 ``Transformer`` / head / loss / model-registry surface.
 """
-from . import _build, _lib, audio, audio_bank, augment, backbone, checkpoint, clip, dp, frames, graphs, metrics, ops, optim, predict, vggface2  # noqa: F401
+from . import _build, _cabi, _lib, audio, audio_bank, augment, backbone, checkpoint, clip, dp, frames, graphs, metrics, ops, optim, predict, vggface2  # noqa: F401
 from ._lib import get_f32_arithmetic, set_f32_arithmetic  # noqa: F401
 from .backbone import FrozenAudioModel, FrozenBasicBlock, FrozenResFormer, FrozenVideoModel  # noqa: F401
 from .vggface2 import FrozenBottleneck, FrozenVGGFace2, VGGFormer  # noqa: F401

@@ -10,229 +10,35 @@ import ctypes as C
 import os
 import threading
 
-from . import _build
+from . import _build, _cabi
 
-F32, BF16 = 0, 1
-EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = 0, 1, 2, 3
-CLIP_CTHW, CLIP_TCHW = 0, 1
-WAVE_F32, WAVE_I16 = 0, 1
-STEM_POOL_PAD1, STEM_POOL_CEIL = 0, 1
+_defines, _structs, _functions = _cabi.header()
 
-_vp = C.c_void_p
-_i64 = C.c_int64
-_int = C.c_int
-_f = C.c_float
-_sz = C.c_size_t
+F32, BF16 = _defines["AVF_F32"], _defines["AVF_BF16"]
+EPI_NONE, EPI_BIAS_RES, EPI_BIAS_GELU, EPI_DGELU = (_defines["AVF_EPI_" + n] for n in ("NONE", "BIAS_RES", "BIAS_GELU", "DGELU"))
+CLIP_CTHW, CLIP_TCHW = _defines["AVF_CLIP_CTHW"], _defines["AVF_CLIP_TCHW"]
+STEM_POOL_PAD1, STEM_POOL_CEIL = _defines["AVF_STEM_POOL_PAD1"], _defines["AVF_STEM_POOL_CEIL"]
+EX_CROSS_ENTROPY, EX_FOCAL = _defines["AVF_EX_CROSS_ENTROPY"], _defines["AVF_EX_FOCAL"]
+AU_BCE, AU_DICE_BCE = _defines["AVF_AU_BCE"], _defines["AVF_AU_DICE_BCE"]
+WAVE_F32, WAVE_I16 = 0, 1  # wave_dtype: the header states it in the comment above avf_mel_power_bank
 
 
-class LayerCfg(C.Structure):
-    _fields_ = [("batch", C.c_int32), ("tokens", C.c_int32), ("dim", C.c_int32), ("heads", C.c_int32),
-                ("dim_head", C.c_int32), ("mlp_dim", C.c_int32), ("dtype", C.c_int32), ("project_out", C.c_int32),
-                ("ln_eps", C.c_float), ("dropout_p", C.c_float), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
-                ("layer_index", C.c_int32), ("seed_dev", C.c_void_p), ("grad_stream_bf16", C.c_int32), ("mx8_fwd", C.c_int32),
-                ("resid_bf16", C.c_int32), ("mx8_bwd", C.c_int32), ("dx_out_mx8", C.c_int32), ("key_mask", C.c_void_p),
-                ("f32_arith", C.c_int32)]
+def _structure(name: str, c_name: str):
+    """the ctypes image of one of the header's structs, fields in the header's order (pickles by reference as _lib.<name>)"""
+    return type(name, (C.Structure,), {"_fields_": _structs[c_name], "__module__": __name__, "__qualname__": name,
+                                       "__doc__": c_name})
 
 
-PARAM_FIELDS = ("ln1_w", "ln1_b", "w_qkv", "w_out", "b_out", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")
+LayerCfg = _structure("LayerCfg", "avf_layer_cfg")
+LayerPtrs = _structure("LayerPtrs", "avf_layer_params")  # 11 device pointers in state_dict order; avf_layer_grads too:
+assert _structs["avf_layer_grads"] == _structs["avf_layer_params"], "avf_layer_grads no longer has avf_layer_params' layout"
+TaskLossCfg = _structure("TaskLossCfg", "avf_task_loss_cfg")
+EvalCfg = _structure("EvalCfg", "avf_eval_cfg")
+PARAM_FIELDS = tuple(n for n, _ in _structs["avf_layer_params"])
 
-
-class LayerPtrs(C.Structure):
-    """avf_layer_params / avf_layer_grads: 11 device pointers in state_dict order."""
-    _fields_ = [(n, _vp) for n in PARAM_FIELDS]
-
-
-class TaskLossCfg(C.Structure):
-    """avf_task_loss_cfg"""
-    _fields_ = [("ex_mode", C.c_int32), ("au_mode", C.c_int32), ("ex_col", C.c_int32), ("au_col", C.c_int32), ("va_col", C.c_int32),
-                ("va_ncols", C.c_int32), ("va_tanh", C.c_int32), ("normalize", C.c_int32), ("ex_use_ignore", C.c_int32),
-                ("reserved", C.c_int32), ("ex_ignore", C.c_int64), ("gamma", C.c_float), ("smooth", C.c_float),
-                ("ex_weight", C.c_float * 7), ("pos_weight", C.c_float * 12), ("au_ignore", C.c_float), ("va_ignore", C.c_float),
-                ("va_weight", C.c_float * 2), ("reserved2", C.c_float)]
-
-
-class EvalCfg(C.Structure):
-    """avf_eval_cfg"""
-    _fields_ = [("ex_col", C.c_int32), ("au_col", C.c_int32), ("va_col", C.c_int32), ("va_tanh", C.c_int32),
-                ("ex_ignore", C.c_int64), ("au_ignore", C.c_float), ("va_ignore", C.c_float)]
-
-
-EX_CROSS_ENTROPY, EX_FOCAL = 0, 1
-AU_BCE, AU_DICE_BCE = 0, 1
-
-# name -> (restype, argtypes); every symbol declared in include/avformer_hip.h
-SIGNATURES = {
-    "avf_version": (_int, []),
-    "avf_sizeof_layer_cfg": (_sz, []),
-    "avf_sizeof_layer_params": (_sz, []),
-    "avf_last_error": (C.c_char_p, []),
-    "avf_device_ok": (_int, []),
-    "avf_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _f, _vp]),
-    "avf_layernorm_bwd_workspace_bytes": (_sz, [_i64, _int]),
-    "avf_layernorm_bwd": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
-    "avf_layernorm_fwd_ex": (_int, [_vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _f, _vp]),
-    "avf_layernorm_bwd_ex": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int,
-                                    C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
-    "avf_colsum_workspace_bytes": (_sz, [_i64, _int]),
-    "avf_colsum": (_int, [_vp, _int, _i64, _int, _i64, _vp, _vp, _vp]),
-    "avf_cast_f32_to_bf16": (_int, [_vp, _vp, _i64, _vp]),
-    "avf_prep_weight_bf16": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
-    "avf_gemm_workspace_bytes": (_sz, [_int, _int, _int, _i64, _i64, _i64]),
-    "avf_gemm": (_int, [_int, _int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp,
-                        _i64, _vp, _i64, _vp, _vp]),
-    "avf_pack_weight_ws_ok": (_int, [_i64, _i64]),
-    "avf_pack_weight_ws_bytes": (_sz, [_i64, _i64]),
-    "avf_gemm_nt_ws_workspace_bytes": (_sz, [_i64, _i64]),
-    "avf_gemm_nt_ws_dispatch": (_int, [_i64, _i64, _i64, _int, _int]),
-    "avf_pack_weight_ws": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
-    "avf_gemm_nt_ex": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
-                              C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
-    "avf_gemm_nt_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _i64, _i64, _int, _f, C.POINTER(C.c_int),
-                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_gemm_nt_ws": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
-                              _vp]),
-    "avf_gemm_tn_group_workspace_bytes": (_sz, [_int, _i64, _vp, _vp]),
-    "avf_gemm_tn_group": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "avf_gemm_tn_group_plan": (_int, [_int, _i64, _vp, _vp, _vp]),
-    "avf_gemm_tn_plan": (_int, [_i64, _i64, _i64, _vp]),
-    "avf_gemm_f32_ex": (_int, [_int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp,
-                               C.c_uint32, C.c_uint32, _int, _int, _f, _vp]),
-    "avf_gemm_f32_plan": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _i64, _int, _int, _vp]),
-    "avf_gemm_f32_tn_group_workspace_bytes": (_sz, [_int, _i64, _vp, _vp]),
-    "avf_gemm_f32_tn_group_plan": (_int, [_int, _i64, _vp, _vp, _vp]),
-    "avf_gemm_f32_tn_group": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "avf_stack_quant_weights_mx8": (_int, [_vp, _int, _vp, _vp]),
-    "avf_quant_mx8": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "avf_gemm_mx8_nt": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64,
-                               _vp, _vp, _vp]),
-    "avf_gemm_mx8_nt_ex": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _i64,
-                                  _vp, _vp, C.c_uint32, C.c_uint32, _int, _int, _f, _vp, _vp, _vp]),
-    "avf_gemm_mx8_nt_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _i64, _i64, _int, _f, _int,
-                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_layernorm_fwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _vp]),
-    "avf_attn_fwd": (_int, [_int, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_bwd_workspace_bytes": (_sz, [_int, _int, _int, _int]),
-    "avf_attn_bwd": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_fwd_qs": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_bwd_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_plan": (_int, [_int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_attn_parity_plan": (_int, [_int, _int, _int, _int, _int, _int]),
-    "avf_attn_masked_on_mfma": (_int, [_int, _int]),
-    "avf_attn_fwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_bwd_masked_qs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_fuse_tokens": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_token_mean_fwd": (_int, [_vp, _vp, _int, _int, _int, _vp]),
-    "avf_token_mean_fwd_bf16": (_int, [_vp, _vp, _int, _int, _int, _vp]),
-    "avf_fuse_tokens_bf16": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_token_mean_bwd": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_bn1d_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _f, _f, _int, _vp]),
-    "avf_bn1d_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_token_dots_fwd": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _int, _int, _vp]),
-    "avf_token_dots_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _vp]),
-    "avf_assemble_tokens": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_cat_features": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_transpose_add": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_zero_cols": (_int, [_vp, _i64, _int, _int, _int, _vp]),
-    "avf_seed_advance": (_int, [_vp, _vp, _vp]),
-    "avf_linear_pad_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_linear_pad_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_au_loss": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _vp, _vp, _vp]),
-    "avf_au_loss_sum": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _vp, _vp, _vp]),
-    "avf_au_loss_wide": (_int, [_vp, _i64, _vp, _i64, _vp, _f, _int, _int, _int, _int, _vp, _vp, _vp]),
-    "avf_sizeof_task_loss_cfg": (_sz, []),
-    "avf_task_loss": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
-    "avf_task_loss_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
-    "avf_sizeof_eval_cfg": (_sz, []),
-    "avf_eval_update": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
-    "avf_eval_scores": (_int, [_vp, _vp, _vp, _vp]),
-    "avf_mel_power": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
-    "avf_mel_db_norm": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_double, C.c_double, C.c_double, _vp]),
-    "avf_mel_power_bank": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _vp,
-                                  _vp, _int, _int, _vp, _vp, _vp]),
-    "avf_wave_gather": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "avf_clip_normalize": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _int, _int, _vp]),
-    "avf_clip_denormalize": (_int, [_vp, _int, _int, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
-    "avf_clip_autoaugment": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
-    "avf_clip_autoaugment_max_pixels": (_i64, []),
-    "avf_clip_autoaugment_normalize": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp, _int, _int, _vp]),
-    "avf_clip_gather": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
-    "avf_clip_gather_normalize": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _int, _int,
-                                         _vp]),
-    "avf_clip_gather_autoaugment": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
-    "avf_clip_gather_autoaugment_normalize": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp,
-                                                     _vp, _int, _int, _vp]),
-    "avf_feature_clip_tokens": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp]),
-    "avf_conv_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_conv2d_nhwc": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _int, _vp]),
-    "avf_conv_pack_weight_f32x3": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_conv2d_nhwc_f32x3": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp, _int, _int, _int, _int, _int, _vp]),
-    "avf_conv_plan": (_int, [_int, _int, _int, _int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_avgpool_nhwc": (_int, [_vp, _int, _vp, _i64, _int, _int, _vp]),
-    "avf_stem_packed_k": (_int, [_int]),
-    "avf_stem_pack_weight": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _int, _int, _vp]),
-    "avf_stem_nchw": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _vp]),
-    "avf_stem_plan": (_int, [_int, _int, _int, _int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_stem_nchw_pool": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
-    "avf_stem_out_hw": (_int, [_int, _int, _int] + [C.POINTER(C.c_int)] * 4),
-    "avf_layer_saved_bytes": (_sz, [C.POINTER(LayerCfg)]),
-    "avf_layer_lowp_bytes": (_sz, [C.POINTER(LayerCfg)]),
-    "avf_layernorm_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
-    "avf_attn_fwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_bwd_emits_mx8": (_int, [_int, _int]),
-    "avf_attn_bwd_mx8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_fwd_masked": (_int, [_int, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_attn_bwd_masked": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "avf_layer_workspace_bytes": (_sz, [C.POINTER(LayerCfg)]),
-    "avf_layer_grad_stream_bytes": (_sz, [C.POINTER(LayerCfg)]),
-    "avf_layer_prepare_weights": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp]),
-    "avf_layer_fwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp]),
-    "avf_layer_bwd": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                             C.POINTER(LayerPtrs), _vp, _vp]),
-    "avf_layernorm_fwd_embed": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _f, _vp]),
-    "avf_layernorm_bwd_pos_ok": (_int, [_int, _int, _int]),
-    "avf_layernorm_bwd_pos_workspace_bytes": (_sz, [_int, _int, _int]),
-    "avf_layernorm_bwd_pos": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "avf_layer_fwd_embed_ok": (_int, [C.POINTER(LayerCfg)]),
-    "avf_layer_small_path": (_int, [C.POINTER(LayerCfg)]),
-    "avf_layer_fwd_embed": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
-    "avf_layer_bwd_pos_ok": (_int, [C.POINTER(LayerCfg)]),
-    "avf_layer_bwd_pos": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                 C.POINTER(LayerPtrs), _vp, _vp]),
-    "avf_layer_bwd_dx_pos": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp]),
-    "avf_layer_dw_defer_ok": (_int, [C.POINTER(LayerCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "avf_layers_dw_max": (_int, []),
-    "avf_layer_dw_block_bytes": (_sz, [C.POINTER(LayerCfg)]),
-    "avf_layer_dw_desc_bytes": (_sz, []),
-    "avf_layer_bwd_dx": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                C.POINTER(LayerPtrs), _vp, _vp, _vp, _vp]),
-    "avf_layers_dw_workspace_bytes": (_sz, [C.POINTER(LayerCfg), _int]),
-    "avf_layers_dw": (_int, [C.POINTER(LayerCfg), _int, _vp, _vp, _sz, _vp]),
-    "avf_layer_adam_step": (_int, [C.POINTER(LayerCfg), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs),
-                                   C.POINTER(LayerPtrs), _vp, _f, _f, _f, _f, _f, _vp, _vp]),
-    "avf_stack_adam_step": (_int, [C.POINTER(LayerCfg), _int, C.POINTER(LayerPtrs), C.POINTER(LayerPtrs), C.POINTER(LayerPtrs),
-                                   C.POINTER(LayerPtrs), _vp, _f, _f, _f, _f, _f, _vp, _vp]),
-    "avf_adam_step_tensors": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
-    "avf_adam_batch_begin": (_int, []),
-    "avf_adam_batch_end": (_int, []),
-    "avf_adam_batch_abort": (_int, []),
-    "avf_selftest_adam_table": (_int, [_vp]),
-    "avf_grad_control_workspace_bytes": (_sz, [_int, _vp]),
-    "avf_grad_control": (_int, [_int, _vp, _vp, _f, _int, _vp, _vp, _vp, _vp]),
-    "avf_adam_batch_control": (_int, [_vp]),
-    "avf_dropout_factors": (_int, [C.c_uint32, C.c_uint32, _int, _int, _f, _i64, _int, _vp, _vp]),
-    "avf_timing_enable": (_int, [_int]),
-    "avf_timing_read": (_int, [_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
-                               C.POINTER(C.c_double)]),
-    "avf_hip_error_reset": (_int, [_vp]),
-    "avf_crash_line_arm": (_int, [C.c_char_p, _int]),
-    "avf_crash_line_disarm": (_int, []),
-    "avf_set_f32_arith": (_int, [_int]),
-    "avf_get_f32_arith": (_int, []),
-    "avf_selftest_mfma_bf16": (_int, [_vp, _vp, _vp, _vp]),
-    "avf_selftest_mfma_f32": (_int, [_vp, _vp, _vp, _vp]),
-    "avf_selftest_tr16": (_int, [_vp, _vp, _vp]),
-}
+# name -> (restype, argtypes) of every entry point, as include/avformer_hip.h declares it (read by _cabi.py, not repeated here)
+SIGNATURES = _cabi.bind(_functions, {"avf_layer_cfg": LayerCfg, "avf_layer_params": LayerPtrs, "avf_layer_grads": LayerPtrs,
+                                     "avf_task_loss_cfg": TaskLossCfg, "avf_eval_cfg": EvalCfg})
 
 _lock = threading.Lock()
 _lib = None
@@ -291,6 +97,7 @@ def load(build_if_missing: bool = True):
     return _lib
 
 
+# class index -> name: the header states it in the comment above avf_timing_enable
 KERNEL_CLASSES = ("gemm_bf16_nt", "gemm_bf16_tn", "gemm_f32", "attn_fwd", "attn_bwd", "layernorm", "other", "gemm_mx8_nt")
 
 
@@ -315,7 +122,7 @@ def check(rc: int, what: str = ""):
         raise RuntimeError(f"libavformer_hip: {what} failed (rc={rc}): {msg}")
 
 
-F32_ARITH = {"f32": 0, "bf16x3": 1}
+F32_ARITH = {"f32": 0, "bf16x3": 1}  # mode: the header states it in the comment above avf_set_f32_arith
 
 
 def set_f32_arithmetic(mode: str) -> str:

@@ -13,6 +13,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _cabi
+
 
 class MultiLabelAccF1:
     def __init__(self, ignore_index: Optional[float] = -1, num_labels: int = 12):
@@ -55,9 +57,9 @@ class MultiLabelAccF1:
 # ---- the whole evaluation side of train.py:106-169 ------------------------------------------------------------------
 # Every metric of evaluate() is a function of plain sums over rows, so the accumulators below keep statistics, not samples:
 # they can be updated batch by batch without a host copy, merged, and summed across ranks with one collective.  The layout of
-# the 128 fp64 words is the one of include/avformer_hip.h (avf_eval_update).
-STATE_WORDS = 128
-EX_CONF, AU_STATS, VA_MOMENTS, LOSS_SUM, LOSS_STEPS = 0, 49, 109, 121, 122
+# the fp64 words is the one of include/avformer_hip.h (avf_eval_update), read from there.
+STATE_WORDS, EX_CONF, AU_STATS, VA_MOMENTS, LOSS_SUM, LOSS_STEPS = (
+    _cabi.header()[0]["AVF_EVAL_" + n] for n in ("STATE_WORDS", "EX_CONF", "AU_STATS", "VA_MOMENTS", "LOSS_SUM", "LOSS_STEPS"))
 SCORE_NAMES = ("ex_acc", "ex_f1", "ex_score", "au_acc", "au_f1", "au_score", "ccc_v", "ccc_a", "va_score", "avg_loss",
                "ex_kept_rows", "au_labelled")
 AU_SWITCH = 2.0 ** -23  # round(sigmoid(x)) leaves 0 above this logit with a correctly rounded fp32 sigmoid

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _cabi, _lib
 from ._lib import BF16, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_DGELU, EPI_NONE, F32  # noqa: F401
 
 _TORCH2AVF = {torch.float32: F32, torch.bfloat16: BF16}
@@ -829,8 +829,8 @@ def attn_bwd(qkv, o, d_o, lse2, batch: int, tokens: int, heads: int, dim_head: i
     return dqkv
 
 
-ATTN_KINDS = {0: "res8", 1: "res12", 2: "res_multi", 3: "stream", 4: "f32"}  # AVF_ATTN_* of avformer_hip.h
-ATTN_MERGED = 8
+ATTN_KINDS = {_cabi.header()[0]["AVF_ATTN_" + n.upper()]: n for n in ("res8", "res12", "res_multi", "stream", "f32")}
+ATTN_MERGED = _cabi.header()[0]["AVF_ATTN_MERGED"]
 
 
 def attn_plan(tokens: int, dim_head: int, q_prescaled: bool = False, masked: bool = False) -> dict:
