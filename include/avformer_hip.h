@@ -220,8 +220,8 @@ int avf_gemm_nt_ws(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, 
  * `workspace` (avf_gemm_tn_group_workspace_bytes) and are folded by a second launch; a group whose tiles fill the chip
  * unsplit needs no workspace (0 bytes) and stores straight to C_i.
  * avf_gemm_tn_group_plan: what that launch decides, by the function the launcher itself acts on (host code only; the
- * tuning switches AVF_TN_BIG / AVF_TN_WAVES / AVF_TN_XCD / AVF_TN_SPLITS count exactly as in the launch).  out[0] = 1 for the
- * 256 x 128 tile, 0 for the 128 x 128 one; out[1] = wavefronts per workgroup (4 or 8); out[2] = output tiles of the group;
+ * tuning switches AVF_TN_BIG / AVF_TN_XCD / AVF_TN_SPLITS count exactly as in the launch).  out[0] = 1 for the
+ * 256 x 128 tile, 0 for the 128 x 128 one; out[1] = wavefronts per workgroup (8 on the 256 x 128 tile, else 4); out[2] = output tiles of the group;
  * out[3] = S, the split count; out[4] = reduction rows per split (a multiple of 64; a split that starts past K writes a slab
  * of zeros); out[5] = the block order of the 256 x 128 kernel (> 0: XCD groups, -1: eighths of the split-major work list,
  * 0: tile-major; 0 on the 128 x 128 kernel); out[6] = workgroups launched; out[7] = the fold kernel's instantiation (2 .. 8 =

@@ -276,18 +276,8 @@ constexpr int RES_A = 1;          // tiles whose DMA is issued before any comput
 constexpr float RES_TAU = 6.0f;   // log2 of the largest probability kept before a rescale
 
 // The DMA of the head-resident forward is the asm form (glds16_asm; mfma_frag.hpp says why): with the builtin the pieces
-// fed from hooks inside the first tile's compute cost a full memory round trip each.  AVF_ATTN_DMA_ASM=0 at build time
-// (-DAVF_ATTN_DMA_ASM=0) restores the builtin.
-#ifndef AVF_ATTN_DMA_ASM
-#define AVF_ATTN_DMA_ASM 1
-#endif
-__device__ __forceinline__ void res_dma16(const void* g, char* l) {
-#if AVF_ATTN_DMA_ASM
-  glds16_asm(g, l);
-#else
-  glds<16>(g, l);
-#endif
-}
+// fed from hooks inside the first tile's compute cost a full memory round trip each.
+__device__ __forceinline__ void res_dma16(const void* g, char* l) { glds16_asm(g, l); }
 
 __device__ __forceinline__ bf16x8_t ones_frag() {
   u32x4_t r = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
@@ -975,11 +965,8 @@ store_row_pairs<DB>(outk, lg, [&](int d) { return dkt[d][kb] * kscale; });
 }  // namespace
 
 namespace {
-// head-resident kernels: dim_head 64, the head's two operands fit in LDS; AVF_ATTN_RESIDENT=0 forces the streaming ones
-bool use_resident(int N, int dh) {
-  static const int allow = tuning_int("AVF_ATTN_RESIDENT", 1);
-  return allow && dh == 64 && N <= RES_MAX_N;
-}
+// head-resident kernels: dim_head 64, the head's two operands fit in LDS
+bool use_resident(int N, int dh) { return dh == 64 && N <= RES_MAX_N; }
 
 // The head-resident variant for N tokens.  V = ceil(N/32) row groups: up to 8 take the 8-wave kernel and 9 .. 12 the 12-wave
 // one, a wave per row group in a single pass; more are spread over ceil(V/8) passes of the 8-wave multi-pass kernel.
@@ -1031,12 +1018,7 @@ int res_launch(const TimingScope* ts, const char* family, const char* tag, int b
 }  // namespace
 
 // log2(e)/sqrt(dh): the factor the layer path folds into the query rows of its bf16 Wqkv image
-// (AVF_ATTN_QS=0, a tuning aid, turns the folding off: factor 1 and the kernels that scale the scores themselves)
-bool attn_q_prescale_on() {
-  static const int on = tuning_int("AVF_ATTN_QS", 1);
-  return on != 0;
-}
-float attn_q_prescale(int dh) { return attn_q_prescale_on() ? LOG2E / sqrtf((float)dh) : 1.0f; }
+float attn_q_prescale(int dh) { return LOG2E / sqrtf((float)dh); }
 
 // the head-resident forward kernel can also write the MX-FP8 image of its output
 bool attn_fwd_emits_mx8(int N, int dh) { return use_resident(N, dh); }

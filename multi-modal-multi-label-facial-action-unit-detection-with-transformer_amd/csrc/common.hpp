@@ -22,7 +22,7 @@ int check_launch(const char* what);
 // <file> - tools/shape_table.py joins it with a rocprofv3 kernel trace into the per-shape table under profiles/.
 bool shape_log_on();
 void shape_log(const char* fmt, ...);
-// Every tuning / A-B switch of the library (AVF_NT_WS, AVF_NT_TILE, AVF_ATTN_RESIDENT, ...: INTEGRATION.md lists them) is read
+// Every tuning / A-B switch of the library (AVF_NT_WS, AVF_NT_TILE, AVF_TN_BIG, ...: INTEGRATION.md lists them) is read
 // through this: unless the process was started with AVF_TUNING=1 the switches do not exist - a product process runs ONE
 // dispatch, the one the parity tests exercised, whatever else is in its environment.
 inline const char* tuning_env(const char* name) {
@@ -712,7 +712,6 @@ size_t small_bwd_partial_floats(int B, int D, int M);
 int layer_bwd_small_a(int B, int N, int D, int I, int M, const SmallBwdAHost& h, hipStream_t s);
 int layer_bwd_small_b(int B, int N, int D, int I, const SmallBwdBHost& h, hipStream_t s);
 float attn_q_prescale(int dh);
-bool attn_q_prescale_on();
 // keep (optional, [B][N] bytes): the token mask of heads.py:225-232 on the MFMA kernels - attn_masked_bf16_ok says where
 int attn_fwd_bf16(const bf16* qkv, bf16* o, float* lse2, int B, int N, int H, int dh, hipStream_t s,
                   bool q_prescaled = false, void* mx_q = nullptr, void* mx_s = nullptr, const void* keep = nullptr);

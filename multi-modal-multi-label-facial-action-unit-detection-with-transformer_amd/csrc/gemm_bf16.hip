@@ -494,9 +494,9 @@ struct TnGroup {
 // both travel by value: the group to the GEMM kernels, the group and the column folds to fold_group_kernel
 static_assert(sizeof(TnGroup) + sizeof(FoldList) + 16 <= 4096, "TnGroup + FoldList exceed the 4 KiB kernel-argument budget");
 
-// WNW = wavefronts along N (2 -> 4 waves of 64x64, 4 -> 8 waves of 64x32)
-template <int WNW>
-__global__ __launch_bounds__(128 * WNW) void gemm_bf16_tn_group_kernel(TnGroup g) {
+// 4 waves of 64x64 (2 x 2); 8 waves of 64x32 measured 5 % slower here (unlike the NT kernel)
+__global__ __launch_bounds__(256) void gemm_bf16_tn_group_kernel(TnGroup g) {
+  constexpr int WNW = 2;         // wavefronts along N
   constexpr int OPB = TR * 256;  // bytes per operand per stage (64 rows x 256 B) = 16 KiB
   constexpr int NI = 8 / WNW;    // 16-column blocks per wave
   constexpr int INS = 8 / WNW;   // LDS-DMA instructions per wave per operand per stage (16 in total)
@@ -1011,8 +1011,7 @@ TnGroupPlan gemm_bf16_tn_group_plan_full(const TnGroupArgs& a) {
   pl.fold = fold_code(pl.S);
   pl.xcd_groups = 0;
   pl.blocks = pl.tiles * pl.S;
-  static const int tn_waves = tuning_int("AVF_TN_WAVES", 4);  // tuning aid; 8 waves measured 5 % slower here (unlike the NT kernel)
-  pl.waves = (pl.big || tn_waves != 4) ? 8 : 4;
+  pl.waves = pl.big ? 8 : 4;
   if (!pl.big) return pl;
   static const int xcd_order = tuning_int("AVF_TN_XCD", 1);  // tuning aid: 0 = tile-major block ids
   if (!xcd_order) return pl;
@@ -1085,8 +1084,7 @@ int gemm_bf16_tn_group(const TnGroupArgs& a, hipStream_t s, const FoldList* extr
       raised3.mark();
     }
     launch_in_scope(&ts, gemm_bf16_tn_group_big_kernel<3>, dim3(pl.blocks), dim3(512), 3 * 48 * 1024, s, g);
-  } else if (pl.waves == 4) launch_in_scope(&ts, gemm_bf16_tn_group_kernel<2>, dim3(pl.blocks), dim3(256), 0, s, g);
-  else launch_in_scope(&ts, gemm_bf16_tn_group_kernel<4>, dim3(pl.blocks), dim3(512), 0, s, g);
+  } else launch_in_scope(&ts, gemm_bf16_tn_group_kernel, dim3(pl.blocks), dim3(256), 0, s, g);
   AVF_TRY(check_launch("gemm_bf16_tn_group_kernel"));
   FoldList fl;
   memset(&fl, 0, sizeof(fl));

@@ -199,7 +199,7 @@ template <int EPI, typename CT>
 NtPlan nt_plan_mx8(const NtParams& p) {
   // K/2: the same LDS bytes per row as a bf16 problem of that depth; the kernel has two LDS stages
   const int tile = pick_nt_tile(p.M, p.N, p.K / 2), ti = nt_tile_index(tile, /*max_stages=*/2);
-  // The instantiations are (tile, LEAN): tiles 0, 1, 2, 3, 5 with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every
+  // The instantiations are (tile, LEAN): tiles 1, 2, 5 with 0; tiles 2 and 5 - the 8-wave ones - also with 1 (every
   // epilogue), 5 (BIAS_GELU, DGELU) and 3, 7 (DGELU).  The lean epilogue (options fixed at compile time) runs when nothing asks
   // for the general one's (and never on an id that only runs as tile 2 because this kernel does not have it).
   int lean = 1 + (p.cs_partial ? 2 : 0) + (p.mxq ? 4 : 0);

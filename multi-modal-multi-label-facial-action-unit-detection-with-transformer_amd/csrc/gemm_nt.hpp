@@ -535,16 +535,14 @@ __device__ __forceinline__ void lds_read_words(uint32_t* dst, uint32_t addr, std
 }
 
 // tile configurations (block tile, wavefronts, LDS stages, resident blocks per CU):
-//   0: 128x128, 4 waves of 64x64, 2 stages (64 KiB, 2/CU)
 //   1:  64x128, 4 waves of 32x64, 2 stages (48 KiB, 3/CU)   - finer grain for grids that cannot fill the chip
-//   2: 128x128, 8 waves of 64x32, 2 stages (64 KiB, 2/CU)   - twice the waves per CU hide the DMA / epilogue
-//                                                             latency better (+5..8 % measured at K = 512..1536)
-//   3:  96x128, 4 waves of 48x64, 2 stages (56 KiB, 2/CU)   - M = 10368, N = 512: 432 workgroups fill the 512 slots in
-//                                                             one round; 8..11 % faster than (1) once K >= 1024
-//   5:  96x128, 8 waves of 48x32, 2 stages (56 KiB, 2/CU)   - the same tile with twice the waves (12 DMA instructions per
-//                                                             operand dealt round-robin to 8 waves): 0.3..2.2 us faster than
-//                                                             (1) / (3) on every N = 512 shape of C2, replaces both there
-// (3- and 4-stage rings, 256x128 / 256x256 / 192x128 tiles, 64x64 tiles and a persistent tile loop were all measured slower
+//   2: 128x128, 8 waves of 64x32, 2 stages (64 KiB, 2/CU)   - twice the waves per CU hide the DMA / epilogue latency better
+//                                                             than four 64x64 waves (+5..8 % measured at K = 512..1536)
+//   5:  96x128, 8 waves of 48x32, 2 stages (56 KiB, 2/CU)   - M = 10368, N = 512: 432 workgroups fill the 512 slots in one
+//                                                             round (12 DMA instructions per operand dealt round-robin to 8
+//                                                             waves): 0.3..2.2 us faster than (1) on every N = 512 shape of C2
+// (ids 0 and 3, the four-wave forms of 2 and 5, were measured, lost to them on every shape and were removed;
+//  3- and 4-stage rings, 256x128 / 256x256 / 192x128 tiles, 64x64 tiles and a persistent tile loop were all measured slower
 //  on this path's shapes - M = 10k..16k, N = 512..1536, K = 512..1536 - and removed: the waves wait ~55 % of their
 //  cycles (SQ_WAIT_ANY) on LDS/barrier latency, which more resident waves hide better than deeper DMA rings)
 //   6:  32x 64, 4 waves of 32x16, 3 stages (36 KiB, 4/CU)   - the bf16 kernel's small-M tile (pick_nt_tile_bf16)
@@ -557,8 +555,7 @@ struct NtTile {
   constexpr int part_rows() const { return WM; }     // column-sum partial rows per block tile: one per wave row
   constexpr bool lean() const { return WM * WN == 8; }  // the 8-wave tiles have the lean-epilogue instantiations
 };
-constexpr NtTile kNtTiles[] = {{0, 2, 2, 4, 4, 2}, {1, 2, 2, 2, 4, 2}, {2, 2, 4, 4, 2, 2},
-                               {3, 2, 2, 3, 4, 2}, {5, 2, 4, 3, 2, 2}, {6, 1, 4, 2, 1, 3}};
+constexpr NtTile kNtTiles[] = {{1, 2, 2, 2, 4, 2}, {2, 2, 4, 4, 2, 2}, {5, 2, 4, 3, 2, 2}, {6, 1, 4, 2, 1, 3}};
 constexpr int kNtTileCount = sizeof(kNtTiles) / sizeof(kNtTiles[0]);
 // index of tile `id`; an id the table does not hold, or one with a deeper ring than the kernel has stages, runs as tile 2
 constexpr int nt_tile_index(int id, int max_stages = 8) {
@@ -571,14 +568,12 @@ constexpr int nt_tile_index(int id, int max_stages = 8) {
 }
 template <typename F>
 int with_nt_tile(int index, F&& f) {  // f(int_c<index>{}): kNtTiles[index] as a compile-time value
-  static_assert(kNtTileCount == 6, "one case per table entry");
+  static_assert(kNtTileCount == 4, "one case per table entry");
   switch (index) {
     case 0: return f(int_c<0>{});
     case 1: return f(int_c<1>{});
     case 2: return f(int_c<2>{});
-    case 3: return f(int_c<3>{});
-    case 4: return f(int_c<4>{});
-    default: return f(int_c<5>{});
+    default: return f(int_c<3>{});
   }
 }
 int nt_lean_on() {
@@ -630,8 +625,7 @@ int pick_nt_tile(int64_t M, int64_t N, int64_t K) {
 // 1088-row layer (816 workgroups at N = 1536) then fit the chip's slots in one round, and co-resident workgroups hide a round trip as
 // well as ring depth does: TFormer (17 tokens, d = 512, B = 64) 144 -> 133 us per layer replayed (2 slots 146, 4 slots 134).
 int pick_nt_tile_bf16(int64_t M, int64_t N, int64_t K) {
-  static const int small_on = tuning_int("AVF_NT_SMALL_M", 1);  // A/B aid: 0 = the large tiles for every shape
-  if (nt_tile_forced() < 0 && small_on && M <= 2048 && ceil_div(M, 96) * ceil_div(N, 128) <= 160) return 6;
+  if (nt_tile_forced() < 0 && M <= 2048 && ceil_div(M, 96) * ceil_div(N, 128) <= 160) return 6;
   return pick_nt_tile(M, N, K);
 }
 

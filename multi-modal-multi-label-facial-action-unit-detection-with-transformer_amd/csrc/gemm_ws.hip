@@ -37,12 +37,6 @@ constexpr int WS_KS = WS_K / 32;   // MFMA k-steps per tile
 #ifndef AVF_WS_STAMPS
 #define AVF_WS_STAMPS 0
 #endif
-#ifndef AVF_WS_EPI_PRIO
-#define AVF_WS_EPI_PRIO 2
-#endif
-#ifndef AVF_WS_DBG
-#define AVF_WS_DBG 0  // timing experiments (WRONG results): bit 0 = no DMA after the prologue, bit 1 = no stores (epilogue sees M = 0)
-#endif
 constexpr int WS_NSTAMP = 64;
 #if AVF_WS_STAMPS
 __device__ unsigned long long g_ws_stamps[512 * 8 * WS_NSTAMP];
@@ -252,7 +246,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
     // well as in its vmcnt, so a DMA issued in front of the K-loop turns every counted lgkmcnt wait of the fragment reads into
     // a wait for the DMA (64 MFMAs: 1850 cycles with the DMA in front, 1280 with none in flight)
     const bool more2 = t + 2 < nt, more1 = t + 1 < nt;
-    if (more2 && !(AVF_WS_DBG & 1)) dma_tile(t0 + t + 2, lds0 + wr_slot);
+    if (more2) dma_tile(t0 + t + 2, lds0 + wr_slot);
     if (more1) pre_dma(t0 + t + 1, (t + 1) & 1);
     WS_STAMP(7 + 6 * t);
     // everything OLDER than what this iteration issued has landed - this wave's pieces of tile t + 1 and the staged epilogue
@@ -275,16 +269,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_ws_kernel(NtParams p, const 
     }
     // the epilogue's vector instructions outrank the SIMD partner's MFMA stream: a wave in its epilogue is on the workgroup's
     // critical path (2480 cycles beside a partner issuing MFMAs against 1450 alone), the matrix pipe has slack
-    __builtin_amdgcn_s_setprio(AVF_WS_EPI_PRIO);
-    if constexpr ((AVF_WS_DBG & 2) != 0) {
-      NtParams p2 = p;
-      p2.M = 0;  // every store predicated off
-      nt_epilogue_lean<EPI, CT, MI, NI, 0, true>(p2, acc, (t0 + t) * BM, n0, li, lg, -1, &pre);
-    } else {
-      // (no bias on the plain and the dGELU form: gemm_bf16_nt_ws_ok)
-      nt_epilogue_lean<EPI, CT, MI, NI, CS ? 2 : 0, true, MXO, EPI != AVF_EPI_NONE && EPI != AVF_EPI_DGELU, DROP>(
-          p, acc, (t0 + t) * BM, n0, li, lg, -1, &pre, cs_acc, dkey);
-    }
+    __builtin_amdgcn_s_setprio(2);
+    // (no bias on the plain and the dGELU form: gemm_bf16_nt_ws_ok)
+    nt_epilogue_lean<EPI, CT, MI, NI, CS ? 2 : 0, true, MXO, EPI != AVF_EPI_NONE && EPI != AVF_EPI_DGELU, DROP>(
+        p, acc, (t0 + t) * BM, n0, li, lg, -1, &pre, cs_acc, dkey);
     __builtin_amdgcn_s_setprio(0);
     rd_slot = rd_slot + SLOT == NSLOT * SLOT ? 0 : rd_slot + SLOT;
     wr_slot = wr_slot + SLOT == NSLOT * SLOT ? 0 : wr_slot + SLOT;
@@ -415,30 +403,27 @@ bool gemm_bf16_nt_ws_ok(const GemmArgs& a) {
 // ... and the shapes gemm_bf16_nt() SENDS there (avf_gemm_nt_ws takes every shape the kernel can run)
 bool gemm_bf16_nt_ws_preferred(const GemmArgs& a) {
   if (!gemm_bf16_nt_ws_ok(a)) return false;
-  {
-    static const int mask = tuning_int("AVF_NT_WS_EPI", 15);  // tuning aid: bit e set = epilogue e (AVF_EPI_*) may take the persistent kernel
-    if (!((mask >> a.epilogue) & 1) && !a.mx_q) return false;
-  }
+  if (a.epilogue < AVF_EPI_NONE || a.epilogue > AVF_EPI_DGELU) return false;  // (no epilogue: the tiled path's error reports it)
   // bias + residual (the out-projection, N = dim): the persistent kernel pays its prologue (a CU's 256 KiB of weights out of
   // L2, ~3 us) once per workgroup; with 4 row tiles per workgroup (C3: 512 tiles over 128 groups) the tiled kernel is ahead -
   // 15.5 against 16.8 us at C3, 13.1 against 14.4 at C2, per-shape rocprof of the pipeline - so this form needs 6 tiles
+  constexpr int kWsResMinTiles = 6;  // row tiles per persistent workgroup from which bias + residual is sent here
   if (a.epilogue == AVF_EPI_BIAS_RES) {
     const int64_t P = a.N / WS_BN, T = (a.M + 31) / 32;
     int64_t G = ws_grid() / P;
     G = G > T ? T : G;
-    static const int min_tiles = tuning_int("AVF_NT_WS_RES_TILES", 6);  // tuning aid
-    if (T / G < min_tiles) return false;
+    if (T / G < kWsResMinTiles) return false;
   }
   // plain, N = dim (d_o in backward): the same prologue serves two column panels only - below three row tiles per workgroup the
   // tiled kernel (whose launches at these sizes leave slots empty and warm their weights, gemm_bf16.hip) is ahead with the weight
   // image cold as in the step: 10.4 against 12.2 us at C2's 10368 rows, 8.1 / 9.7 at 5184, 6.1 / 7.8 at 2048; N = 1536 stays
   // here at every row count (tools/diag/ws_vs_tiled_small_m.py)
+  constexpr int kWsPlainMinTiles = 3;  // row tiles per persistent workgroup below which a plain N <= 512 GEMM goes to the tiled kernel
   if (a.epilogue == AVF_EPI_NONE && a.N / WS_BN <= 2) {
     const int64_t P = a.N / WS_BN, T = (a.M + 31) / 32;
     int64_t G = ws_grid() / P;
     G = G > T ? T : G;
-    static const int min_tiles0 = tuning_int("AVF_NT_WS_PLAIN_TILES", 3);  // tuning aid
-    if (T < min_tiles0 * G) return false;
+    if (T < kWsPlainMinTiles * G) return false;
   }
   return true;
 }

@@ -485,9 +485,9 @@ static int fwd_attention(const Dims& d, const Saved& sv, void* oq, void* os, hip
   const bool lo = d.dt == AVF_BF16;
   // token mask (heads.py:225-232): on the MFMA kernels where they carry it (bf16, dim_head 64, up to 512 tokens), else on
   // the fp32-arithmetic ones (attn_fwd_masked_bf16 chooses); the fp8 mode and the fp32 mode go to the fp32-arithmetic ones directly
-  if (d.keep && lo && !d.mx) return attn_fwd_masked_bf16(sv.qkv, sv.o, sv.lse2, d.keep, d.B, d.N, d.H, d.dh, s, attn_q_prescale_on());
-  if (d.keep) return attn_fwd_vec(d.dt, sv.qkv, sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.keep, d.mx && attn_q_prescale_on(), d.arith);
-  if (lo) return attn_fwd_bf16((const bf16*)sv.qkv, (bf16*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), oq, os);
+  if (d.keep && lo && !d.mx) return attn_fwd_masked_bf16(sv.qkv, sv.o, sv.lse2, d.keep, d.B, d.N, d.H, d.dh, s, /*q_prescaled=*/true);
+  if (d.keep) return attn_fwd_vec(d.dt, sv.qkv, sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.keep, /*q_prescaled=*/d.mx, d.arith);
+  if (lo) return attn_fwd_bf16((const bf16*)sv.qkv, (bf16*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, /*q_prescaled=*/true, oq, os);
   return attn_fwd_f32((const float*)sv.qkv, (float*)sv.o, sv.lse2, d.B, d.N, d.H, d.dh, s, d.arith);
 }
 
@@ -526,8 +526,7 @@ static int layer_fwd_impl(const avf_layer_cfg* cfg, const avf_layer_params* p, c
     o_mx = o_mx_on && !d.keep && attn_fwd_emits_mx8(d.N, d.dh) && d.I % 128 == 0;
   } else if (small_fwd_taken(d)) {  // short sequences: the whole layer in one launch
     const bool lo = d.dt == AVF_BF16;
-    const float sc = attn_q_prescale_on() ? 1.0f : 1.4426950408889634f / sqrtf((float)d.dh);
-    return layer_fwd_small(d.B, d.N, d.D, d.H, d.M, cfg->ln_eps, sc, p, lo ? qkv.lo : (const void*)qkv.w, lo ? out.lo : (const void*)out.w,
+    return layer_fwd_small(d.B, d.N, d.D, d.H, d.M, cfg->ln_eps, /*score_scale=*/1.0f, p, lo ? qkv.lo : (const void*)qkv.w, lo ? out.lo : (const void*)out.w,
                            lo ? mlp1.lo : (const void*)mlp1.w, lo ? mlp2.lo : (const void*)mlp2.w, (const float*)x_in, (float*)io.x_out,
                            sv.h1, sv.mean1, sv.rstd1, sv.qkv, sv.o, sv.lse2, (float*)sv.x_mid, sv.h2, sv.mean2, sv.rstd2, sv.u, sv.g,
                            dr.site0, dr.site1, dr.site2, s);
@@ -746,15 +745,15 @@ int LayerBwd::small() {
   const bool fuse_att = small_att_fused(d);
   if (!fuse_att)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
-                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on()));
+                          d.B, d.N, d.H, d.dh, s, /*q_prescaled=*/true));
   SmallBwdBHost hb;
   hb.attention = fuse_att ? 1 : 0;
   hb.qkv = sv.qkv; hb.o = sv.o; hb.d_o = w.d_o; hb.lse2 = sv.lse2; hb.H = d.H;
   {  // P = exp2(s c - lse2); dq = scale dS k; dk = scale dS^T q = dS^T q' / log2(e) when q' = q log2(e) scale (attn_bf16.hip)
     const float scale = 1.0f / sqrtf((float)d.dh), log2e = 1.4426950408889634f;
-    hb.score_scale = attn_q_prescale_on() ? 1.0f : log2e * scale;
+    hb.score_scale = 1.0f;
     hb.dq_scale = scale;
-    hb.dk_scale = attn_q_prescale_on() ? 1.0f / log2e : scale;
+    hb.dk_scale = 1.0f / log2e;
   }
   hb.dqkv = w.dqkv; hb.wqkv_t = W.lin[kQkv].lo_t; hb.x_in = (const float*)io.x_in; hb.ln1_w = p->ln1_w; hb.mean1 = sv.mean1;
   hb.rstd1 = sv.rstd1; hb.dx_mid = d.gs16 ? nullptr : w.dx_mid; hb.dx_mid_lo = w.dx_mid_lo; hb.dx_in = io.dx_in; hb.dx_in_lo = io.dx_in_lo;
@@ -774,18 +773,14 @@ int LayerBwd::mlp_half() {
   // config 5, backward half: the three dX GEMMs whose A operand leaves a row-wise producer (LayerNorm backward of this /
   // the next layer, the dGELU epilogue) read MX-FP8 images written by that producer; dqkv -> dh1 (A produced per head by the
   // attention backward) and the four weight-gradient GEMMs (reduction over tokens, not features) stay bf16
-  bool dgelu_ws_first = false;
-  if (d.mxb) {
-    if (!gy.q) {  // top of the stack (or a caller without the image): one quantiser pass over the bf16 gradient
-      AVF_TRY(quant_mx8(gy.x, AVF_BF16, d.D, d.R, d.D, w.gyq, d.D, w.gys, s));
-      gy.q = w.gyq; gy.s = w.gys;
-    }
-    // Where the weight-stationary bf16 kernel takes the shape it is the faster form of the dGELU launch even in the fp8 mode (C5:
-    // 49 us against 70 on MX-FP8 operands - the launch is bound by the 168 MB it reads and writes beside the operands, which fp8
-    // does not touch); it emits the same image of du
-    static const int dgelu_ws = tuning_int("AVF_MX8_DGELU_WS", 1);  // A/B aid: 0 = the dGELU GEMM of the fp8 mode on MX-FP8 operands
-    dgelu_ws_first = dgelu_ws != 0;
+  if (d.mxb && !gy.q) {  // top of the stack (or a caller without the image): one quantiser pass over the bf16 gradient
+    AVF_TRY(quant_mx8(gy.x, AVF_BF16, d.D, d.R, d.D, w.gyq, d.D, w.gys, s));
+    gy.q = w.gyq; gy.s = w.gys;
   }
+  // Where the weight-stationary bf16 kernel takes the shape it is the faster form of the dGELU launch even in the fp8 mode (C5:
+  // 49 us against 70 on MX-FP8 operands - the launch is bound by the 168 MB it reads and writes beside the operands, which fp8
+  // does not touch); it emits the same image of du
+  const bool dgelu_ws_first = d.mxb;
   // du = (gy W2) * gelu'(u), with the image of du for the fp8 GEMM behind it (mx8_bwd); bf16: db1 = colsum(du) fused into the epilogue
   GemmArgs e_dgelu;
   e_dgelu.epilogue = AVF_EPI_DGELU; e_dgelu.aux = sv.u; e_dgelu.drop = dr.site1; e_dgelu.mx_q = w.duq; e_dgelu.mx_s = w.dus;
@@ -816,16 +811,16 @@ int LayerBwd::attn_half() {
   // gains ~9 us: C5 5.06 ms per step with it against 4.93 without - OFF unless AVF_MX8_DQKV=1.
   const int dq_mx_on = tuning_int("AVF_MX8_DQKV", 0);  // (read per call: a test flips it inside one process)
   const bool dq_mx = d.mxb && dq_mx_on && !d.keep && (3 * d.I) % 128 == 0 && d.D % 128 == 0 &&
-                     attn_bwd_emits_mx8(d.N, d.dh, attn_q_prescale_on());
+                     attn_bwd_emits_mx8(d.N, d.dh, /*q_prescaled=*/true);
   if (d.keep && lo && !d.mx)  // (attn_bwd_masked_bf16 chooses as the forward's attn_fwd_masked_bf16 did)
     AVF_TRY(attn_bwd_masked_bf16(sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, d.keep, d.B, d.N, d.H, d.dh, s,
-                                 attn_q_prescale_on()));
+                                 /*q_prescaled=*/true));
   else if (d.keep)
     AVF_TRY(attn_bwd_vec(d.dt, sv.qkv, sv.o, w.d_o, sv.lse2, w.dqkv, w.delta, d.B, d.N, d.H, d.dh, s, d.keep,
-                         lo && attn_q_prescale_on(), d.arith));
+                         /*q_prescaled=*/lo, d.arith));
   else if (lo)
     AVF_TRY(attn_bwd_bf16((const bf16*)sv.qkv, (const bf16*)sv.o, (const bf16*)w.d_o, sv.lse2, (bf16*)w.dqkv, w.delta,
-                          d.B, d.N, d.H, d.dh, s, attn_q_prescale_on(), nullptr, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr));
+                          d.B, d.N, d.H, d.dh, s, /*q_prescaled=*/true, nullptr, dq_mx ? w.dqq : nullptr, dq_mx ? w.dqs : nullptr));
   else
     AVF_TRY(attn_bwd_f32((const float*)sv.qkv, (const float*)sv.o, (const float*)w.d_o, sv.lse2, (float*)w.dqkv,
                          w.delta, d.B, d.N, d.H, d.dh, s, d.arith));

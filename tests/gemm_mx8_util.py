@@ -63,7 +63,6 @@ VARIANTS = {
     "TILE2_LEAN": (2, True, [(4000, 2048, 384), (4096, 2048, 128)]),
     "TILE2_GEN": (2, False, [(4000, 2040, 128)]),
 }
-FORCED_SHAPES = [(300, 256, 384), (300, 264, 384)]  # tiles 0 and 3 (AVF_TUNING=1 AVF_NT_TILE=0|3), one child process each
 UNIT_BIAS, UNIT_AUX = 64.0, 30.0
 
 

@@ -258,3 +258,44 @@ def simulate(inp, f=None, f_ldc=None, mutant=None):
         C[16:32, c0 + 4:c0 + 8], C[16:32, c0 + 16:c0 + 20] = blk[:, 16:20], blk[:, 4:8]
     trunc = mutant == "bf16_truncated"
     return round_to(C, cdt, trunc), (None if aux is None else round_to(aux, cdt, trunc)), cs.float()
+
+
+# ------------------------------------------------------------------------------------------------
+# The tile table (kNtTiles of csrc/gemm_nt.hpp) and the shapes whose UNFORCED plan is each of its entries: every entry must
+# be some shape's own pick, or it is a kernel family no input reaches (tests/test_gemm_nt_ref_cpu.py, test_gemm_mx8_ref_cpu.py).
+# (M, N) -> the tile pick_nt_tile plans at any K; the first row is the bf16 kernel's small-M tile 6 at K = 128 and tile 5 of
+# the MX-FP8 kernel at K = 384 (which has no tile 6: two LDS stages).
+PLAN_SHAPES = {(300, 264): None, (4096, 512): 5, (8192, 1024): 2, (10368, 768): 1}
+_TABLE_CHILD = r"""
+import avformer_amd as A
+M, N = 8192, 1024
+print("HELD", A.ops.gemm_nt_plan(M, N, 512)["tile"], A.ops.gemm_mx8_plan(M, N, 512)["tile"])
+"""
+_held = {}
+
+
+def tile_ids_held(repo, ids=range(8)):
+    """-> {"bf16": ids, "mx8": ids}: the tile ids the two kernels' tables hold, asked of the launcher's own plan with the id
+    forced (AVF_TUNING=1 AVF_NT_TILE=id, read once per process: one child per id, side by side; host code, no device).  An id a
+    table does not hold plans as tile 2."""
+    import os
+    import subprocess
+    import sys
+    if not _held:
+        procs = {}
+        for i in ids:
+            env = dict(os.environ, AVF_TUNING="1", AVF_NT_TILE=str(i))
+            procs[i] = subprocess.Popen([sys.executable, "-c", _TABLE_CHILD], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                                        text=True, env=env, cwd=repo)
+        held = {"bf16": set(), "mx8": set()}
+        for i, pr in procs.items():
+            out, err = pr.communicate(timeout=300)
+            assert pr.returncode == 0, err[-2000:]
+            bf, mx = [int(x) for x in [l for l in out.splitlines() if l.startswith("HELD ")][-1].split()[1:]]
+            assert bf in (i, 2) and mx in (i, 2), (i, bf, mx)
+            if bf == i:
+                held["bf16"].add(i)
+            if mx == i:
+                held["mx8"].add(i)
+        _held.update(held)
+    return _held

@@ -184,7 +184,7 @@ def _rows(group, Ks, splits, big, waves, xcd_on=True, heuristic_S=None):
     return out
 
 
-# child name -> (environment beside AVF_TUNING=1, rows).  AVF_TN_BIG / AVF_TN_WAVES / AVF_TN_XCD are read once per process;
+# child name -> (environment beside AVF_TUNING=1, rows).  AVF_TN_BIG / AVF_TN_XCD are read once per process;
 # AVF_TN_SPLITS per call: a child sweeps it.
 CHILDREN = {
     "default": ({},
@@ -196,8 +196,6 @@ CHILDREN = {
             + _rows("SQ1024", [576], [9], 1, 8)   # 288 workgroups on 256 slots: a second round
             + _rows("R16", [192], [1, 3], 1, 8)),
     "big_tile_major": ({"AVF_TN_BIG": "1", "AVF_TN_XCD": "0"}, _rows("R4", [320], [1, 3, 8], 1, 8, xcd_on=False)),
-    "waves8": ({"AVF_TN_BIG": "0", "AVF_TN_WAVES": "8"},
-               _rows("R4", [320], [1, 2, 3, 8], 0, 8) + _rows("R16", [320], [1, 2, 3, 8], 0, 8)),
 }
 
 # the single-problem path: (M, N, K) -> the plan avf_gemm_tn_plan must report
@@ -212,7 +210,7 @@ SINGLE = [
 
 
 def kernel_of(plan):
-    return "big" if plan["big"] else ("g128w8" if plan["waves"] == 8 else "g128")
+    return "big" if plan["big"] else "g128"
 
 
 def reached_by_group(plan, K):
@@ -236,9 +234,9 @@ def reached_by_single(plan, K):
 
 
 # what the whole GPU file must have reached (test_every_variant_was_reached; proven on the CPU for the table first)
-WANT = ({("kernel", k) for k in ("single", "g128", "g128w8", "big")}
+WANT = ({("kernel", k) for k in ("single", "g128", "big")}
         | {("fold", f) for f in (-1, 0, 2, 3, 4, 5, 6, 7, 8)}
         | {("xcd", x) for x in (8, 4, 2, 1, -1, 0)}
-        | {("dead", k) for k in ("single", "g128", "g128w8", "big")}
+        | {("dead", k) for k in ("single", "g128", "big")}
         | {("steps", n) for n in (0, 1, 2, 3, 4, 5, 7)}
         | {("single_S", s) for s in (1, 3, 10, 32)})

@@ -170,3 +170,20 @@ def test_the_plan_names_every_variant_the_gpu_test_lists():
                     assert plan(m, n, k, cdt, X.EPI_BIAS_GELU, want_image=True)["lean"] == 5
                     assert plan(m, n, k, cdt, X.EPI_BIAS_GELU, p=0.2)["lean"] == 0
                     assert plan(m, n, k, cdt, X.EPI_NONE, want_colsum=True)["lean"] == 0
+
+
+def test_every_tile_of_the_table_is_some_shapes_own_plan():
+    """host code only: the tile ids this kernel has (asked with each id forced; the three-stage tile 6 is the bf16 kernel's)
+    are exactly the ones tests/test_gpu_gemm_mx8.py lists, and each is what avf_gemm_mx8_nt_plan picks UNFORCED for some shape"""
+    import os
+    import avformer_amd as A
+    A._build.build()
+    held = G.tile_ids_held(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))["mx8"]
+    assert held == {1, 2, 5}, held
+    picked = set()
+    for (m, n), tile in G.PLAN_SHAPES.items():
+        for k in (384, 1536):
+            plan = A.ops.gemm_mx8_plan(m, n, k)
+            assert plan["tile"] == (5 if tile is None else tile), (m, n, k, plan)
+            picked.add(plan["tile"])
+    assert picked == held, (picked, held)

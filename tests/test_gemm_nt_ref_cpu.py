@@ -1,6 +1,7 @@
 """No device: the fp64 reference and the element-wise bounds of tests/gemm_nt_util.py pass a correctly rounded result for every
 data family, epilogue and C type, and refuse every mutant a subtly wrong NT GEMM kernel would produce (the list in that
-module).  The role tests/test_layernorm_ref_cpu.py has for LayerNorm."""
+module).  The role tests/test_layernorm_ref_cpu.py has for LayerNorm.  And the launcher's own plan query (avf_gemm_nt_plan: host
+code) confirms that every tile of the table is some shape's unforced pick."""
 import pytest
 import torch
 
@@ -93,3 +94,20 @@ def test_every_mutant_fails(name, family):
             continue
         with pytest.raises(AssertionError, match="error / bound above 1"):
             G.check_outputs(what, ref, *G.simulate(inp, f, f_ldc, mutant=name))
+
+
+def test_every_tile_of_the_table_is_some_shapes_own_plan():
+    """host code only: the tile ids the table holds (asked with each id forced) are exactly the ones tests/test_gpu_gemm_nt.py
+    lists, and each is what avf_gemm_nt_plan picks UNFORCED for some shape - a tile no input selects cannot sit in the table"""
+    import os
+    import avformer_amd as A
+    A._build.build()
+    held = G.tile_ids_held(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))["bf16"]
+    assert held == {1, 2, 5, 6}, held
+    picked = set()
+    for (m, n), tile in G.PLAN_SHAPES.items():
+        for k in (128, 512, 1536):
+            plan = A.ops.gemm_nt_plan(m, n, k)
+            assert plan["kind"] == 1 and plan["tile"] == (6 if tile is None else tile), (m, n, k, plan)
+            picked.add(plan["tile"])
+    assert picked == held, (picked, held)

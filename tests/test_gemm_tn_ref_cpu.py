@@ -79,7 +79,7 @@ def test_mutant_table_is_complete():
 
 
 # ------------------------------------------------------------------------------------------------
-# the launcher's own plan, asked in a child process per switch setting (AVF_TN_BIG / _WAVES / _XCD are read once per process)
+# the launcher's own plan, asked in a child process per switch setting (AVF_TN_BIG / _XCD are read once per process)
 _PLAN_CHILD = r"""
 import json, os, sys
 sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
@@ -117,7 +117,7 @@ _plans = {}
 def _child_plans(name):
     if name not in _plans:
         env = dict(os.environ, AVF_TUNING="1", **G.CHILDREN[name][0])
-        for k in ("AVF_TN_BIG", "AVF_TN_WAVES", "AVF_TN_XCD", "AVF_TN_SPLITS"):
+        for k in ("AVF_TN_BIG", "AVF_TN_XCD", "AVF_TN_SPLITS"):
             if k not in G.CHILDREN[name][0]:
                 env.pop(k, None)
         r = subprocess.run([sys.executable, "-c", _PLAN_CHILD, name], capture_output=True, text=True, env=env, cwd=REPO, timeout=300)
@@ -156,7 +156,7 @@ def test_plan_invariants_over_a_sweep(name):
         assert p["workspace_bytes"] >= (p["S"] * elems * 4 if p["S"] > 1 else 0), what
         assert sp is None or p["S"] == sp, what
         assert p["fold"] == (-1 if p["S"] == 1 else (p["S"] if p["S"] <= 8 else 0)), what
-        assert p["waves"] == (8 if (p["big"] or name == "waves8") else 4), what
+        assert p["waves"] == (8 if p["big"] else 4), what
         if not p["big"]:
             assert p["xcd_groups"] == 0 and p["blocks"] == p["tiles"] * p["S"], what
         else:

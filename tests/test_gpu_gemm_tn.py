@@ -4,8 +4,7 @@ tests/test_gemm_tn_ref_cpu.py shows without a device that it bites and that the 
 
 kernel                                            reached by                                             rows (gemm_tn_util)
 gemm_bf16_tn_kernel + fold_slabs_kernel           ops.gemm(trans_a=True, trans_b=False), S = 1, 3, 10, 32   SINGLE
-gemm_bf16_tn_group_kernel<2> (128 x 128, 4 waves) ops.gemm_tn_group, S = 1 .. 9, fold <2 .. 8> unforced     CHILDREN["default"]
-gemm_bf16_tn_group_kernel<4> (128 x 128, 8 waves) AVF_TN_BIG=0 AVF_TN_WAVES=8                               CHILDREN["waves8"]
+gemm_bf16_tn_group_kernel (128 x 128, 4 waves)    ops.gemm_tn_group, S = 1 .. 9, fold <2 .. 8> unforced     CHILDREN["default"]
 gemm_bf16_tn_group_big_kernel<3> (256 x 128)      AVF_TN_BIG=1 (and the heuristic's own pick), S = 1 .. 9:  CHILDREN["big"],
     runs of 0, 1, 2, 3, 4, 5 and 7 K-steps through the three-slot ring, xcd_groups 8, 4, 2, 1, -1;          CHILDREN["default"]
     tile-major ids with AVF_TN_XCD=0                                                                         CHILDREN["big_tile_major"]
@@ -17,14 +16,13 @@ views with 8 NaN pad columns), writes outputs that sit between sentinel guards (
 takes the group's split-K workspace at exactly the queried size from a NaN-prefilled parent between sentinel guards, and checks:
 every output finite, every element within the bound, "int" results equal to the fp64 product bit for bit, every guard intact, a
 second call returning the same bits.  Each case prints a line "TNSTAT {json}" with its worst error / bound ratio.  The switches
-AVF_TN_BIG / AVF_TN_WAVES / AVF_TN_XCD are read once per process: one child process per setting, one after the other, each
+AVF_TN_BIG / AVF_TN_XCD are read once per process: one child process per setting, one after the other, each
 under its own time limit, none started after one that failed; a child saves what the device returned and this process checks it.
 
-Worst error / bound ratios measured on an MI355X over the whole file (96 TNSTAT lines), per kernel and data family:
+Worst error / bound ratios measured on an MI355X over the whole file (88 TNSTAT lines), per kernel and data family:
   kernel                                  normal   wide     cancel   int
   gemm_bf16_tn_kernel (+ fold_slabs)      0.054    0.101    0.006    exact     (the two at 8 x 8 x 8; 0.025 and below from K = 64 on)
-  gemm_bf16_tn_group_kernel<2>            0.0033   0.0072   0.0018   exact
-  gemm_bf16_tn_group_kernel<4>            0.0024   0.0051   0.0014   exact
+  gemm_bf16_tn_group_kernel               0.0033   0.0072   0.0018   exact
   gemm_bf16_tn_group_big_kernel<3>        0.0023   0.0046   0.0012   exact
 No kernel fault, guard hit, NaN or differing second call was found.  The device uses far less of the bound than the fp32
 chain of the CPU test (0.08 / 0.25 / 0.05): the MFMA's 32-term sums and the long fp32 accumulation err far below their worst
@@ -197,7 +195,7 @@ def test_group_child(name, tmp_path):
     tag = list(G.CHILDREN).index(name)
     path = str(tmp_path / f"{name}.pt")
     env = dict(os.environ, AVF_TUNING="1", AVF_TEST_OUT=path, **env_extra)
-    for k in ("AVF_TN_BIG", "AVF_TN_WAVES", "AVF_TN_XCD", "AVF_TN_SPLITS"):
+    for k in ("AVF_TN_BIG", "AVF_TN_XCD", "AVF_TN_SPLITS"):
         if k not in env_extra:
             env.pop(k, None)
     try:
@@ -236,7 +234,7 @@ def test_group_child(name, tmp_path):
 
 
 def test_every_variant_was_reached():
-    """coverage by assertion, from the plans the cases above saw: both group tiles, 4 and 8 waves on the 128 x 128 one, every fold
+    """coverage by assertion, from the plans the cases above saw: both group tiles, every fold
     code, every block order of the 256 x 128 tile, a dead slab on every kernel, runs of 0, 1, 2, 3, 4, 5 and >= 7 K-steps through
     the three-slot ring, S = 1, 3, 10 and 32 on the single-problem path (runs last; needs the tests above to have run)"""
     assert G.WANT <= REACHED, sorted(G.WANT - REACHED)

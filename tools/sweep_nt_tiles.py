@@ -1,6 +1,6 @@
 """Times the bf16 NT GEMM on the layer's eight shapes (forward + dX) under the tile configuration AVF_NT_TILE forces.
 
-    for t in 0 1 2 3; do AVF_NT_TILE=$t python tools/sweep_nt_tiles.py --rows 10368; done
+    for t in 1 2 5; do AVF_TUNING=1 AVF_NT_TILE=$t python tools/sweep_nt_tiles.py --rows 10368; done
 """
 import argparse
 import os
