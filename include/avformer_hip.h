@@ -909,6 +909,37 @@ int avf_conv2d_nhwc_f32x3(const float* x, const void* w_hi, const void* w_lo, co
                           const float* residual, int relu, int k, int stride, float* out, int N, int H, int W, int Cin, int Cout,
                           void* stream);
 
+/* ---- data gradient of the frozen stages (csrc/conv_dgrad.hip, csrc/conv_dgrad_f32.hip) ---------------------------------------
+ * What trains pos_embedding and spatial_transformer behind the frozen layer4 (vformer.py:244-265): the gradient with respect to
+ * the INPUT of avf_conv2d_nhwc, with the identity add and the ReLU gate of BasicBlock's backward in its epilogue, and the
+ * backward of avf_avgpool_nhwc.  The weights are frozen: no weight gradient, no BatchNorm gradient.
+ *   wt [Cin, k, k, Cout] bf16: the image of fp32(w[co, ci, ky, kx] * scale[co]), one RNE rounding - the folded BatchNorm scale
+ *     is part of it, the shift has no gradient.  It is avf_conv_pack_weight's image of the transposed, pre-scaled weight
+ *     [Cin, Cout, k, k] (avf_conv_pack_weight_f32x3's hi / lo pair for the parity form); there is no pack entry of its own.
+ *   avf_conv2d_nhwc_dgrad: with pad = 1 for k = 3 and 0 for k = 1, Ho / Wo by avf_conv2d_nhwc's rule,
+ *       acc[n, iy, ix, ci] = sum over (ky, kx) with ty = iy + pad - ky, tx = ix + pad - kx, ty % stride == 0, tx % stride == 0,
+ *                            oy = ty / stride in [0, Ho), ox = tx / stride in [0, Wo), and co of
+ *                            gy[n, oy, ox, co] * wt[ci, ky, kx, co]
+ *       v   = acc + addend[n, iy, ix, ci]               (addend null: none)
+ *       out = gate[n, iy, ix, ci] > 0 ? v : 0           (gate null: v; a NaN gate gives 0)
+ *     A tap off the stride lattice or out of range counts as zero and is never read.  gy [N, Ho, Wo, Cout] fp32 (rounded to
+ *     bf16, RNE, as it is staged) or bf16; out [N, H, W, Cin] fp32 or bf16 (RNE); addend and gate, where given, have out's type
+ *     and shape.  k = 3 or 1, stride 1 or 2, Cout % 32 == 0 (a reduction chunk is 32 output channels of one tap), Cin % 16 == 0.
+ *     bf16 products accumulate in fp32 (v_mfma_f32_16x16x32_bf16); the epilogue is fp32.  Every operand 16-byte aligned; out may
+ *     not overlap an input.
+ *   avf_conv2d_nhwc_dgrad_f32x3: the same operation, rules and tiles in the parity arithmetic of avf_conv2d_nhwc_f32x3: every
+ *     map fp32, gy split into hi + lo as it is staged, wt_hi / wt_lo the split of fp32(w * scale), three bf16 products per pair.
+ *   avf_conv_dgrad_plan: the tile both run a shape on, avf_conv_plan's rule on N*H*W rows and Cin columns: *tile = its id
+ *     (0: 128 pixels x 64 channels, 1: 64 x 32), *tile_m / *tile_n its extent.  Same shape checks as the launch.
+ *   avf_avgpool_nhwc_bwd: out[n, p, c] = gate[n, p, c] > 0 ? dout[n, c] / HW : 0 (gate null: dout[n, c] / HW); dout [N, C] fp32,
+ *     gate (of out's type) and out [N, HW, C] fp32 or bf16; C % 8 == 0, every operand 16-byte aligned. */
+int avf_conv2d_nhwc_dgrad(const void* gy, int gy_dtype, const void* wt_packed, const void* addend, const void* gate, int k,
+                          int stride, void* out, int out_dtype, int N, int H, int W, int Cin, int Cout, void* stream);
+int avf_conv2d_nhwc_dgrad_f32x3(const float* gy, const void* wt_hi, const void* wt_lo, const float* addend, const float* gate, int k,
+                                int stride, float* out, int N, int H, int W, int Cin, int Cout, void* stream);
+int avf_conv_dgrad_plan(int N, int H, int W, int Cin, int Cout, int k, int stride, int* tile, int* tile_m, int* tile_n);
+int avf_avgpool_nhwc_bwd(const float* dout, const void* gate, void* out, int out_dtype, int64_t N, int HW, int C, void* stream);
+
 /* ---- frozen ResNet stem, forward only (csrc/stem.hip) -----------------------------------------------------------------------
  * What stands in front of layer1: conv1 (7x7, stride 2, pad 3, bias=False) - bn1 - relu - maxpool (3x3, stride 2, pad 1) of
  * ResFormer.forward (vformer.py:238-241) and of the audio stream's ResNet18 (audio.py:22-39, one input channel), in ONE launch

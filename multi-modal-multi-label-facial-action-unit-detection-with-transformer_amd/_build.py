@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "libavformer_hip.so"
-SOURCES = ["api.hip", "norm_elem.hip", "layernorm.hip", "gemm_f32.hip", "attn_f32.hip", "attn_f32_mfma.hip", "attn_f32x3.hip", "gemm_bf16.hip", "gemm_ws.hip", "gemm_mx8.hip", "attn_bf16.hip", "attn_bwd_merged.hip", "layer.hip", "optim.hip", "grad_control.hip", "layer_small.hip", "heads.hip", "task_loss.hip", "eval_metrics.hip", "mel.hip", "clip.hip", "augment.hip", "clip_bank.hip", "mel_bank.hip", "conv.hip", "conv_f32.hip", "stem.hip", "feature_bank.hip"]
+SOURCES = ["api.hip", "norm_elem.hip", "layernorm.hip", "gemm_f32.hip", "attn_f32.hip", "attn_f32_mfma.hip", "attn_f32x3.hip", "gemm_bf16.hip", "gemm_ws.hip", "gemm_mx8.hip", "attn_bf16.hip", "attn_bwd_merged.hip", "layer.hip", "optim.hip", "grad_control.hip", "layer_small.hip", "heads.hip", "task_loss.hip", "eval_metrics.hip", "mel.hip", "clip.hip", "augment.hip", "clip_bank.hip", "mel_bank.hip", "conv.hip", "conv_f32.hip", "conv_dgrad.hip", "conv_dgrad_f32.hip", "stem.hip", "feature_bank.hip"]
 ABI_HEADER = os.path.join(os.path.dirname(HERE), "include", "avformer_hip.h")  # the C ABI: every entry point's .hip includes it, _cabi.py reads it
-HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "mfma_frag.hpp"), os.path.join(CSRC, "gemm_nt.hpp"), os.path.join(CSRC, "gemm_dispatch.hpp"), os.path.join(CSRC, "attn_dispatch.hpp"), os.path.join(CSRC, "clip_source.hpp"), os.path.join(CSRC, "conv_common.hpp"), os.path.join(CSRC, "conv_kernel.hpp"), os.path.join(CSRC, "bf16x3.hpp"), os.path.join(CSRC, "attn_parity_kernel.hpp"),
+HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "mfma_frag.hpp"), os.path.join(CSRC, "gemm_nt.hpp"), os.path.join(CSRC, "gemm_dispatch.hpp"), os.path.join(CSRC, "attn_dispatch.hpp"), os.path.join(CSRC, "clip_source.hpp"), os.path.join(CSRC, "conv_common.hpp"), os.path.join(CSRC, "conv_kernel.hpp"), os.path.join(CSRC, "conv_dgrad_kernel.hpp"), os.path.join(CSRC, "bf16x3.hpp"), os.path.join(CSRC, "attn_parity_kernel.hpp"),
            os.path.join(CSRC, "clip_kernels.hpp"), os.path.join(CSRC, "augment_kernels.hpp"), os.path.join(CSRC, "mel_kernels.hpp"), ABI_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # per-source extra flags.  attn_bwd_merged.hip: MFMA results in architectural VGPRs (the kernel pins its long-lived

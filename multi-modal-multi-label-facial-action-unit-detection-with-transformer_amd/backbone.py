@@ -1,6 +1,8 @@
 """The frozen ResNet stages of the reference's S-Former (``ResFormer``, vformer.py:128-268; copied in sformer.py, tformer.py,
 dual_sformer.py): ``FrozenBasicBlock`` and ``FrozenResFormer``, and the audio stream's ResNet18 (``AudioModel``, audio.py:22-39):
-``FrozenAudioModel``; forward only.
+``FrozenAudioModel``.  Forward only, with one exception: ``FrozenResFormer(train_tokens=True)`` differentiates through the
+frozen ``layer4`` and ``avgpool`` (data gradients only, csrc/conv_dgrad.hip), so that ``pos_embedding`` and
+``spatial_transformer`` train on the hip backend.
 
 "Frozen" means eval-mode here: BatchNorm2d always uses its running statistics, whatever ``train()`` says.  That is exact for
 ``evaluate()`` (train.py:106-169) and whole-dataset inference (test_aff2.py); the reference itself runs the BatchNorm of its
@@ -20,8 +22,9 @@ launches is fp32 and every fp32 product runs as three bf16 MFMA products (bf16x3
 parity form: in this mode the stem is the torch definition in fp32, followed by one NCHW -> NHWC fp32 conversion, and
 ``stem="hip"`` is refused.
 
-The hip backend computes no gradients: with grad mode on and an input or parameter that requires grad, ``forward`` raises
-instead of silently cutting the graph."""
+By default the hip backend computes no gradients: with grad mode on and an input or parameter that requires grad, ``forward``
+raises instead of silently cutting the graph.  ``FrozenResFormer(train_tokens=True)`` is the opt-in: the stem and every stage
+stay frozen, and the gradient of the pooled features reaches the token section through ``FrozenBasicBlock.backward_nhwc``."""
 from __future__ import annotations
 
 from typing import Optional
@@ -91,7 +94,8 @@ class _FrozenBlock(nn.Module):
     zero-padded to 32, in the arithmetic ``conv_dtype`` names - their cache (version counters, a ``load_state_dict`` hook,
     ``refresh_weights``), ``set_conv_dtype``, the forward-only guard and the NCHW fp32 ``forward`` around ``forward_nhwc``.  A
     subclass sets ``inplanes`` / ``planes`` / ``stride`` / ``downsample`` and defines ``_pairs``, ``_forward_torch`` and
-    ``_forward_convs``."""
+    ``_forward_convs``.  A subclass with a backward (``FrozenBasicBlock``) also defines ``_forward_convs_saving`` and
+    ``backward_nhwc``; the packed data-gradient images (``_pack_dgrad``) sit in the same cache entry as the forward images."""
     expansion = 1
 
     def __init__(self, backend="torch", conv_dtype="bf16"):
@@ -133,8 +137,25 @@ class _FrozenBlock(nn.Module):
                     w = F.pad(w, (0, 0, 0, 0, 0, ci - w.shape[1], 0, co - w.shape[0]))
                     ts = [F.pad(t, (0, co - t.numel()), value=float(i == 3)) for i, t in enumerate(ts)]
                 packs.append(pack(w.float(), *[t.float() for t in ts], eps=bn.eps))
-            self._packed = (key, packs)
+            self._packed = (key, packs, {})  # {}: the data-gradient images of this key, packed when a backward first asks
         return self._packed[1]
+
+    def _pack_dgrad(self, device):
+        """one data-gradient image (``ops.conv_pack_weight_dgrad``; the (hi, lo) pair with ``conv_dtype="f32"``) per pair of
+        ``_pairs()``, channels zero-padded like the forward images and cached with them"""
+        self._pack(device)
+        cache = self._packed[2]
+        if "dgrad" not in cache:
+            images, pack = [], ops.conv_pack_weight_dgrad_f32 if self.conv_dtype == "f32" else ops.conv_pack_weight_dgrad
+            for conv, bn in self._pairs():
+                w, gamma, var = conv.weight.detach(), bn.weight.detach(), bn.running_var.detach()
+                co, ci = _pad_to(w.shape[0]), _pad_to(w.shape[1])
+                if (co, ci) != tuple(w.shape[:2]):  # zero weights and gamma = 0: the padded channels carry no gradient
+                    w = F.pad(w, (0, 0, 0, 0, 0, ci - w.shape[1], 0, co - w.shape[0]))
+                    gamma, var = F.pad(gamma, (0, co - gamma.numel())), F.pad(var, (0, co - var.numel()), value=1.0)
+                images.append(pack(w.float(), gamma.float(), var.float(), eps=bn.eps))
+            cache["dgrad"] = images
+        return cache["dgrad"]
 
     def forward_nhwc(self, x, out_dtype=torch.bfloat16):
         """x [N, H, W, pad32(inplanes)] bf16 or fp32 -> [N, Ho, Wo, pad32(expansion * planes)] in ``out_dtype``; with
@@ -143,6 +164,20 @@ class _FrozenBlock(nn.Module):
         f32 = self.conv_dtype == "f32"
         return self._forward_convs(x, self._pack(x.device), ops.conv2d_nhwc_f32 if f32 else ops.conv2d_nhwc,
                                    {} if f32 else {"out_dtype": out_dtype})
+
+    def forward_nhwc_saving(self, x, out_dtype=torch.bfloat16):
+        """``forward_nhwc`` with the same launches -> (y, saved): ``saved`` = (h, y, (H, W)), the maps the launches wrote anyway
+        (h: the block's inner ReLU output) and the input map's extent, what ``backward_nhwc`` takes"""
+        _no_grad_or_raise(self, x, type(self).__name__)
+        f32 = self.conv_dtype == "f32"
+        return self._forward_convs_saving(x, self._pack(x.device), ops.conv2d_nhwc_f32 if f32 else ops.conv2d_nhwc,
+                                          {} if f32 else {"out_dtype": out_dtype})
+
+    def _forward_convs_saving(self, x, p, conv, last):
+        raise NotImplementedError(f"{type(self).__name__} has no backward on the hip backend")
+
+    def backward_nhwc(self, gs, saved, x_gate=None, out_dtype=None):
+        raise NotImplementedError(f"{type(self).__name__} has no backward on the hip backend")
 
     def forward(self, x):
         if self.backend == "torch":
@@ -187,9 +222,34 @@ class FrozenBasicBlock(_FrozenBlock):
         return pairs
 
     def _forward_convs(self, x, p, conv, last):
+        return self._forward_convs_saving(x, p, conv, last)[0]
+
+    def _forward_convs_saving(self, x, p, conv, last):
         h = conv(x, *p[0], k=3, stride=self.stride, relu=True)
         identity = x if self.downsample is None else conv(x, *p[2], k=1, stride=self.stride)
-        return conv(h, *p[1], k=3, stride=1, residual=identity, relu=True, **last)
+        y = conv(h, *p[1], k=3, stride=1, residual=identity, relu=True, **last)
+        return y, (h, y, tuple(x.shape[1:3]))
+
+    def backward_nhwc(self, gs, saved, x_gate=None, out_dtype=None):
+        """The gradient for the block's input, [N, H, W, pad32(inplanes)], from ``gs`` [N, Ho, Wo, pad32(planes)]: the gradient
+        with respect to the block's pre-ReLU sum, i.e. the caller's dy already gated by y > 0.  ``saved`` comes from
+        ``forward_nhwc_saving``.  ``x_gate``: the block's input map when that map is itself a ReLU output (between blocks) - the
+        result is then gated by x_gate > 0 and is the ``gs`` of the block before; ``None`` leaves it ungated.  Three launches,
+        or two without a downsample (csrc/conv_dgrad.hip):
+            dh  = dgrad(conv2; gy = gs, gate = h)
+            add = dgrad(downsample; gy = gs) if the block has one, else gs
+            dx  = dgrad(conv1; gy = dh, addend = add, gate = x_gate)
+        ``out_dtype``: dx's type (default: x_gate's, else the map type of ``conv_dtype``); add and x_gate have it too, dh has
+        h's.  With ``conv_dtype="f32"`` every map is fp32.  The weights are frozen: nothing else has a gradient."""
+        h, _, in_hw = saved
+        f32 = self.conv_dtype == "f32"
+        dgrad, w = (ops.conv2d_nhwc_dgrad_f32 if f32 else ops.conv2d_nhwc_dgrad), self._pack_dgrad(gs.device)
+        if out_dtype is None:
+            out_dtype = x_gate.dtype if x_gate is not None else _map_dtype(self.conv_dtype)
+        mid, last = ({}, {}) if f32 else ({"out_dtype": h.dtype}, {"out_dtype": out_dtype})
+        dh = dgrad(gs, w[1], tuple(h.shape[1:3]), k=3, stride=1, gate=h, **mid)
+        add = gs if self.downsample is None else dgrad(gs, w[2], in_hw, k=1, stride=self.stride, **last)
+        return dgrad(dh, w[0], in_hw, k=3, stride=self.stride, addend=add, gate=x_gate, **last)
 
 
 class _Stage(nn.Sequential):
@@ -241,6 +301,32 @@ class _HipStem:
         return ops.stem_nchw(x.contiguous(), *self._stem_pack(x.device), pool=self._stem_pool)
 
 
+class _Layer4Pool(torch.autograd.Function):
+    """``FrozenResFormer.tokens_to_features`` with a backward: ``layer4`` with its ReLU maps kept, then the NHWC pool; backward
+    = the pool's backward gated by the last ReLU map, then the blocks in reverse, the last launch writing the fp32 gradient of
+    the transformer's output.  No host synchronisation; every buffer comes from torch's allocator."""
+
+    @staticmethod
+    def forward(ctx, t, stage, hw):
+        x = t.detach().contiguous().view(t.shape[0], hw[0], hw[1], t.shape[2])
+        saved = []
+        for blk in stage:
+            x, s = blk.forward_nhwc_saving(x)
+            saved.append(s)
+        ctx.stage, ctx.maps, ctx.t_shape = stage, saved, t.shape
+        return ops.avgpool_nhwc(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        blocks, saved = list(ctx.stage), ctx.maps
+        y = saved[-1][1]
+        g = ops.avgpool_nhwc_bwd(dout.float().contiguous(), y.shape[1] * y.shape[2], gate=y).view(y.shape)
+        for i in range(len(blocks) - 1, -1, -1):
+            g = blocks[i].backward_nhwc(g, saved[i], x_gate=saved[i - 1][1] if i else None, out_dtype=None if i else torch.float32)
+        return g.view(ctx.t_shape), None, None
+
+
 class FrozenResFormer(_HipStem, ResFormerTokens):
     """The whole S-Former, ``ResFormer(BasicBlock, layers)`` (vformer.py:168-268), with the reference's names - ``conv1``, ``bn1``,
     ``maxpool``, ``layer1`` .. ``layer4``, ``avgpool``, ``pos_embedding``, ``spatial_transformer.*`` - so that a reference checkpoint
@@ -255,10 +341,20 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
 
     ``conv_dtype="f32"`` (hip backend): the parity form of the conv stages (csrc/conv_f32.hip, bf16x3 products, fp32 maps
     throughout); the stem is the torch definition in fp32, followed by one NCHW -> NHWC fp32 conversion (``stem="hip"`` has no
-    parity form and is refused).  With ``compute_dtype="f32"`` the whole module then runs in parity arithmetic."""
+    parity form and is refused).  With ``compute_dtype="f32"`` the whole module then runs in parity arithmetic.
+
+    ``train_tokens=True`` trains ``pos_embedding`` and ``spatial_transformer`` on the hip backend.  The constructor freezes the
+    stem and the stages (``conv1``, ``bn1``, ``layer1`` .. ``layer4``: ``requires_grad_(False)``); ``forward`` then runs the stem
+    and ``layer1`` .. ``layer3`` under ``no_grad``, adds ``pos_embedding`` and runs ``spatial_transformer`` under autograd, and
+    differentiates ``layer4`` + ``avgpool`` with the data-gradient kernels (csrc/conv_dgrad.hip): gradient maps in bf16 with
+    ``conv_dtype="bf16"``, fp32 with ``"f32"``, the last launch writing the fp32 gradient the transformer's backward takes.
+    A stage parameter that requires grad again is refused by name, and so is an input that requires grad (the stem and
+    ``layer1`` .. ``layer3`` have no backward).  Under ``torch.no_grad()``, and with the default ``train_tokens=False``, every
+    path is the forward-only one."""
+    _STAGES = ("conv1", "bn1", "layer1", "layer2", "layer3", "layer4")
 
     def __init__(self, layers=(2, 2, 2, 2), backend="torch", in_channels=3, dropout=0.0, compute_dtype="bf16", stem="torch",
-                 conv_dtype="bf16"):
+                 conv_dtype="bf16", train_tokens=False):
         super().__init__(dropout=dropout, compute_dtype=compute_dtype)
         self.backend = _check_backend(backend)
         self.stem_backend = _check_stem(stem, backend)
@@ -276,6 +372,17 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
         for m in self.modules():                                                        # vformer.py:200-205
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+        self.train_tokens = False
+        self.set_train_tokens(train_tokens)
+
+    def set_train_tokens(self, flag):
+        """``True``: freeze the stem and the stages and let ``forward`` differentiate ``layer4`` + ``avgpool`` for the token
+        section (hip backend); ``False``: the forward-only module (parameters frozen earlier stay frozen)"""
+        self.train_tokens = bool(flag)
+        if self.train_tokens:
+            for name in self._STAGES:
+                getattr(self, name).requires_grad_(False)
+        return self
 
     def _make_layer(self, planes, blocks, stride=1):
         downsample = None
@@ -311,9 +418,12 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
     def nhwc_to_tokens(self, x):
         """hip: the stem's NHWC map (bf16; fp32 with ``conv_dtype="f32"``) -> layer1 .. layer3 -> ([B', h*w, 256] fp32 tokens +
         pos_embedding, (h, w))"""
+        t, hw = self._nhwc_to_raw_tokens(x)
+        return t + self.pos_embedding[:, :t.shape[1]], hw                         # vformer.py:253
+
+    def _nhwc_to_raw_tokens(self, x):
         x = self.layer3.forward_nhwc(self.layer2.forward_nhwc(self.layer1.forward_nhwc(x)), out_dtype=torch.float32)
-        t = x.view(x.shape[0], x.shape[1] * x.shape[2], x.shape[3])               # NHWC IS [B', tokens, C]: no permute
-        return t + self.pos_embedding[:, :t.shape[1]], (x.shape[1], x.shape[2])   # vformer.py:253
+        return x.view(x.shape[0], x.shape[1] * x.shape[2], x.shape[3]), (x.shape[1], x.shape[2])  # NHWC IS [B', tokens, C]: no permute
 
     def tokens_to_features(self, t, hw):
         """hip: the transformer's [B', h*w, 256] fp32 output -> layer4 -> avgpool -> [B', 512] fp32"""
@@ -328,9 +438,31 @@ class FrozenResFormer(_HipStem, ResFormerTokens):
             x = self.layer4(ResFormerTokens.forward(self, x))                     # vformer.py:245-261
             return torch.flatten(self.avgpool(x), 1)
         ops._need_cuda(x)
+        if self.train_tokens and torch.is_grad_enabled():
+            return self._forward_train_tokens(x)
         _no_grad_or_raise(self, x, "FrozenResFormer")
         t, hw = self.nhwc_to_tokens(self.stem_nhwc(x)) if self.stem_backend == "hip" else self.stages_to_tokens(self.stem(x))
         return self.tokens_to_features(self.spatial_transformer(t), hw)
+
+
+    def _forward_train_tokens(self, x):
+        """hip, ``train_tokens=True``, grad mode on: the frozen front under ``no_grad``, the token section under autograd,
+        ``layer4`` + ``avgpool`` through ``_Layer4Pool``"""
+        if x.requires_grad:
+            raise RuntimeError("FrozenResFormer(backend='hip') is forward-only: it computes no gradients for its input, which "
+                               "requires grad (train_tokens=True differentiates layer4 and avgpool for the token section only); "
+                               "backend='torch' differentiates")
+        for stage in self._STAGES:
+            for name, p in getattr(self, stage).named_parameters():
+                if p.requires_grad:
+                    raise RuntimeError(f"FrozenResFormer(train_tokens=True): parameter {stage}.{name} requires grad, but the stem and "
+                                       "the stages are frozen on the hip backend (data gradients only, no weight or BatchNorm "
+                                       "gradient) - requires_grad_(False) it, or use backend='torch'")
+        with torch.no_grad():
+            x = self.stem_nhwc(x) if self.stem_backend == "hip" else to_nhwc(self.stem(x), dtype=_map_dtype(self.conv_dtype))
+            t, hw = self._nhwc_to_raw_tokens(x)
+        t = t + self.pos_embedding[:, :t.shape[1]]                                # vformer.py:253, under autograd
+        return _Layer4Pool.apply(self.spatial_transformer(t), self.layer4, hw)
 
 
 class _FrozenResNet18(_HipStem, nn.Module):
@@ -413,10 +545,11 @@ class FrozenVideoModel(nn.Module):
     """``VideoModel`` (vformer.py:295-311) with its fc replaced by the identity, as avformer.py:61-66 uses it: clip [B, C, T, H, W]
     -> the last ``num_channels`` channels -> ``s_former`` -> ``t_former`` -> [B, 512]"""
 
-    def __init__(self, backend="torch", compute_dtype="bf16", stem="torch", conv_dtype="bf16"):
+    def __init__(self, backend="torch", compute_dtype="bf16", stem="torch", conv_dtype="bf16", train_tokens=False):
         super().__init__()
         from .heads import TFormer
-        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype, stem=stem, conv_dtype=conv_dtype)
+        self.s_former = FrozenResFormer(backend=backend, compute_dtype=compute_dtype, stem=stem, conv_dtype=conv_dtype,
+                                        train_tokens=train_tokens)
         self.t_former = TFormer(compute_dtype=compute_dtype)
         self.num_channels = 3
 

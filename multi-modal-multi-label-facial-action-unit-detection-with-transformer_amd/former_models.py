@@ -10,7 +10,7 @@ takes them as two modules, ``stem`` (frames [B', C, H, W] -> stage-3 feature map
 does.  Without a backbone the models consume what the backbone would produce (a [B', 256, 7, 7] map, ``tail`` = global
 average pool + a fixed channel tiling to 512 features), which is enough to drive the token path, the heads and the
 [B, 21] output contract.  ``backbone="resnet18_frozen"`` builds the stages themselves: ``backbone.FrozenResFormer``, the reference's whole
-``ResFormer`` in eval mode on the HIP conv kernels, forward only (csrc/conv.hip).  Module / parameter names follow the reference so that its checkpoints load with strict=False.
+``ResFormer`` in eval mode on the HIP conv kernels (csrc/conv.hip): forward only by default, and with ``train_tokens=True`` differentiated through the frozen ``layer4`` (csrc/conv_dgrad.hip) so that its token section trains.  Module / parameter names follow the reference so that its checkpoints load with strict=False.
 The small ``fc`` heads (BatchNorm1d / Linear) are plain PyTorch modules - plumbing either side of the hot path.
 
 ``vggformer`` (VGGVisualFormer, vggformer.py:323-421) is the fifth entry: ``VGGVisualFormerModel`` owns its backbone - the frozen
@@ -71,9 +71,10 @@ def _check_backbone_dtype(backbone, backbone_dtype):
     return backbone_dtype
 
 
-def _s_former(backbone, num_channels=3, backbone_dtype="bf16", **kw):
+def _s_former(backbone, num_channels=3, backbone_dtype="bf16", train_tokens=False, **kw):
     """the S-Former of a ``*former`` model: ``backbone=None`` or a ``(stem, tail)`` pair -> ``ResFormerShell``;
-    ``backbone="resnet18_frozen"`` -> ``backbone.FrozenResFormer`` on the HIP conv kernels (eval-mode stages, forward only), whose
+    ``backbone="resnet18_frozen"`` -> ``backbone.FrozenResFormer`` on the HIP conv kernels (eval-mode stages; forward only unless ``train_tokens=True``, which
+    trains ``pos_embedding`` and ``spatial_transformer`` behind the frozen stages), whose
     ``conv1`` takes the ``num_channels`` channels the modality selects (vformer.py:313-331); ``"resnet18_frozen_fused"`` -> the
     same with the stem on its HIP kernel too.  ``backbone_dtype``: ``"bf16"`` (default) or ``"f32"``, the frozen module's
     ``conv_dtype`` - ``"f32"`` runs its conv stages in the parity arithmetic (csrc/conv_f32.hip) and has no fused-stem form"""
@@ -83,7 +84,9 @@ def _s_former(backbone, num_channels=3, backbone_dtype="bf16", **kw):
             raise ValueError(f"backbone must be None, a (stem, tail) pair or one of {FROZEN_BACKBONES}, got {backbone!r}")
         from .backbone import FrozenResFormer
         return FrozenResFormer(backend="hip", in_channels=num_channels, stem="hip" if backbone.endswith("_fused") else "torch",
-                               conv_dtype=backbone_dtype, **kw)
+                               conv_dtype=backbone_dtype, train_tokens=train_tokens, **kw)
+    if train_tokens:
+        raise ValueError(f"train_tokens=True is the frozen backbones' switch: backbone must be one of {FROZEN_BACKBONES}, got {backbone!r}")
     return ResFormerShell(backbone, **kw)
 
 
@@ -114,11 +117,11 @@ class SpatialFormerModel(_FormerTask):
     """registry name ``sformer`` (sformer.py:338-382): per-frame features -> fc head, AU logits from ``AU_former``"""
 
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
-                 backbone_dtype="bf16"):
+                 backbone_dtype="bf16", train_tokens=False):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.base_model = _s_former(backbone, self.num_channels, backbone_dtype, dropout=0.2, compute_dtype=compute_dtype)
+        self.base_model = _s_former(backbone, self.num_channels, backbone_dtype, train_tokens, dropout=0.2, compute_dtype=compute_dtype)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype)
@@ -140,9 +143,9 @@ class SpatialFormerModel(_FormerTask):
 
 
 class _VideoModel(nn.Module):
-    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype, num_channels=3, backbone_dtype="bf16"):
+    def __init__(self, backbone, temporal_dim, au_tokens, compute_dtype, num_channels=3, backbone_dtype="bf16", train_tokens=False):
         super().__init__()
-        self.s_former = _s_former(backbone, num_channels, backbone_dtype, compute_dtype=compute_dtype)
+        self.s_former = _s_former(backbone, num_channels, backbone_dtype, train_tokens, compute_dtype=compute_dtype)
         self.au_head = AU_former(dropout=0.2, compute_dtype=compute_dtype) if au_tokens else None
         self.t_former = TFormer(dim=temporal_dim, compute_dtype=compute_dtype)
 
@@ -158,11 +161,11 @@ class VisualFormerModel(_FormerTask):
     """registry name ``vformer`` (vformer.py:358-387): S-Former frames -> ``TFormer`` over 16 frames -> fc head"""
 
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
-                 backbone_dtype="bf16"):
+                 backbone_dtype="bf16", train_tokens=False):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.video_model = _VideoModel(backbone, 512, False, compute_dtype, self.num_channels, backbone_dtype)
+        self.video_model = _VideoModel(backbone, 512, False, compute_dtype, self.num_channels, backbone_dtype, train_tokens)
         self.task, self.modes = task, ["clip"]
         self.fc = _fc_head(512)
         self._init_task_losses(task_losses, REFERENCE_TASK_LOSSES['vformer'])
@@ -219,11 +222,11 @@ class SpatialTemporalFormerModel(_FormerTask):
     from ``tformer_AU_head`` on the [B, 12, 128] view of the temporal feature"""
 
     def __init__(self, modality='A;V;M', video_pretrained=True, task='EX', backbone=None, compute_dtype="bf16", task_losses="plain",
-                 backbone_dtype="bf16"):
+                 backbone_dtype="bf16", train_tokens=False):
         super().__init__()
         self.has_backbone = backbone is not None
         self._config(modality, task)
-        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype, self.num_channels, backbone_dtype)
+        self.video_model = _VideoModel(backbone, 128 * 12, True, compute_dtype, self.num_channels, backbone_dtype, train_tokens)
         self.task, self.modes = task, ["clip"]
         self.au_head = tformer_AU_head(dropout=0.2, compute_dtype=compute_dtype)
         self.fc = _fc_head(128 * 12)

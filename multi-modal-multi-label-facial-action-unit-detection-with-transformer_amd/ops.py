@@ -1582,6 +1582,107 @@ def avgpool_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return out
 
 
+# data gradient of the frozen stages (csrc/conv_dgrad.hip; csrc/conv_dgrad_f32.hip: the same kernel in the parity arithmetic) ------
+def _conv_pack_dgrad(images: int, w, gamma, running_var, eps):
+    """the body of ``conv_pack_weight_dgrad`` (images = 1) and ``conv_pack_weight_dgrad_f32`` (2): the forward pack kernels run on
+    the transposed weight with the folded BatchNorm scale multiplied in -> [image [Cin, k*k*Cout], ...]"""
+    _need_cuda(w, gamma, running_var)
+    w, gamma, var = [t.detach().contiguous() for t in (w, gamma, running_var)]
+    assert w.dtype == gamma.dtype == var.dtype == torch.float32 and w.dim() == 4 and w.shape[2] == w.shape[3]
+    Cout, Cin = w.shape[:2]
+    assert gamma.numel() == var.numel() == Cout
+    scale = (gamma.double() / torch.sqrt(var.double() + float(eps))).float()   # what avf_conv_pack_weight folds (fp64 -> fp32)
+    wt = (w * scale.view(Cout, 1, 1, 1)).transpose(0, 1).contiguous()          # fp32(w * scale), [Cin, Cout, k, k]
+    one, zero = torch.ones(Cin, dtype=torch.float32, device=w.device), torch.zeros(Cin, dtype=torch.float32, device=w.device)
+    return _conv_pack(images, wt, one, zero, zero, one, 0.0)[0]
+
+
+def conv_pack_weight_dgrad(w: torch.Tensor, gamma: torch.Tensor, running_var: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """nn.Conv2d weight [Cout, Cin, k, k] fp32 + the BatchNorm2d behind it -> wt [Cin, k*k*Cout] bf16, the image of
+    fp32(w[co, ci, ky, kx] * scale[co]) ordered tap-major / output-channel-minor, one RNE rounding, for ``conv2d_nhwc_dgrad``.
+    scale = gamma / sqrt(running_var + eps) as ``conv_pack_weight`` folds it; the shift has no gradient."""
+    return _conv_pack_dgrad(1, w, gamma, running_var, eps)[0]
+
+
+def conv_pack_weight_dgrad_f32(w: torch.Tensor, gamma: torch.Tensor, running_var: torch.Tensor, eps: float = 1e-5):
+    """``conv_pack_weight_dgrad`` for ``conv2d_nhwc_dgrad_f32``: -> (wt_hi, wt_lo), the hi / lo split of fp32(w * scale)"""
+    return tuple(_conv_pack_dgrad(2, w, gamma, running_var, eps))
+
+
+def conv_dgrad_plan(N: int, H: int, W: int, Cin: int, Cout: int, k: int, stride: int = 1) -> dict:
+    """The tile ``conv2d_nhwc_dgrad`` runs this shape on (avf_conv_dgrad_plan; H, W the INPUT map's): dict(tile = 0 | 1, tile_m,
+    tile_n).  Raises on a shape the kernel does not take."""
+    out = [C.c_int(-1) for _ in range(3)]
+    _lib.check(_lib.load().avf_conv_dgrad_plan(int(N), int(H), int(W), int(Cin), int(Cout), int(k), int(stride), *[C.byref(o) for o in out]),
+               "conv_dgrad_plan")
+    return dict(tile=out[0].value, tile_m=out[1].value, tile_n=out[2].value)
+
+
+def _conv2d_dgrad(name: str, gy, ws, in_hw, k, stride, addend, gate, out, out_dtype):
+    """the body of ``conv2d_nhwc_dgrad`` (ws = (wt,)) and ``conv2d_nhwc_dgrad_f32`` (ws = (wt_hi, wt_lo); the maps fp32): shapes /
+    contiguity / dtypes, allocation, the call"""
+    f32 = len(ws) == 2
+    _need_cuda(gy, *ws, addend, gate, out)
+    N, Ho, Wo, Cout = gy.shape
+    H, W = in_hw
+    Cin = ws[0].shape[0]
+    if (Ho, Wo) != conv_out_hw(H, W, k, stride):
+        raise ValueError(f"{name}: a {H} x {W} input map gives a {conv_out_hw(H, W, k, stride)} output at k={k}, stride={stride}; gy is "
+                         f"{tuple(gy.shape)}")
+    if out is None:
+        out = torch.empty((N, H, W, Cin), dtype=torch_dtype(out_dtype), device=gy.device)
+    wnames = ("wt_hi", "wt_lo") if f32 else ("wt",)
+    for nm, t, shape, dt in ([("gy", gy, (N, Ho, Wo, Cout), torch.float32 if f32 else gy.dtype)] +
+                             [(nm, t, (Cin, k * k * Cout), torch.bfloat16) for nm, t in zip(wnames, ws)] +
+                             [(nm, t, (N, H, W, Cin), out.dtype) for nm, t in (("addend", addend), ("gate", gate), ("out", out))]):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != dt):
+            raise ValueError(f"{name}: {nm} must be a contiguous {shape} {dt} tensor (got {tuple(t.shape)}, strides {t.stride()}, {t.dtype})")
+    if f32 and out.dtype != torch.float32:
+        raise ValueError(f"{name}: out must be fp32 (got {out.dtype})")
+    ptrs, geom = [_ptr(t) for t in (*ws, addend, gate)], (N, H, W, Cin, Cout, _stream())
+    if f32:
+        rc = _lib.load().avf_conv2d_nhwc_dgrad_f32x3(_ptr(gy), *ptrs, int(k), int(stride), _ptr(out), *geom)
+    else:
+        rc = _lib.load().avf_conv2d_nhwc_dgrad(_ptr(gy), avf_dtype(gy.dtype), *ptrs, int(k), int(stride), _ptr(out), avf_dtype(out.dtype), *geom)
+    _lib.check(rc, name)
+    return out
+
+
+def conv2d_nhwc_dgrad(gy: torch.Tensor, wt: torch.Tensor, in_hw: Tuple[int, int], k: int, stride: int = 1,
+                      addend: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      out_dtype=torch.bfloat16) -> torch.Tensor:
+    """The gradient of ``conv2d_nhwc`` with respect to its input (avf_conv2d_nhwc_dgrad): gy [N, Ho, Wo, Cout] fp32 or bf16, wt
+    from ``conv_pack_weight_dgrad``, ``in_hw`` = (H, W) of the input map -> gate > 0 ? dx + addend : 0, [N, H, W, Cin] fp32 or
+    bf16; addend / gate (optional) have out's shape and type.  The weights are frozen: no weight or BatchNorm gradient."""
+    return _conv2d_dgrad("conv2d_nhwc_dgrad", gy, (wt,), in_hw, k, stride, addend, gate, out, out_dtype)
+
+
+def conv2d_nhwc_dgrad_f32(gy: torch.Tensor, wt_split, in_hw: Tuple[int, int], k: int, stride: int = 1,
+                          addend: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``conv2d_nhwc_dgrad`` in the parity arithmetic (avf_conv2d_nhwc_dgrad_f32x3): every map fp32, ``wt_split`` = (wt_hi, wt_lo)
+    from ``conv_pack_weight_dgrad_f32``, three bf16 MFMA products per fp32 product (bf16x3, oracle/bf16x3.py)."""
+    wt_hi, wt_lo = wt_split
+    return _conv2d_dgrad("conv2d_nhwc_dgrad_f32", gy, (wt_hi, wt_lo), in_hw, k, stride, addend, gate, out, torch.float32)
+
+
+def avgpool_nhwc_bwd(dout: torch.Tensor, hw: int, gate: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     out_dtype=torch.bfloat16) -> torch.Tensor:
+    """The backward of ``avgpool_nhwc`` behind a ReLU (avf_avgpool_nhwc_bwd): dout [N, C] fp32 -> out[n, p, c] = gate[n, p, c] > 0 ?
+    dout[n, c] / hw : 0, [N, hw, C] fp32 or bf16; gate (optional: no gating) is a contiguous [N, ..., C] map of out's type."""
+    _need_cuda(dout, gate, out)
+    N, Cn = dout.shape
+    if out is None:
+        out = torch.empty((N, int(hw), Cn), dtype=gate.dtype if gate is not None else torch_dtype(out_dtype), device=dout.device)
+    if dout.dtype != torch.float32 or not dout.is_contiguous() or not out.is_contiguous() or out.numel() != N * hw * Cn:
+        raise ValueError(f"avgpool_nhwc_bwd: dout must be a contiguous [N, C] fp32 tensor and out a contiguous [N, {hw}, C] one")
+    if gate is not None and (gate.dtype != out.dtype or not gate.is_contiguous() or gate.numel() != out.numel()):
+        raise ValueError(f"avgpool_nhwc_bwd: gate must be a contiguous {out.dtype} tensor of out's size (got {tuple(gate.shape)}, {gate.dtype})")
+    _lib.check(_lib.load().avf_avgpool_nhwc_bwd(_ptr(dout), _ptr(gate), _ptr(out), avf_dtype(out.dtype), N, int(hw), Cn, _stream()),
+               "avgpool_nhwc_bwd")
+    return out
+
+
 # frozen ResNet stem (csrc/stem.hip) -------------------------------------------------------------------
 STEM_COUT = 64
 

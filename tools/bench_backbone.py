@@ -35,7 +35,18 @@ The parity form of the conv stages (conv_dtype="f32", csrc/conv_f32.hip: fp32 ma
 against the throughput form (conv_dtype="bf16"), both FrozenResFormer(backend="hip", stem="torch"), in one process, the arms
 alternated: the same three sections, then every distinct conv shape of the stages alone on avf_conv2d_nhwc (bf16 in, bf16 out)
 and on avf_conv2d_nhwc_f32x3, alternated per shape.  The errors are against arm a (backend="torch").  Writes
-<out-dir>/backbone_f32.json."""
+<out-dir>/backbone_f32.json.
+
+    python tools/bench_backbone.py --train-tokens [--frames 1024 16] [--groups 7] [--calls 5] [--warmup 2]
+
+Training the token section behind the frozen layer4 (FrozenResFormer(train_tokens=True), csrc/conv_dgrad.hip): forward + backward
+of the whole module on the hip backend against backend="torch" (fp32 NCHW autograd through layer4), both with the stem and the
+stages frozen, in one process, the arms alternated; the forward with train_tokens=True under no_grad against the default
+forward (the same launches: the difference belongs inside the spread of the two); then the five data-gradient launches of
+layer4's backward and the pool backward alone, each with the FLOPs of its live taps (2 * N*Ho*Wo * k*k * Cin * Cout) as a share
+of the bf16 MFMA peak, the bytes it must move as a share of the HBM rate, and which of the two bounds it.  The launches are
+timed with device events around back-to-back calls of one launch, not with a profiler.  Writes
+<out-dir>/backbone_token_grad.json."""
 import argparse
 import copy
 import json
@@ -58,13 +69,17 @@ def main():
     ap.add_argument("--stem", action="store_true", help="time the stem arms instead (profiles/ab/backbone_stem.json)")
     ap.add_argument("--conv-dtype", choices=("bf16", "f32"), default="bf16",
                     help="f32: time the parity form of the conv stages against the bf16 form instead (profiles/ab/backbone_f32.json)")
+    ap.add_argument("--train-tokens", action="store_true",
+                    help="time forward + backward with train_tokens=True against backend='torch' (profiles/ab/backbone_token_grad.json)")
     ap.add_argument("--name", default=None)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "ab"))
     args = ap.parse_args()
     if args.groups < 5:
         ap.error("--groups must be at least 5 (the result is a median)")
     if args.name is None:
-        args.name = "backbone_stem" if args.stem else "backbone_f32" if args.conv_dtype == "f32" else "backbone_frozen"
+        args.name = "backbone_token_grad" if args.train_tokens else "backbone_stem" if args.stem else "backbone_f32" if args.conv_dtype == "f32" else "backbone_frozen"
+    if args.train_tokens:
+        return train_tokens_main(args)
     if args.stem:
         return stem_main(args)
     if args.conv_dtype == "f32":
@@ -390,6 +405,118 @@ def conv_dtype_main(args):
         print(json.dumps({"frames": Bp, "median_ms_per_call": r["median_ms_per_call"], "f32_over_bf16": r["f32_over_bf16"],
                           "rel_fro_vs_torch_backend": r["rel_fro_vs_torch_backend"]}))
         for s in r["conv_shapes"]:
+            print(json.dumps(s))
+
+
+PEAK_HBM = 8.0e12  # bytes / s
+
+
+def train_tokens_main(args):
+    import torch
+    import avformer_amd as A
+    from tools.ab_bench import box_id
+    from tools.bench_mel import shader_clock
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_backbone.py measures on the GPU; no device found")
+    dev, ops = torch.device("cuda:0"), A.ops
+    torch.manual_seed(0)
+    m_t = A.FrozenResFormer(backend="torch", train_tokens=True).to(dev).eval()
+    m_h = copy.deepcopy(m_t).set_backend("hip")
+    m_d = copy.deepcopy(m_t).set_backend("hip").set_train_tokens(False)  # the forward-only module (everything frozen above stays so)
+
+    def step(m, x, w):
+        for p in m.parameters():
+            p.grad = None
+        (m(x) * w).sum().backward()
+
+    def window(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def alternate(arms, calls):
+        for fn in arms.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        runs = {k: [] for k in arms}
+        for _ in range(args.groups):
+            for k, fn in arms.items():
+                runs[k].append(round(window(fn, calls), 5))
+        return runs
+
+    def no_grad(m, x):
+        with torch.no_grad():
+            return m(x)
+
+    clock_before = shader_clock()
+    result = {}
+    for Bp in args.frames:
+        x = torch.randn(Bp, 3, args.size, args.size, device=dev)
+        w = torch.randn(Bp, 512, device=dev)
+        runs = alternate({"hip_fwd_bwd": lambda: step(m_h, x, w), "torch_fwd_bwd": lambda: step(m_t, x, w)}, args.calls)
+        step(m_h, x, w)
+        g_h = torch.cat([p.grad.flatten() for p in m_h.parameters() if p.grad is not None])
+        step(m_t, x, w)
+        g_t = torch.cat([p.grad.flatten() for p in m_t.parameters() if p.grad is not None])
+        runs.update(alternate({"fwd_no_grad_train_tokens": lambda: no_grad(m_h, x), "fwd_no_grad_default": lambda: no_grad(m_d, x),
+                               "fwd_no_grad_default_again": lambda: no_grad(m_d, x)}, args.calls))
+        med = {k: statistics.median(v) for k, v in runs.items()}
+        # layer4's backward, launch by launch, in the order it runs: the maps bf16, the last launch's output fp32
+        hh = (args.size // 16, args.size // 16)
+        ho = ((hh[0] - 1) // 2 + 1, (hh[1] - 1) // 2 + 1)
+        launches = [("block2.conv2", ho, 512, 512, 3, 1, False, True, torch.bfloat16), ("block2.conv1", ho, 512, 512, 3, 1, True, True, torch.bfloat16),
+                    ("block1.conv2", ho, 512, 512, 3, 1, False, True, torch.bfloat16), ("block1.downsample", hh, 256, 512, 1, 2, False, False, torch.float32),
+                    ("block1.conv1", hh, 256, 512, 3, 2, True, False, torch.float32)]
+        per, n = [], 20 if Bp <= 64 else 5
+        dout = torch.randn(Bp, 512, device=dev)
+        gate = torch.randn(Bp, ho[0] * ho[1], 512, device=dev).clamp_min(0).bfloat16()
+        out = ops.avgpool_nhwc_bwd(dout, ho[0] * ho[1], gate=gate)
+        ms = statistics.median(window(lambda: ops.avgpool_nhwc_bwd(dout, ho[0] * ho[1], gate=gate, out=out), n) for _ in range(5))
+        nbytes = dout.numel() * 4 + gate.numel() * 2 + out.numel() * 2
+        per.append({"launch": "avgpool_bwd", "ms": round(ms, 5), "bytes": nbytes, "hbm_fraction": round(nbytes / (ms * 1e-3) / PEAK_HBM, 4),
+                    "bound": "memory (no arithmetic to speak of)"})
+        for name, (H, W), Cin, Cout, k, s, add, gated, odt in launches:
+            oh, ow = ops.conv_out_hw(H, W, k, s)
+            gy = torch.randn(Bp, oh, ow, Cout, device=dev).bfloat16()
+            wt = torch.randn(Cin, k * k * Cout, device=dev).bfloat16()
+            a = torch.randn(Bp, H, W, Cin, device=dev).to(odt) if add else None
+            g = torch.randn(Bp, H, W, Cin, device=dev).clamp_min(0).to(odt) if gated else None
+            o = ops.conv2d_nhwc_dgrad(gy, wt, (H, W), k, s, addend=a, gate=g, out_dtype=odt)
+            ms = statistics.median(window(lambda: ops.conv2d_nhwc_dgrad(gy, wt, (H, W), k, s, addend=a, gate=g, out=o), n) for _ in range(5))
+            flops = 2.0 * Bp * oh * ow * k * k * Cin * Cout
+            nbytes = sum(t.numel() * t.element_size() for t in (gy, wt, a, g, o) if t is not None)
+            t_mfma, t_hbm = flops / PEAK_BF16 * 1e3, nbytes / PEAK_HBM * 1e3
+            per.append({"launch": name, "gy": [Bp, oh, ow, Cout], "out": [Bp, H, W, Cin], "k": k, "stride": s, "addend": add, "gate": gated,
+                        "tile": ops.conv_dgrad_plan(Bp, H, W, Cin, Cout, k, s)["tile"], "ms": round(ms, 5), "live_tap_flops": flops,
+                        "issued_flops": 2.0 * Bp * H * W * k * k * Cin * Cout, "bytes": nbytes,
+                        "mfma_fraction_of_bf16_peak": round(flops / (ms * 1e-3) / PEAK_BF16, 4),
+                        "hbm_fraction": round(nbytes / (ms * 1e-3) / PEAK_HBM, 4),
+                        "bound": ("launch latency" if ms < 0.02 and max(t_mfma, t_hbm) < 0.25 * ms else "mfma" if t_mfma >= t_hbm else "memory")})
+            del gy, wt, a, g, o
+        result[str(Bp)] = {"ms_per_call": runs, "median_ms_per_call": med,
+                           "spread_ms_max_minus_min": {k: round(max(v) - min(v), 5) for k, v in runs.items()},
+                           "torch_over_hip_fwd_bwd": round(med["torch_fwd_bwd"] / med["hip_fwd_bwd"], 3),
+                           "fwd_no_grad_train_tokens_minus_default_ms": round(med["fwd_no_grad_train_tokens"] - med["fwd_no_grad_default"], 5),
+                           "fwd_no_grad_default_a_a_ms": round(abs(med["fwd_no_grad_default_again"] - med["fwd_no_grad_default"]), 5),
+                           "grad_rel_fro_hip_vs_torch": float((g_h - g_t).norm() / g_t.norm()), "backward_launches": per}
+        del x, w
+    out = {"name": args.name, "frame_counts": args.frames, "size": args.size, "box": box_id(), "clock_before": clock_before,
+           "clock_after": shader_clock(), "device": torch.cuda.get_device_name(0), "alternations": args.groups,
+           "calls_per_group": args.calls, "warmup_calls": args.warmup, "bf16_peak_flops_assumed": PEAK_BF16, "hbm_bytes_per_s_assumed": PEAK_HBM,
+           "launch": "eager, device events around the calls, inputs already on the device; per-launch times: device events around "
+                     "back-to-back calls of one launch (no profiler pass)", "frames": result}
+    os.makedirs(args.out_dir, exist_ok=True)
+    with open(os.path.join(args.out_dir, args.name + ".json"), "w") as f:
+        json.dump(out, f, indent=1)
+    for Bp, r in result.items():
+        print(json.dumps({"frames": Bp, "median_ms_per_call": r["median_ms_per_call"], "torch_over_hip_fwd_bwd": r["torch_over_hip_fwd_bwd"],
+                          "grad_rel_fro_hip_vs_torch": r["grad_rel_fro_hip_vs_torch"]}))
+        for s in r["backward_launches"]:
             print(json.dumps(s))
 
 
